@@ -5,11 +5,15 @@ A step = one pass of the hot path over the resident tables: q1(lineitem), q3(cus
 lineitem), q5(six tables), through the public decorator API (front end -> planner -> C ABI -> HIP
 kernels), result materialised on the host.  Inputs are synthetic (sdqlpy_amd/tpch.py, seed fixed)
 and already resident in HBM when the timed region starts.  rows/sec = rows of every table scanned
-by the step / step time.  `--extra-queries` (q6, q9: BASELINE configs[0] and [4]) are measured in the
-same run with the same protocol after the timed region; they are reported per query and are not part
-of `value`.
+by the step / step time.  A plain run sets up, warms up, times `--steps` steps and prints the line
+(`value`, `ms_per_step`: one timed step's milliseconds); `--dump-outputs DIR` also writes what the
+last timed step returned (output_arrays).  Everything else is measured with `--full`, after the
+timed region: `--extra-queries` (q6, q9: BASELINE configs[0] and [4]) with the same protocol,
+reported per query and not part of `value`; the per-kernel, roofline, steady-state, reference-width,
+scan-form and hash-path legs; the results against the reference's and the CPU baseline.
 
-    python bench.py                       # 1 GPU, defaults finish in a few minutes
+    python bench.py                       # 1 GPU, the headline figure only
+    python bench.py --full                # ... and every other figure of the line (a few minutes)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py --gpus N              # no launcher: bench.py starts its N ranks itself (spawn_ranks) and relays rank 0's line
     ... bench.py --gpus 8 --global-sf 100     # BASELINE configs[3] / [4]: SF=100 over the 8 GPUs
@@ -18,7 +22,7 @@ N > 1 is weak scaling by default (every rank holds an SF=10 shard of a global SF
 shards by rows, q5 runs the chain plan, q3 is the partitioned join of sdqlpy_amd/dist.py.  The timed
 step HASH-partitions q3 on o_orderkey — build survivors and filtered probe rows really travel through
 the RCCL all-to-all — because that is the redistribution step the metric names; the range shortcut
-(dbgen-clustered shards: nothing moves) is timed beside it and reported, not counted in `value`.
+(dbgen-clustered shards: nothing moves) is timed beside it with `--full`, not counted in `value`.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -63,6 +67,12 @@ def parse(argv=None):
     ap.add_argument("--no-hash-path", action="store_true", help="skip the leg that prices the open-addressing layouts (direct layouts off; Q3 on keys beyond 2^40 in shuffled rows)")
     ap.add_argument("--no-scan-form", action="store_true", help="skip the leg that re-runs the step with every loop streaming every row (no driven walk, no clustered pack, no delta twins)")
     ap.add_argument("--no-reference-width", action="store_true", help="skip the leg that re-runs q1/q3/q6 on the reference's 8-byte columns (twins and codes off)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, measure and check everything else the line can report: the extra queries, the "
+                    "evented and per-query repeats, per-kernel and roofline figures, the steady-state, reference-width, scan-form and hash-path legs, "
+                    "q3's exchange both ways, HBM use, the results against the reference's and the CPU baseline (the --no-* options above and "
+                    "--extra-queries / --steady-steps apply to it).  Without it a run sets up, warms up, times --steps steps and prints `value`")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what each query of the LAST timed step returned as DIR/<query>_<column>.npy "
+                    "(float64; rows sorted by their exact columns; text as one code point per element)")
     return ap.parse_args(argv)
 
 
@@ -187,7 +197,7 @@ def main(argv=None, hooks=None):
     queries = [q for q in args.queries.split(",") if q]
     world = int(os.environ.get("WORLD_SIZE", "1"))
     extra = args.extra_queries if args.extra_queries is not None else ("q6,q9" if world == 1 else "")
-    extra = [q for q in extra.split(",") if q and q not in queries]
+    extra = [q for q in extra.split(",") if q and q not in queries] if args.full else []
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.share_gpu:
@@ -246,7 +256,8 @@ def main(argv=None, hooks=None):
         from sdqlpy_amd import dist as sdist
         trivial = None if world > 1 else (not args.trivial_collectives)
         runner = sdist.DistributedRunner(eng, rank, world, partition=args.partition, skip_trivial=trivial)
-        runner_range = sdist.DistributedRunner(eng, rank, world, partition="auto", skip_trivial=trivial)      # the clustered-shard shortcut, timed beside
+        if args.full:
+            runner_range = sdist.DistributedRunner(eng, rank, world, partition="auto", skip_trivial=trivial)      # the clustered-shard shortcut, timed beside
         run_query = lambda q: runner.run(q, db)           # noqa: E731
     else:
         run_query = lambda q: Q.run(q, db)                # noqa: E731
@@ -268,12 +279,12 @@ def main(argv=None, hooks=None):
         columns no earlier query uploaded, narrow / byte twins, dictionaries, delta twins, run indexes, row packs (in row order or
         clustered), min / max and ordering facts, plan lowering, hiprtc — and the HBM it leaves resident beside the columns."""
         def in_use():
-            if device != "cuda":
+            if device != "cuda" or not args.full:
                 return 0
             free_b, total_b = torch.cuda.mem_get_info(local_rank)
             return total_b - free_b
         use0, res0 = in_use(), int(eng.resident_bytes)
-        prof = device == "cuda" and not use_dist
+        prof = device == "cuda" and not use_dist and args.full
         if prof:
             eng.ctx.set_profiling(2, only=None)
         tq = time.perf_counter()
@@ -307,18 +318,19 @@ def main(argv=None, hooks=None):
     # the step's DOMINANT kernel: the longest single launch over ALL queries of the step, found by one fully evented run of each query
     # before the timed region (its name depends on the route the planner took: a kernel specialised at run time on the loop — xk_* —
     # or a fixed-shape one — k_*).  Q1's streaming kernel — the north-star's "Q1 at >= 60 % of the roofline" — is priced the same way
-    # beside it as `roofline.q1` when it is not the dominant one.
-    longest = {}
-    for q in queries:
-        eng.ctx.set_profiling(2, only=None)
-        r = run_query(q)
-        r.wait() if hasattr(r, "wait") else None
-        barrier()
-        launches_q = eng.ctx.profile()
-        eng.ctx.set_profiling(0)
-        longest[q] = max(launches_q, key=lambda kv: kv[1]) if launches_q else (DOMINANT[q][0], 0.0)
-    dom_q = max(queries, key=lambda q: longest[q][1])
-    dom_kernel = longest[dom_q][0]
+    # beside it as `roofline.q1` when it is not the dominant one.  (--full only: a plain run events nothing.)
+    longest, dom_q, dom_kernel = {}, None, None
+    if args.full:
+        for q in queries:
+            eng.ctx.set_profiling(2, only=None)
+            r = run_query(q)
+            r.wait() if hasattr(r, "wait") else None
+            barrier()
+            launches_q = eng.ctx.profile()
+            eng.ctx.set_profiling(0)
+            longest[q] = max(launches_q, key=lambda kv: kv[1]) if launches_q else (DOMINANT[q][0], 0.0)
+        dom_q = max(queries, key=lambda q: longest[q][1])
+        dom_kernel = longest[dom_q][0]
 
     def step_order(qs):
         if args.launch_order == "given":
@@ -334,9 +346,10 @@ def main(argv=None, hooks=None):
         whose last device call is launched without being waited for: sdqlpy_amd/result.py DeferredResultSet)."""
         return r.wait() if hasattr(r, "wait") else r
 
-    def run_steps(nsteps, only, qs=None, run=None, each_waited_for=False):
+    def run_steps(nsteps, only, qs=None, run=None, each_waited_for=False, keep=None):
         """One step = every query of `qs` LAUNCHED, then every result finished (a step ends with all its results complete on the
-        host).  each_waited_for: every query's result finished before the next query is launched (per-query wall times)."""
+        host).  each_waited_for: every query's result finished before the next query is launched (per-query wall times).
+        keep: a dict that receives {query: finished result} of the last step (not with each_waited_for)."""
         qs = queries if qs is None else qs
         run = run or run_query
         per_q = {q: 0.0 for q in qs}
@@ -364,6 +377,8 @@ def main(argv=None, hooks=None):
                 finish(r)
         barrier()
         took = time.perf_counter() - t_begin
+        if keep is not None and nsteps > 0 and not each_waited_for:
+            keep.update((q, finish(r)) for q, r in zip(order, results))
         # [(kernel, ms, modelled HBM bytes)] of every recorded launch (sdqh_profile_entry_bytes: what the library's own choice of
         # encodings makes that launch stream; 0 where a kernel has no model)
         # (a plan runs on one lane of the engine — a context with a stream of its own: the launches are read per context)
@@ -380,106 +395,116 @@ def main(argv=None, hooks=None):
         runner.reset_collectives()
     # THE TIMED REGION: args.steps steps, nothing evented — settled plans are launched as recorded graphs (one call per query) where the
     # engine records them (single-GPU plans; SDQLPY_AMD_PLAN_GRAPHS=0 switches that off)
-    elapsed, launch_host_ms, _ = run_steps(args.steps, "-")
-    graph_stats = dict(getattr(eng, "graph_stats", {}) or {})
-    # the same steps once more with the dominant kernel's launches evented (HIP events on the stream it runs on): evented launches are
-    # issued call by call — a recorded graph has no place for an event pair — so this region also says what the step costs without graphs
-    elapsed_calls, launch_host_calls_ms, timed_log = run_steps(args.steps, dom_kernel)
-    # the same steps with every query's result finished before the next query starts: per-query wall times, and the step as a caller
-    # who reads each result at once sees it; then evented (in that region a kernel has the chip to itself — in the overlapped steps the
-    # queries' kernels share it, lane by lane, and a kernel's duration there is not a statement about the kernel)
-    run_steps(max(args.warmup, 3), "-", each_waited_for=True)      # (untimed: a query that is waited for alone is launched as a recorded plan — recorded here, not in the timed steps)
-    elapsed_waited, per_query_ms, _ = run_steps(args.steps, "-", each_waited_for=True)
-    _, _, waited_log = run_steps(args.steps, dom_kernel, each_waited_for=True)
-    q1_log = None
-    if "q1" in queries and dom_q != "q1":
-        # Q1's streaming kernel evented in steps of its own (the filter takes one kernel name), outside `value`
-        _, _, q1_log = run_steps(args.steps, longest["q1"][0], ["q1"], each_waited_for=True)
-    timed_collectives = None
-    if runner is not None:
-        timed_collectives = {k: {"calls": v[0], "on_device_tensors": v[1], "bytes": v[2]} for k, v in sorted(runner.collectives.items())}
-        if "q3" in queries:
-            # a "distributed" step that took the single-GPU plan measures nothing (round 2's world-1 profile did)
-            assert runner.last_partitioning == args.partition or (args.partition == "auto" and runner.last_partitioning in ("range", "hash")), \
-                "q3 did not run the partitioned join (partitioning %r)" % (runner.last_partitioning,)
-            assert runner.collectives.get("all_to_all", [0])[0] > 0 or runner.last_partitioning == "range" or (world == 1 and runner.skip_trivial), "no all-to-all ran in the timed step"
-            if args.partition == "hash":
-                assert runner.exchanged_rows.get("probe_sent", 0) > 0, runner.exchanged_rows
+    last_step = {} if args.dump_outputs else None
+    elapsed, launch_host_ms, _ = run_steps(args.steps, "-", keep=last_step)
+    if last_step is not None:
+        # owned copies, and the result objects dropped before anything runs again: a recorded plan is not launched again while views
+        # of its result block are alive
+        outputs = output_arrays(last_step)
+        last_step = None
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+        outputs = None
     nlanes = int(getattr(eng, "nlanes", 1))
-    shared_launches = [ms for q, name, ms, _ in timed_log if q == dom_q and name == dom_kernel]
-    alone_launches = [ms for q, name, ms, _ in waited_log if q == dom_q and name == dom_kernel]
-    # one lane: the queries of a step run one behind the other on one stream, and the first region's launches are as alone as the second's
-    dom_launches = alone_launches if (nlanes > 1 and alone_launches) else shared_launches
-    dom_model = [nb for q, name, _, nb in (waited_log if dom_launches is alone_launches else timed_log) if q == dom_q and name == dom_kernel and nb > 0]
-    # per-kernel table: a separate pass with events around every launch, after the timed region
-    profile_steps = max(1, min(args.steps, 10))
-    _, _, launch_log = run_steps(profile_steps, None, each_waited_for=True)      # (one query at a time: a kernel's duration is its own)
-    exchange = None
-    if use_dist and "q3" in queries:
-        # q3's redistribution step, both ways, outside `value`: what moved and what it cost
-        exchange = {}
-        for label, rn in ((args.partition, runner), ("auto", runner_range)):
-            rn.run("q3", db)
-            took, _, _ = run_steps(max(1, min(args.steps, 10)), "-", ["q3"], lambda q, rn=rn: rn.run(q, db))
-            ms = took / max(1, min(args.steps, 10)) * 1e3
-            if world > 1:
-                t = torch.tensor([ms], dtype=torch.float64, device=coll_device)
-                dist.all_reduce(t, op=dist.ReduceOp.MAX)
-                ms = float(t.item())
-                moved = torch.tensor([rn.exchanged_bytes], dtype=torch.float64, device=coll_device)
-                dist.all_reduce(moved)
-                total_bytes = float(moved.item())
-            else:
-                total_bytes = float(rn.exchanged_bytes)
-            exchange[label if label != "auto" else "auto(" + str(rn.last_partitioning) + ")"] = {
-                "ms_q3": round(ms, 4), "partitioning": rn.last_partitioning, "exchanged_rows_rank0": rn.exchanged_rows,
-                "exchanged_bytes_all_ranks": int(total_bytes),
-                "all_to_all_GBs_all_ranks": round(total_bytes / (ms * 1e-3) / 1e9, 1) if ms > 0 else None}
-    extra_ms, extra_log, extra_steps = {}, [], max(1, min(args.steps, 10))
-    if extra:
-        for q in extra:                                   # upload + warm-up, then the same protocol per query
-            first_run(q)
-            for _ in range(args.warmup):
-                run_query(q)
-        run_steps(3, "-", extra, each_waited_for=True)       # (untimed: plans settle / are recorded here)
-        took_x, extra_ms, _ = run_steps(extra_steps, "-", extra, each_waited_for=True)
-        _, _, extra_log = run_steps(extra_steps, None, extra, each_waited_for=True)
-    # the timed region is args.steps steps (the driver fixes 20: 15 ms); the same step for ~1 s of back-to-back work, outside `value`:
-    # is the figure steady state or a burst out of warm caches?
-    steady = None
-    if world == 1 and args.steady_steps > 0:
-        took_long, _, _ = run_steps(args.steady_steps, "-")
-        steady = {"steps": args.steady_steps, "ms_per_step": round(took_long / args.steady_steps * 1e3, 4), "seconds": round(took_long, 3)}
-    # one finished result per query of the step, kept for the comparison with the CPU implementation's results on the same tables
-    hip_results = {q: finish(run_query(q)) for q in queries} if (world == 1 and not args.no_cpu_baseline) else {}
-    hbm = None
-    try:                                                       # what the process holds of the GPU's HBM behind the timed region: columns at the reference's widths,
-        import torch                                           # their twins and dictionaries, the pools' table memory, recorded plans, the runtime's own
-        free_b, total_b = torch.cuda.mem_get_info(local_rank if use_dist else 0)
-        hbm = {"in_use_GB": round((total_b - free_b) / 1e9, 2), "of_GB": round(total_b / 1e9, 1), "columns_at_reference_width_GB": round(int(eng.resident_bytes) / 1e9, 2)}
-        try:
-            # where it is (sdqh_memory_stats over the engine's lanes): what the pools have handed out — the columns, everything attached to them
-            # (twins, codes, dictionaries, delta twins, run indexes, row packs) and tables still alive —, what they keep cached for the next
-            # run's tables, what recorded plan graphs reserve; the rest is the runtime's (code objects, RCCL / torch, queues)
-            ms = eng.ctx.memory_stats()
-            cols = int(eng.resident_bytes)
-            hbm["pools"] = {"handed_out_GB": round(ms["used"] / 1e9, 2), "of_which_columns_GB": round(cols / 1e9, 2),
-                            "of_which_attached_to_columns_and_live_tables_GB": round(max(0, ms["used"] - cols - ms["graphs"]) / 1e9, 2),
-                            "cached_free_GB": round(ms["cached_free"] / 1e9, 2), "reserved_by_recorded_plans_GB": round(ms["graphs"] / 1e9, 2), "blocks": ms["blocks"]}
-            hbm["outside_the_pools_GB"] = round(((total_b - free_b) - ms["used"] - ms["cached_free"]) / 1e9, 2)
-        except Exception as exc:                               # (reporting only)
-            hbm["pools"] = {"error": str(exc)[:100]}
-    except Exception as exc:                                   # (reporting only)
-        hbm = {"error": str(exc)[:100]}
-    reference_width = None
-    if world == 1 and not use_dist and "engine" not in hooks and not args.no_reference_width:
-        reference_width = reference_width_leg(args, eng, db, rows, queries + extra, run_query, run_steps, finish)
-    scan_form = None
-    if world == 1 and not use_dist and "engine" not in hooks and not args.no_scan_form:
-        scan_form = scan_form_leg(args, eng, queries, queries + extra, run_query, run_steps, finish)
-    hash_path = None
-    if world == 1 and not use_dist and "engine" not in hooks and not args.no_hash_path:
-        hash_path = hash_path_leg(args, eng, db, rows, queries + extra, run_steps, finish)
+    if args.full:
+        graph_stats = dict(getattr(eng, "graph_stats", {}) or {})
+        # the same steps once more with the dominant kernel's launches evented (HIP events on the stream it runs on): evented launches are
+        # issued call by call — a recorded graph has no place for an event pair — so this region also says what the step costs without graphs
+        elapsed_calls, launch_host_calls_ms, timed_log = run_steps(args.steps, dom_kernel)
+        # the same steps with every query's result finished before the next query starts: per-query wall times, and the step as a caller
+        # who reads each result at once sees it; then evented (in that region a kernel has the chip to itself — in the overlapped steps the
+        # queries' kernels share it, lane by lane, and a kernel's duration there is not a statement about the kernel)
+        run_steps(max(args.warmup, 3), "-", each_waited_for=True)      # (untimed: a query that is waited for alone is launched as a recorded plan — recorded here, not in the timed steps)
+        elapsed_waited, per_query_ms, _ = run_steps(args.steps, "-", each_waited_for=True)
+        _, _, waited_log = run_steps(args.steps, dom_kernel, each_waited_for=True)
+        q1_log = None
+        if "q1" in queries and dom_q != "q1":
+            # Q1's streaming kernel evented in steps of its own (the filter takes one kernel name), outside `value`
+            _, _, q1_log = run_steps(args.steps, longest["q1"][0], ["q1"], each_waited_for=True)
+        timed_collectives = None
+        if runner is not None:
+            timed_collectives = {k: {"calls": v[0], "on_device_tensors": v[1], "bytes": v[2]} for k, v in sorted(runner.collectives.items())}
+            if "q3" in queries:
+                # a "distributed" step that took the single-GPU plan measures nothing (round 2's world-1 profile did)
+                assert runner.last_partitioning == args.partition or (args.partition == "auto" and runner.last_partitioning in ("range", "hash")), \
+                    "q3 did not run the partitioned join (partitioning %r)" % (runner.last_partitioning,)
+                assert runner.collectives.get("all_to_all", [0])[0] > 0 or runner.last_partitioning == "range" or (world == 1 and runner.skip_trivial), "no all-to-all ran in the timed step"
+                if args.partition == "hash":
+                    assert runner.exchanged_rows.get("probe_sent", 0) > 0, runner.exchanged_rows
+        shared_launches = [ms for q, name, ms, _ in timed_log if q == dom_q and name == dom_kernel]
+        alone_launches = [ms for q, name, ms, _ in waited_log if q == dom_q and name == dom_kernel]
+        # one lane: the queries of a step run one behind the other on one stream, and the first region's launches are as alone as the second's
+        dom_launches = alone_launches if (nlanes > 1 and alone_launches) else shared_launches
+        dom_model = [nb for q, name, _, nb in (waited_log if dom_launches is alone_launches else timed_log) if q == dom_q and name == dom_kernel and nb > 0]
+        # per-kernel table: a separate pass with events around every launch, after the timed region
+        profile_steps = max(1, min(args.steps, 10))
+        _, _, launch_log = run_steps(profile_steps, None, each_waited_for=True)      # (one query at a time: a kernel's duration is its own)
+        exchange = None
+        if use_dist and "q3" in queries:
+            # q3's redistribution step, both ways, outside `value`: what moved and what it cost
+            exchange = {}
+            for label, rn in ((args.partition, runner), ("auto", runner_range)):
+                rn.run("q3", db)
+                took, _, _ = run_steps(max(1, min(args.steps, 10)), "-", ["q3"], lambda q, rn=rn: rn.run(q, db))
+                ms = took / max(1, min(args.steps, 10)) * 1e3
+                if world > 1:
+                    t = torch.tensor([ms], dtype=torch.float64, device=coll_device)
+                    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+                    ms = float(t.item())
+                    moved = torch.tensor([rn.exchanged_bytes], dtype=torch.float64, device=coll_device)
+                    dist.all_reduce(moved)
+                    total_bytes = float(moved.item())
+                else:
+                    total_bytes = float(rn.exchanged_bytes)
+                exchange[label if label != "auto" else "auto(" + str(rn.last_partitioning) + ")"] = {
+                    "ms_q3": round(ms, 4), "partitioning": rn.last_partitioning, "exchanged_rows_rank0": rn.exchanged_rows,
+                    "exchanged_bytes_all_ranks": int(total_bytes),
+                    "all_to_all_GBs_all_ranks": round(total_bytes / (ms * 1e-3) / 1e9, 1) if ms > 0 else None}
+        extra_ms, extra_log, extra_steps = {}, [], max(1, min(args.steps, 10))
+        if extra:
+            for q in extra:                                   # upload + warm-up, then the same protocol per query
+                first_run(q)
+                for _ in range(args.warmup):
+                    run_query(q)
+            run_steps(3, "-", extra, each_waited_for=True)       # (untimed: plans settle / are recorded here)
+            took_x, extra_ms, _ = run_steps(extra_steps, "-", extra, each_waited_for=True)
+            _, _, extra_log = run_steps(extra_steps, None, extra, each_waited_for=True)
+        # the timed region is args.steps steps (20 by default: ~10 ms); the same step for ~1 s of back-to-back work, outside `value`:
+        # is the figure steady state or a burst out of warm caches?
+        steady = None
+        if world == 1 and args.steady_steps > 0:
+            took_long, _, _ = run_steps(args.steady_steps, "-")
+            steady = {"steps": args.steady_steps, "ms_per_step": round(took_long / args.steady_steps * 1e3, 4), "seconds": round(took_long, 3)}
+        # one finished result per query of the step, kept for the comparison with the CPU implementation's results on the same tables
+        hip_results = {q: finish(run_query(q)) for q in queries} if (world == 1 and not args.no_cpu_baseline) else {}
+        hbm = None
+        try:                                                       # what the process holds of the GPU's HBM behind the timed region: columns at the reference's widths,
+            import torch                                           # their twins and dictionaries, the pools' table memory, recorded plans, the runtime's own
+            free_b, total_b = torch.cuda.mem_get_info(local_rank if use_dist else 0)
+            hbm = {"in_use_GB": round((total_b - free_b) / 1e9, 2), "of_GB": round(total_b / 1e9, 1), "columns_at_reference_width_GB": round(int(eng.resident_bytes) / 1e9, 2)}
+            try:
+                # where it is (sdqh_memory_stats over the engine's lanes): what the pools have handed out — the columns, everything attached to them
+                # (twins, codes, dictionaries, delta twins, run indexes, row packs) and tables still alive —, what they keep cached for the next
+                # run's tables, what recorded plan graphs reserve; the rest is the runtime's (code objects, RCCL / torch, queues)
+                ms = eng.ctx.memory_stats()
+                cols = int(eng.resident_bytes)
+                hbm["pools"] = {"handed_out_GB": round(ms["used"] / 1e9, 2), "of_which_columns_GB": round(cols / 1e9, 2),
+                                "of_which_attached_to_columns_and_live_tables_GB": round(max(0, ms["used"] - cols - ms["graphs"]) / 1e9, 2),
+                                "cached_free_GB": round(ms["cached_free"] / 1e9, 2), "reserved_by_recorded_plans_GB": round(ms["graphs"] / 1e9, 2), "blocks": ms["blocks"]}
+                hbm["outside_the_pools_GB"] = round(((total_b - free_b) - ms["used"] - ms["cached_free"]) / 1e9, 2)
+            except Exception as exc:                               # (reporting only)
+                hbm["pools"] = {"error": str(exc)[:100]}
+        except Exception as exc:                                   # (reporting only)
+            hbm = {"error": str(exc)[:100]}
+        reference_width = None
+        if world == 1 and not use_dist and "engine" not in hooks and not args.no_reference_width:
+            reference_width = reference_width_leg(args, eng, db, rows, queries + extra, run_query, run_steps, finish)
+        scan_form = None
+        if world == 1 and not use_dist and "engine" not in hooks and not args.no_scan_form:
+            scan_form = scan_form_leg(args, eng, queries, queries + extra, run_query, run_steps, finish)
+        hash_path = None
+        if world == 1 and not use_dist and "engine" not in hooks and not args.no_hash_path:
+            hash_path = hash_path_leg(args, eng, db, rows, queries + extra, run_steps, finish)
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -492,102 +517,24 @@ def main(argv=None, hooks=None):
     ms_per_step = elapsed / args.steps * 1e3
     value = total_rows_per_step * args.steps / elapsed
 
-    kstat = {}
-    for q, name, ms, nb in launch_log + extra_log:
-        name = "%s:%s" % (q, name)
-        tot, n, b = kstat.get(name, (0.0, 0, 0))
-        kstat[name] = (tot + ms, n + 1, b + nb)
-    kernels = {name: {"launches_per_step": n / profile_steps, "avg_launch_ms": tot / n, "ms_per_step": tot / profile_steps}
-               for name, (tot, n, _) in kstat.items()}
-    for name, (tot, n, b) in kstat.items():
-        if b:                                            # streamed bytes by the library's own model, and the rate they imply
-            kernels[name]["model_bytes_per_launch"] = b / n
-            kernels[name]["model_GBs"] = b / n / (tot / n * 1e-3) / 1e9 if tot > 0 else None
-    # kernels are attributed to the query that was running when they were launched
-    device_ms = {q: sum(ms for qq, _, ms, _ in launch_log if qq == q) / profile_steps for q in queries}
-    device_ms.update({q: sum(ms for qq, _, ms, _ in extra_log if qq == q) / extra_steps for q in extra})
+    if args.full:
+        kstat = {}
+        for q, name, ms, nb in launch_log + extra_log:
+            name = "%s:%s" % (q, name)
+            tot, n, b = kstat.get(name, (0.0, 0, 0))
+            kstat[name] = (tot + ms, n + 1, b + nb)
+        kernels = {name: {"launches_per_step": n / profile_steps, "avg_launch_ms": tot / n, "ms_per_step": tot / profile_steps}
+                   for name, (tot, n, _) in kstat.items()}
+        for name, (tot, n, b) in kstat.items():
+            if b:                                            # streamed bytes by the library's own model, and the rate they imply
+                kernels[name]["model_bytes_per_launch"] = b / n
+                kernels[name]["model_GBs"] = b / n / (tot / n * 1e-3) / 1e9 if tot > 0 else None
+        # kernels are attributed to the query that was running when they were launched
+        device_ms = {q: sum(ms for qq, _, ms, _ in launch_log if qq == q) / profile_steps for q in queries}
+        device_ms.update({q: sum(ms for qq, _, ms, _ in extra_log if qq == q) / extra_steps for q in extra})
 
     out = None
     if rank == 0:
-        dom_name = dom_q + ":" + dom_kernel
-        roofline = None
-        def price(q, kernel, launches_ms, model):
-            """One kernel against the HBM roofline.  `frac` is the PHYSICAL fraction: HBM bytes the kernel really moves / its average
-            launch time (HIP events on the stream it runs on, inside the timed steps) / peak; the bytes are the committed PMC figure
-            (`traffic`) when its row counts and kernel names match this run, else the library's own model of THIS run
-            (`traffic_model`, sdqh_profile_entry_bytes: rows x the bytes per row of the encodings the engine chose + what the launch
-            stores by construction), so the fraction can be recomputed from the line alone.  SURVEY.md 8(d)'s algorithmic figure (the
-            reference's 8-byte / UCS-4 widths) is carried beside it as `frac_algorithmic`: the kernels read exact narrow encodings, so
-            that one can exceed 1 and is no roofline fraction; `reference_width` times the same queries on the 8-byte columns."""
-            ms = sum(launches_ms) / len(launches_ms)
-            per_launch_bytes = DOMINANT[q][1](rows)
-            achieved = per_launch_bytes / (ms * 1e-3) / 1e9
-            traffic, traffic_source = pmc_traffic(q, kernel, rows)
-            traffic_model = int(sum(model) / len(model)) if model else None
-            bytes_used, frac_source = (traffic, "pmc") if traffic else (traffic_model, "model")
-            phys_gbs = bytes_used / (ms * 1e-3) / 1e9 if bytes_used else None
-            return {"bound": "hbm", "kernel": q + ":" + kernel, "achieved": round(phys_gbs, 1) if phys_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(phys_gbs / HBM_PEAK_GBS, 4) if phys_gbs else None, "frac_source": frac_source,
-                    "traffic": traffic, "traffic_source": traffic_source, "traffic_stale": ("STALE" in traffic_source) if traffic_source else None,
-                    "traffic_model": traffic_model, "traffic_model_over_pmc": round(traffic_model / traffic, 4) if traffic and traffic_model else None,
-                    "frac_model": round(traffic_model / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic_model else None,
-                    "achieved_algorithmic": round(achieved, 1), "frac_algorithmic": round(achieved / HBM_PEAK_GBS, 4),
-                    "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_ms": round(ms, 4),
-                    "launches_timed": len(launches_ms)}
-        if dom_launches:
-            roofline = price(dom_q, dom_kernel, dom_launches, dom_model)
-            roofline["dominant"] = "the longest single launch over all queries of the step (one evented run of each query before the timed region): " + \
-                                   ", ".join("%s %s %.4f ms" % (q, longest[q][0], longest[q][1]) for q in queries)
-            roofline["achievable_peak_note"] = "MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 TB/s measured for a float4 copy"
-            if q1_log is not None:
-                k1 = longest["q1"][0]
-                ms1 = [ms for q, name, ms, _ in q1_log if q == "q1" and name == k1]
-                if ms1:
-                    roofline["q1"] = price("q1", k1, ms1, [nb for q, name, _, nb in q1_log if q == "q1" and name == k1 and nb > 0])
-                    roofline["q1"]["measured_in"] = "steps of q1 alone, waited for, after the timed region"
-            if dom_launches is alone_launches:
-                # which of the two timed regions the launches above are from, and the same kernel's launches in the other
-                shared_ms = sum(shared_launches) / len(shared_launches) if shared_launches else None
-                roofline["measured_in"] = ("%d steps whose queries are waited for one by one, every launch of this kernel between a pair of HIP events on the stream it "
-                                           "runs on (calls issued one by one: a recorded plan has no place for events) — there the kernel has the chip to itself; in the "
-                                           "overlapped steps the engine's %d lanes run the queries' kernels side by side" % (args.steps, nlanes))
-                roofline["in_overlapped_steps"] = {"avg_launch_ms": round(shared_ms, 4) if shared_ms else None, "launches_timed": len(shared_launches),
-                                                   "note": "the same kernel sharing the chip with the other lanes' kernels: the step, not the kernel, is the unit there (roofline.step)"}
-            # the step as a whole against the same roofline: HBM bytes of its queries (PMC, per query) / the step's wall time
-            step_bytes = [pmc_traffic(q, None, rows)[0] for q in queries]
-            if all(step_bytes):
-                roofline["step"] = {"physical_bytes": int(sum(step_bytes)), "ms_per_step": round(ms_per_step, 4),
-                                    "frac": round(sum(step_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "frac_each_query_waited_for": round(sum(step_bytes) / (elapsed_waited / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
-                                    "traffic_source": "per-query PMC bytes (profiles/), wall time of this run"}
-            if reference_width and dom_q in reference_width.get("queries", {}):
-                rw = reference_width["queries"][dom_q]
-                roofline["reference_width"] = {"kernel": rw["dominant_kernel"], "avg_launch_ms": rw["dominant_avg_launch_ms"], "achieved": rw["achieved"], "frac": rw["frac"]}
-            if reference_width and "q1" in roofline and "q1" in reference_width.get("queries", {}):
-                rw = reference_width["queries"]["q1"]
-                roofline["q1"]["reference_width"] = {"kernel": rw["dominant_kernel"], "avg_launch_ms": rw["dominant_avg_launch_ms"], "achieved": rw["achieved"], "frac": rw["frac"]}
-        per_query = {}
-        for q in queries + extra:
-            ab = algorithmic_bytes(q, rows)
-            wall = (per_query_ms[q] / args.steps) if q in per_query_ms else (extra_ms[q] / extra_steps)
-            phys, phys_source = pmc_traffic(q, None, rows, ran={name.split(":", 1)[1] for name in kernels if name.startswith(q + ":")})
-            per_query[q] = {"ms_wall": round(wall, 4), "ms_kernels": round(device_ms[q], 4),
-                            "in_timed_step": q in queries,
-                            "rows_per_s_wall": round(scanned_rows(q, rows) / (wall * 1e-3), 1),
-                            "algorithmic_bytes": ab,
-                            "algorithmic_GBs_wall": round(ab / (wall * 1e-3) / 1e9, 1),
-                            "algorithmic_GBs_kernels": round(ab / (device_ms[q] * 1e-3) / 1e9, 1) if device_ms[q] else None,
-                            "algorithmic_frac_kernels": round(ab / (device_ms[q] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if device_ms[q] else None,
-                            "physical_frac_kernels": round(phys / (device_ms[q] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if phys and device_ms[q] else None,
-                            "first_run_ms": first_run_ms.get(q),
-                            "built_once": built_once(q, first_run_detail.get(q), {name.split(":", 1)[1]: v["ms_per_step"] for name, v in kernels.items() if name.startswith(q + ":")},
-                                                     device_ms[q], scan_form),
-                            # SURVEY.md §8(d): physical bytes moved beside the algorithmic figure
-                            "physical_bytes": phys,
-                            "physical_GBs_kernels": round(phys / (device_ms[q] * 1e-3) / 1e9, 1) if phys and device_ms[q] else None,
-                            "traffic_source": phys_source,
-                            # streamed bytes of the query's kernels by the library's model of this run (lower bound: no gathers, no survivor-dependent stores)
-                            "model_streamed_bytes": int(sum(v.get("model_bytes_per_launch", 0) * v["launches_per_step"] for k, v in kernels.items() if k.startswith(q + ":"))) or None}
         out = {
             "metric": "tpch_" + "_".join(queries) + "_sf%g_rows_per_sec" % sf_per_gpu, "value": round(value, 1), "unit": "rows/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -596,61 +543,143 @@ def main(argv=None, hooks=None):
                        "sf_per_gpu": sf_per_gpu, "sf_global": sf_global, "rows_per_gpu": rows,
                        "partitioning": "none" if not use_dist else "q1 row-sharded; q5 small builds replicated, orders-lineitem join co-partitioned; q3 partitioned on o_orderkey (%s), RCCL all-to-all; exchanged rows %s"
                                        % (runner.last_partitioning, runner.exchanged_rows)},
-            # what a step is: its queries launched one after the other, then their results finished — a plan's last device call is
-            # queued without being waited for (Engine.deferred_results) and every result is complete on the host before the step ends.
-            # Beside it, the same step with every query's result finished before the next query is launched.
-            # the same two figures under explicit names: `value` is the overlapped one
             "lanes": nlanes,
-            "value_overlapped": round(value, 1), "value_sequential": round(total_rows_per_step * args.steps / elapsed_waited, 1),
-            "step": {"launch_then_finish": True, "launch_order": step_order(queries), "deferred_results": bool(getattr(eng, "deferred_results", False)),
-                     # host time to LAUNCH each query of an overlapped step (plan closures, ctypes calls, kernel launches; nothing waited for)
-                     "host_launch_ms": {q: round(launch_host_ms[q] / args.steps, 4) for q in queries},
-                     # ... and with the calls issued one by one (the evented repeat of the timed steps: no graphs there)
-                     "host_launch_ms_calls_issued": {q: round(launch_host_calls_ms[q] / args.steps, 4) for q in queries},
-                     "ms_per_step_calls_issued": round(elapsed_calls / args.steps * 1e3, 4),
-                     "plan_graphs": graph_stats or None,
-                     "ms_per_step_each_query_waited_for": round(elapsed_waited / args.steps * 1e3, 4),
-                     "value_each_query_waited_for": round(total_rows_per_step * args.steps / elapsed_waited, 1)},
-            "ms_per_query": per_query,
-            "kernels_pass": "separate pass of %d steps after the timed region, every query waited for before the next starts, HIP events around every launch" % profile_steps,
-            "kernels": {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in sorted(kernels.items())},
-            "roofline": roofline,
-            "first_pass_with_upload_s": round(first_pass_s, 3), "generate_s": round(gen_s, 2),
-            # the boundary hands over host buffers: the PCIe-inclusive first pass (never the reported value)
-            "first_pass_upload": {"bytes": uploaded_bytes, "GBs_including_plan_lowering": round(uploaded_bytes / first_pass_s / 1e9, 2) if first_pass_s > 0 else None},
         }
-        out["engine_stats"] = eng.stats() if hasattr(eng, "stats") else None      # loops that ran on the host (none in the configured queries), plan graphs, resident bytes
-        out["hbm"] = hbm
-        if steady is not None:
-            out["steady_state"] = steady
-        if reference_width is not None:
-            out["reference_width"] = reference_width
-        if scan_form is not None:
-            out["scan_form"] = scan_form
-        if hash_path is not None:
-            out["hash_path"] = hash_path
-        try:
-            c, d = eng.ctx.jit_stats()
-            out["specialised_kernels"] = {"compiled_by_hiprtc_in_this_process": int(c), "loaded_from_jit_cache": int(d)}
-        except Exception:
-            pass
         if args.share_gpu:
             out["share_gpu"] = "the %d ranks of this run SHARED one GPU (gloo between the processes, pinned host buffers): every plan and kernel of the N > 1 path, none of its transport; not a scaling figure" % world
         if world > 1 or use_dist:
             out["n_gpus_note"] = "ranks in this run: %d%s" % (world, "" if world > 1 else " (the distributed plan on a group of one; N > 1 was not run here)")
-        if exchange is not None:
-            out["q3_exchange"] = exchange
-        if timed_collectives is not None:
-            out["collectives_in_timed_region_rank0"] = timed_collectives
-            out["distributed_plan"] = {"device_sized_join_runs": runner.fast_runs, "repeated_with_exact_sizes": runner.fast_retries,
-                                       "collectives_over_a_group_of_one": "skipped" if (world == 1 and runner.skip_trivial) else "issued"}
-        if hip_results:
-            ref = reference_at_bench_size(hip_results, sf_per_gpu, rows)
-            if ref is not None:
-                out["reference_at_bench_size"] = ref
-        if not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only
-            out["cpu_baseline"] = cpu_baseline(args, queries, db, rows, hip_results)
-            out["cpu_baseline"]["configs0_q6_sf1"] = q6_sf1_leg(eng)
+        if args.full:
+            dom_name = dom_q + ":" + dom_kernel
+            roofline = None
+            def price(q, kernel, launches_ms, model):
+                """One kernel against the HBM roofline.  `frac` is the PHYSICAL fraction: HBM bytes the kernel really moves / its average
+                launch time (HIP events on the stream it runs on, inside the timed steps) / peak; the bytes are the committed PMC figure
+                (`traffic`) when its row counts and kernel names match this run, else the library's own model of THIS run
+                (`traffic_model`, sdqh_profile_entry_bytes: rows x the bytes per row of the encodings the engine chose + what the launch
+                stores by construction), so the fraction can be recomputed from the line alone.  SURVEY.md 8(d)'s algorithmic figure (the
+                reference's 8-byte / UCS-4 widths) is carried beside it as `frac_algorithmic`: the kernels read exact narrow encodings, so
+                that one can exceed 1 and is no roofline fraction; `reference_width` times the same queries on the 8-byte columns."""
+                ms = sum(launches_ms) / len(launches_ms)
+                per_launch_bytes = DOMINANT[q][1](rows)
+                achieved = per_launch_bytes / (ms * 1e-3) / 1e9
+                traffic, traffic_source = pmc_traffic(q, kernel, rows)
+                traffic_model = int(sum(model) / len(model)) if model else None
+                bytes_used, frac_source = (traffic, "pmc") if traffic else (traffic_model, "model")
+                phys_gbs = bytes_used / (ms * 1e-3) / 1e9 if bytes_used else None
+                return {"bound": "hbm", "kernel": q + ":" + kernel, "achieved": round(phys_gbs, 1) if phys_gbs else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(phys_gbs / HBM_PEAK_GBS, 4) if phys_gbs else None, "frac_source": frac_source,
+                        "traffic": traffic, "traffic_source": traffic_source, "traffic_stale": ("STALE" in traffic_source) if traffic_source else None,
+                        "traffic_model": traffic_model, "traffic_model_over_pmc": round(traffic_model / traffic, 4) if traffic and traffic_model else None,
+                        "frac_model": round(traffic_model / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic_model else None,
+                        "achieved_algorithmic": round(achieved, 1), "frac_algorithmic": round(achieved / HBM_PEAK_GBS, 4),
+                        "algorithmic_bytes_per_launch": per_launch_bytes, "avg_launch_ms": round(ms, 4),
+                        "launches_timed": len(launches_ms)}
+            if dom_launches:
+                roofline = price(dom_q, dom_kernel, dom_launches, dom_model)
+                roofline["dominant"] = "the longest single launch over all queries of the step (one evented run of each query before the timed region): " + \
+                                       ", ".join("%s %s %.4f ms" % (q, longest[q][0], longest[q][1]) for q in queries)
+                roofline["achievable_peak_note"] = "MI355X HBM3E: 8.0 TB/s spec, 6.29 TB/s measured for a float4 copy"
+                if q1_log is not None:
+                    k1 = longest["q1"][0]
+                    ms1 = [ms for q, name, ms, _ in q1_log if q == "q1" and name == k1]
+                    if ms1:
+                        roofline["q1"] = price("q1", k1, ms1, [nb for q, name, _, nb in q1_log if q == "q1" and name == k1 and nb > 0])
+                        roofline["q1"]["measured_in"] = "steps of q1 alone, waited for, after the timed region"
+                if dom_launches is alone_launches:
+                    # which of the two timed regions the launches above are from, and the same kernel's launches in the other
+                    shared_ms = sum(shared_launches) / len(shared_launches) if shared_launches else None
+                    roofline["measured_in"] = ("%d steps whose queries are waited for one by one, every launch of this kernel between a pair of HIP events on the stream it "
+                                               "runs on (calls issued one by one: a recorded plan has no place for events) — there the kernel has the chip to itself; in the "
+                                               "overlapped steps the engine's %d lanes run the queries' kernels side by side" % (args.steps, nlanes))
+                    roofline["in_overlapped_steps"] = {"avg_launch_ms": round(shared_ms, 4) if shared_ms else None, "launches_timed": len(shared_launches),
+                                                       "note": "the same kernel sharing the chip with the other lanes' kernels: the step, not the kernel, is the unit there (roofline.step)"}
+                # the step as a whole against the same roofline: HBM bytes of its queries (PMC, per query) / the step's wall time
+                step_bytes = [pmc_traffic(q, None, rows)[0] for q in queries]
+                if all(step_bytes):
+                    roofline["step"] = {"physical_bytes": int(sum(step_bytes)), "ms_per_step": round(ms_per_step, 4),
+                                        "frac": round(sum(step_bytes) / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                        "frac_each_query_waited_for": round(sum(step_bytes) / (elapsed_waited / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
+                                        "traffic_source": "per-query PMC bytes (profiles/), wall time of this run"}
+                if reference_width and dom_q in reference_width.get("queries", {}):
+                    rw = reference_width["queries"][dom_q]
+                    roofline["reference_width"] = {"kernel": rw["dominant_kernel"], "avg_launch_ms": rw["dominant_avg_launch_ms"], "achieved": rw["achieved"], "frac": rw["frac"]}
+                if reference_width and "q1" in roofline and "q1" in reference_width.get("queries", {}):
+                    rw = reference_width["queries"]["q1"]
+                    roofline["q1"]["reference_width"] = {"kernel": rw["dominant_kernel"], "avg_launch_ms": rw["dominant_avg_launch_ms"], "achieved": rw["achieved"], "frac": rw["frac"]}
+            per_query = {}
+            for q in queries + extra:
+                ab = algorithmic_bytes(q, rows)
+                wall = (per_query_ms[q] / args.steps) if q in per_query_ms else (extra_ms[q] / extra_steps)
+                phys, phys_source = pmc_traffic(q, None, rows, ran={name.split(":", 1)[1] for name in kernels if name.startswith(q + ":")})
+                per_query[q] = {"ms_wall": round(wall, 4), "ms_kernels": round(device_ms[q], 4),
+                                "in_timed_step": q in queries,
+                                "rows_per_s_wall": round(scanned_rows(q, rows) / (wall * 1e-3), 1),
+                                "algorithmic_bytes": ab,
+                                "algorithmic_GBs_wall": round(ab / (wall * 1e-3) / 1e9, 1),
+                                "algorithmic_GBs_kernels": round(ab / (device_ms[q] * 1e-3) / 1e9, 1) if device_ms[q] else None,
+                                "algorithmic_frac_kernels": round(ab / (device_ms[q] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if device_ms[q] else None,
+                                "physical_frac_kernels": round(phys / (device_ms[q] * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if phys and device_ms[q] else None,
+                                "first_run_ms": first_run_ms.get(q),
+                                "built_once": built_once(q, first_run_detail.get(q), {name.split(":", 1)[1]: v["ms_per_step"] for name, v in kernels.items() if name.startswith(q + ":")},
+                                                         device_ms[q], scan_form),
+                                # SURVEY.md §8(d): physical bytes moved beside the algorithmic figure
+                                "physical_bytes": phys,
+                                "physical_GBs_kernels": round(phys / (device_ms[q] * 1e-3) / 1e9, 1) if phys and device_ms[q] else None,
+                                "traffic_source": phys_source,
+                                # streamed bytes of the query's kernels by the library's model of this run (lower bound: no gathers, no survivor-dependent stores)
+                                "model_streamed_bytes": int(sum(v.get("model_bytes_per_launch", 0) * v["launches_per_step"] for k, v in kernels.items() if k.startswith(q + ":"))) or None}
+            out.update({
+                # what a step is: its queries launched one after the other, then their results finished — a plan's last device call is
+                # queued without being waited for (Engine.deferred_results) and every result is complete on the host before the step ends.
+                # Beside it, the same step with every query's result finished before the next query is launched.
+                # the same two figures under explicit names: `value` is the overlapped one
+                "value_overlapped": round(value, 1), "value_sequential": round(total_rows_per_step * args.steps / elapsed_waited, 1),
+                "step": {"launch_then_finish": True, "launch_order": step_order(queries), "deferred_results": bool(getattr(eng, "deferred_results", False)),
+                         # host time to LAUNCH each query of an overlapped step (plan closures, ctypes calls, kernel launches; nothing waited for)
+                         "host_launch_ms": {q: round(launch_host_ms[q] / args.steps, 4) for q in queries},
+                         # ... and with the calls issued one by one (the evented repeat of the timed steps: no graphs there)
+                         "host_launch_ms_calls_issued": {q: round(launch_host_calls_ms[q] / args.steps, 4) for q in queries},
+                         "ms_per_step_calls_issued": round(elapsed_calls / args.steps * 1e3, 4),
+                         "plan_graphs": graph_stats or None,
+                         "ms_per_step_each_query_waited_for": round(elapsed_waited / args.steps * 1e3, 4),
+                         "value_each_query_waited_for": round(total_rows_per_step * args.steps / elapsed_waited, 1)},
+                "ms_per_query": per_query,
+                "kernels_pass": "separate pass of %d steps after the timed region, every query waited for before the next starts, HIP events around every launch" % profile_steps,
+                "kernels": {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in sorted(kernels.items())},
+                "roofline": roofline,
+                "first_pass_with_upload_s": round(first_pass_s, 3), "generate_s": round(gen_s, 2),
+                # the boundary hands over host buffers: the PCIe-inclusive first pass (never the reported value)
+                "first_pass_upload": {"bytes": uploaded_bytes, "GBs_including_plan_lowering": round(uploaded_bytes / first_pass_s / 1e9, 2) if first_pass_s > 0 else None},
+            })
+            out["engine_stats"] = eng.stats() if hasattr(eng, "stats") else None      # loops that ran on the host (none in the configured queries), plan graphs, resident bytes
+            out["hbm"] = hbm
+            if steady is not None:
+                out["steady_state"] = steady
+            if reference_width is not None:
+                out["reference_width"] = reference_width
+            if scan_form is not None:
+                out["scan_form"] = scan_form
+            if hash_path is not None:
+                out["hash_path"] = hash_path
+            try:
+                c, d = eng.ctx.jit_stats()
+                out["specialised_kernels"] = {"compiled_by_hiprtc_in_this_process": int(c), "loaded_from_jit_cache": int(d)}
+            except Exception:
+                pass
+            if exchange is not None:
+                out["q3_exchange"] = exchange
+            if timed_collectives is not None:
+                out["collectives_in_timed_region_rank0"] = timed_collectives
+                out["distributed_plan"] = {"device_sized_join_runs": runner.fast_runs, "repeated_with_exact_sizes": runner.fast_retries,
+                                           "collectives_over_a_group_of_one": "skipped" if (world == 1 and runner.skip_trivial) else "issued"}
+            if hip_results:
+                ref = reference_at_bench_size(hip_results, sf_per_gpu, rows)
+                if ref is not None:
+                    out["reference_at_bench_size"] = ref
+            if not args.no_cpu_baseline and world == 1:      # the CPU leg is reported at N=1 only
+                out["cpu_baseline"] = cpu_baseline(args, queries, db, rows, hip_results)
+                out["cpu_baseline"]["configs0_q6_sf1"] = q6_sf1_leg(eng)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if use_dist:
         dist.barrier()
@@ -1021,6 +1050,50 @@ def physical_cores():
     except OSError:
         pass
     return logical, logical
+
+
+DUMP_LIMIT_BYTES = 64 << 20          # --dump-outputs writes at most this much in all
+
+
+def output_arrays(results):
+    """[(query, column, float64 array)] of finished results, laid out so that two builds can be compared file by file: a scalar result
+    as one value; a result set column by column, its rows (unordered in the result) sorted by every exact column — integers, text —
+    then by the floats; a text column as one value per code point, zero-padded to the column's width (rows x width)."""
+    import numpy as np
+    out = []
+    for q, res in sorted(results.items()):
+        if not hasattr(res, "arrays"):
+            out.append((q, "value", np.array([float(res)], dtype=np.float64)))
+            continue
+        cols = [np.asarray(a) for a in res.arrays]
+        cols = [a.astype(str) if a.dtype.kind == "O" else a for a in cols]
+        keys = [a for a in cols if a.dtype.kind != "f"] + [a for a in cols if a.dtype.kind == "f"]
+        order = np.lexsort(keys[::-1]) if keys else np.arange(0)
+        for name, a in zip(res.columns, cols):
+            a = a[order]
+            if a.dtype.kind in "US":
+                unit = np.uint32 if a.dtype.kind == "U" else np.uint8
+                width = a.dtype.itemsize // np.dtype(unit).itemsize
+                a = np.ascontiguousarray(a).view(unit).reshape(len(a), width) if width else np.zeros((len(a), 1), unit)
+            out.append((q, name, np.array(a, dtype=np.float64)))
+    return out
+
+
+def dump_outputs(path, items, limit=DUMP_LIMIT_BYTES):
+    """Write output_arrays' items as path/<query>_<column>.npy.  Beyond `limit` bytes in all, every query keeps the same fixed, seeded
+    sample of its rows in each of its columns (its share of the limit), rows in their sorted order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for _, _, a in items)
+    rows = {}
+    if total > limit:
+        for q, _, a in items:
+            if q not in rows:
+                n = len(a)
+                k = min(n, max(1, n * limit // total))
+                rows[q] = np.sort(np.random.default_rng(12345).choice(n, size=k, replace=False))
+    for q, name, a in items:
+        np.save(os.path.join(path, "%s_%s.npy" % (q, name)), a[rows[q]] if q in rows else a)
 
 
 def compare_results(got, want):

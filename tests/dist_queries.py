@@ -5,3 +5,9 @@ from sdqlpy_amd import tpch_queries as Q
 
 def register():
     Q.register("q18_low", Q.large_orders(230), Q.TPCH_ORDER["q18"])
+
+
+def unregister():
+    """Leave the registry as it was: tests in the same process iterate over every registered query (test_hip_parity's sweep)."""
+    for table in (Q.QUERIES, Q.QUERY_TABLES, Q.TPCH_ORDER):
+        table.pop("q18_low", None)

@@ -42,7 +42,10 @@ def single(oracle_lib):
     res = {q: helpers.run_query(eng, q, db) for q in qs}
     import dist_queries
     dist_queries.register()
-    res["q18"] = helpers.run_query(eng, "q18_low", db)          # q18 with a threshold that leaves rows at this scale
+    try:
+        res["q18"] = helpers.run_query(eng, "q18_low", db)      # q18 with a threshold that leaves rows at this scale
+    finally:
+        dist_queries.unregister()
     assert res["q18"].size() > 3
     eng.close()
     return res
@@ -177,7 +180,7 @@ def test_bench_contract_under_a_two_rank_launch(tmp_path):
     environment), on CPU: gloo + the CPU implementation of the ABI injected through bench.main's
     hooks.  Rank 0 prints exactly one JSON line with the contract's fields; the other rank prints none."""
     port = free_port()
-    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_gloo_worker.py"), str(r), "2", str(port), "0.01"],
+    procs = [subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "bench_gloo_worker.py"), str(r), "2", str(port), "0.01", "--full"],
                               stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(2)]
     outs = [p.communicate(timeout=600) for p in procs]
     for p, (o, e) in zip(procs, outs):
@@ -201,6 +204,37 @@ def test_bench_contract_under_a_two_rank_launch(tmp_path):
     assert rec["value"] * rec["ms_per_step"] * 1e-3 > 1.5 * per_rank
 
 
+def test_plain_bench_line_and_its_outputs(tmp_path, oracle_lib):
+    """A plain run (no --full) prints the headline only, and --dump-outputs writes what the last timed step returned: the same
+    arrays, bit for bit, as the same queries on the same generated tables outside the benchmark, laid out by bench.output_arrays."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    dump = tmp_path / "outputs"
+    done = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_gloo_worker.py"), "0", "1", str(free_port()), "0.05",
+                           "--dump-outputs", str(dump)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert done.returncode == 0, done.stderr[-3000:]
+    lines = [ln for ln in done.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, done.stdout[-500:]
+    rec = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in rec, key
+    assert rec["steps"] == 2 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "rows/s" and rec["dtype"] == "f64"
+    assert not {"kernels", "ms_per_query", "roofline", "cpu_baseline", "steady_state", "q3_exchange"} & set(rec), sorted(rec)
+    eng = engine.Engine(oracle_lib.context(threads=2))
+    try:
+        qs = ["q1", "q3", "q5"]
+        db = tpch.generate(0.05, tables=sorted(tpch.columns_for(qs)), columns=tpch.columns_for(qs), threads=2)
+        want = bench.output_arrays({q: helpers.run_query(eng, q, db) for q in qs})
+    finally:
+        eng.close()
+    assert sorted(p.name for p in dump.iterdir()) == sorted("%s_%s.npy" % (q, c) for q, c, _ in want)
+    for q, c, a in want:
+        got = np.load(dump / ("%s_%s.npy" % (q, c)))
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a), (q, c)
+    assert len(np.load(dump / "q3_l_orderkey.npy")) > 100
+
+
 def test_bench_starts_its_own_ranks():
     """Plain `python bench.py --gpus 2` — no torchrun, no WORLD_SIZE: bench.py is its own launcher (spawn_ranks: child processes with
     the rendezvous environment, started before the parent touches a GPU), relays rank 0's single JSON line and exits 0; a rank that
@@ -208,7 +242,7 @@ def test_bench_starts_its_own_ranks():
     env = dict(os.environ, SDQLPY_AMD_BENCH_CHILD=os.path.join(ROOT, "tests", "bench_spawn_worker.py"))
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--sf", "0.01", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--sf", "0.01", "--no-cpu-baseline", "--full"]
     done = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert done.returncode == 0, done.stderr[-3000:]
     lines = [ln for ln in done.stdout.splitlines() if ln.strip()]

@@ -2,7 +2,6 @@
 own TPCH text fares (tests/golden/reference_lowering.json, made by make_lowering_fixture.py)."""
 import json
 import os
-import sys
 
 import pytest
 
@@ -183,45 +182,6 @@ def test_merging_equal_keys_of_large_results_on_codes_and_buckets():
         assert len(got) == d.size() == len(want)
         assert got == {k: (v[0], v[1]) for k, v in want.items()}
         assert d.val_fields[0][1].dtype == np.int64
-
-
-def test_reference_text_runs_against_goldens_when_the_reference_is_here():
-    """Live form of the fixture's `matches_reference_results` (the build container only: /root/reference does not travel): the
-    reference's own q2 / q11 / q12 / q16 text -> desugared (frontend._desugar) -> lowered -> CPU implementation -> golden results."""
-    ref = "/root/reference/test/test_all.py"
-    if not os.path.exists(ref):
-        pytest.skip("the reference is not mounted here")
-    import ast
-    import subprocess
-    import helpers
-    from sdqlpy_amd import abi, engine
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    import make_lowering_fixture as mk
-    src = open(ref).read()
-    tree, lines = ast.parse(src), src.splitlines()
-    plans = {}
-    for node in tree.body:
-        if isinstance(node, ast.FunctionDef) and node.name in ("q2", "q11", "q12", "q16"):
-            first = min([d.lineno for d in node.decorator_list] + [node.lineno])
-            plans[node.name] = (frontend.lower_source("\n".join(lines[first - 1:node.end_lineno]), node.name, first),
-                                [mk.TABLE_OF_TYPE[v.id] for v in node.decorator_list[0].args[0].values])
-    assert len(plans) == 4
-    subprocess.run(["make", "-s", "-C", os.path.join(os.path.dirname(HERE), "oracle")], check=True)
-    eng = engine.Engine(abi.Library(os.path.join(os.path.dirname(HERE), "oracle", "libsdqloracle.so")).context(threads=2))
-    try:
-        with open(os.path.join(HERE, "golden", "tpch_golden_wide.json")) as fh:
-            gold = json.load(fh)
-        n = 0
-        for case in gold["cases"]:
-            db = helpers.case_db(case)
-            for q, (plan, tabs) in plans.items():
-                res = engine.execute_plan(eng, plan, [db[t] for t in tabs])
-                helpers.check_against_golden(res, case["results"][q], 1e-12, "reference text/%s/%s" % (case["name"], q))
-                n += 1
-            eng.clear()
-        assert n == 12
-    finally:
-        eng.close()
 
 
 def test_dictionary_passes_started_when_a_plan_is_bound_change_no_row(oracle_lib):

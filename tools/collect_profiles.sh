@@ -8,13 +8,13 @@ R=${1:-r03}
 OUT=gpurun_out/$R
 mkdir -p $OUT
 export TMPDIR=/tmp
-python3 bench.py --no-cpu-baseline > $OUT/bench_for_rows.json 2> $OUT/bench_for_rows.err
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --no-cpu-baseline --extra-queries "" --no-scan-form --no-hash-path > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
+python3 bench.py --full --no-cpu-baseline > $OUT/bench_for_rows.json 2> $OUT/bench_for_rows.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --no-cpu-baseline --extra-queries "" --no-scan-form --no-hash-path > $OUT/bench_under_rocprof.json 2> $OUT/trace.log
 python3 tools/pmc_summary.py $OUT/trace > $OUT/kernel_trace_summary.txt 2>&1
 find $OUT/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats.csv
 # the same with ONE lane (queries of a step one behind the other on one stream): there every launch of a kernel has the chip to itself,
 # and the average duration in the stats is the kernel's own (under the default the overlapped steps' launches share the chip)
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_lanes1 -- python3 bench.py --no-cpu-baseline --extra-queries "" --no-scan-form --no-hash-path --lanes 1 > $OUT/bench_under_rocprof_lanes1.json 2> $OUT/trace_lanes1.log
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_lanes1 -- python3 bench.py --full --no-cpu-baseline --extra-queries "" --no-scan-form --no-hash-path --lanes 1 > $OUT/bench_under_rocprof_lanes1.json 2> $OUT/trace_lanes1.log
 python3 tools/pmc_summary.py $OUT/trace_lanes1 > $OUT/kernel_trace_summary_lanes1.txt 2>&1
 find $OUT/trace_lanes1 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats_lanes1.csv
 ITERS=5
