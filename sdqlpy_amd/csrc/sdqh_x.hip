@@ -251,8 +251,12 @@ int analyse(sdqh_ctx* ctx, int64_t nrows, const sdqh_program* p, int max_vals, b
 bool is_cmp(int code) { return code >= SDQH_X_LT && code <= SDQH_X_NE; }
 
 // [lo, hi] of an i64 operation over the columns' actual value ranges (min / max are cached per column; a coded column's
-// range is its dictionary's ends).  false: unknown (a product that leaves 62 bits, an operation without a range).
+// range is its dictionary's ends).  false: unknown (a result that leaves 62 bits, an operation without a range, an empty one).
+bool op_interval_of(sdqh_ctx* ctx, const XInfo& x, int k, int64_t* lo, int64_t* hi);
 bool op_interval(sdqh_ctx* ctx, const XInfo& x, int k, int64_t* lo, int64_t* hi) {
+    return op_interval_of(ctx, x, k, lo, hi) && *lo <= *hi;
+}
+bool op_interval_of(sdqh_ctx* ctx, const XInfo& x, int k, int64_t* lo, int64_t* hi) {
     const sdqh_xop& o = x.p->ops[k];
     if (o.type != SDQH_T_I64) return false;
     const __int128 LIM = (__int128)1 << 62;
@@ -282,7 +286,12 @@ bool op_interval(sdqh_ctx* ctx, const XInfo& x, int k, int64_t* lo, int64_t* hi)
             if (!fits(l, h)) return false;
             *lo = (int64_t)l; *hi = (int64_t)h; return true;
         }
-        case SDQH_X_NEG: if (!op_interval(ctx, x, o.a, &al, &ah)) return false; *lo = -ah; *hi = -al; return true;
+        case SDQH_X_NEG: {                                              // (-INT64_MIN is not an int64: a column holding it has no range here)
+            if (!op_interval(ctx, x, o.a, &al, &ah)) return false;
+            const __int128 l = -(__int128)ah, h = -(__int128)al;
+            if (!fits(l, h)) return false;
+            *lo = (int64_t)l; *hi = (int64_t)h; return true;
+        }
         case SDQH_X_YEAR: if (!op_interval(ctx, x, o.a, &al, &ah) || al < 0) return false; *lo = al / 10000; *hi = ah / 10000; return true;
         case SDQH_X_DIVI: if (!op_interval(ctx, x, o.a, &al, &ah) || al < 0) return false; *lo = al / o.imm_i; *hi = ah / o.imm_i; return true;
         case SDQH_X_MODI: if (!op_interval(ctx, x, o.a, &al, &ah) || al < 0) return false; *lo = 0; *hi = std::min<int64_t>(ah, o.imm_i - 1); return true;
