@@ -486,6 +486,15 @@ int sdqh_lookup_aggregate_block(sdqh_ctx* ctx, int64_t nrows, const sdqh_filter*
 #define SDQH_X_STR    40   /* predicate `aux` (SDQH_STR_*) of STR column `col` against the constant str[0..slen): bool     */
 #define SDQH_X_STRIDX 41   /* firstIndex(col, constant): position of the first occurrence, -1 if none (varchar.h:91-97), i64 */
 #define SDQH_X_CHAR   42   /* code unit `aux` of STR column `col` (0 past the text), i64 — substr() as group-key parts     */
+#define SDQH_X_RUNNEW 43   /* "first of its run": key = I64 column `col` (K), value = COL operation a (V, i64), b = -1 or a bool operation G whose
+                            * operands are COL / CONST / arithmetic / comparison / AND / OR / NOT / SELECT operations only (it is evaluated at other
+                            * rows).  bool: true iff NO row r' < r has K[r'] = K[r], V[r'] = V[r] and (b = -1 or G(r')).  Gated by G itself, a count
+                            * of the true rows per key is the number of DISTINCT values per key (the reference's `{k: vector({v})}` in Python mode
+                            * and `dictSize` of its entries).  K must be non-decreasing over the column (equal keys are neighbours, so the candidates
+                            * r' are the rows directly in front of r); otherwise the call fails with SDQH_ERR_UNSUPPORTED.  Exact for any run
+                            * length; a run of L equal keys costs O(L^2) reads.  Evaluated by the sum, group-by and probe-aggregate calls; builds,
+                            * key sets and stages refuse it (SDQH_ERR_UNSUPPORTED).  An implementation may refuse the operation altogether
+                            * (SDQH_ERR_UNSUPPORTED, "unknown operation code"): callers keep a route that does not need it. */
 
 #define SDQH_STR_EQ 0      /* the modes of sdqh_spred.negate */
 #define SDQH_STR_NE 1

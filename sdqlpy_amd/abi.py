@@ -128,6 +128,7 @@ X_ADD, X_SUB, X_MUL, X_DIV, X_NEG, X_I2F, X_YEAR, X_PACK2, X_DIVI, X_MODI = 10, 
 X_LT, X_LE, X_GT, X_GE, X_EQ, X_NE = 20, 21, 22, 23, 24, 25
 X_AND, X_OR, X_NOT, X_SELECT = 30, 31, 32, 33
 X_STR, X_STRIDX, X_CHAR = 40, 41, 42
+X_RUNNEW = 43      # first row of its key run that carries its value (include/sdqh.h): distinct values per key on a table stored in key order
 MAX_XOPS, MAX_XCOLS, MAX_XTABLES, MAX_XGATES, MAX_XSTR = 96, 16, 6, 16, 256
 
 

@@ -103,7 +103,7 @@ struct XInfo {
 
 bool op_is_light(const sdqh_xop& o) {        // evaluable on streamed registers
     switch (o.code) {
-        case SDQH_X_LOOKUP: case SDQH_X_FIELD: case SDQH_X_ACC: case SDQH_X_STR: case SDQH_X_STRIDX: case SDQH_X_CHAR: return false;
+        case SDQH_X_LOOKUP: case SDQH_X_FIELD: case SDQH_X_ACC: case SDQH_X_STR: case SDQH_X_STRIDX: case SDQH_X_CHAR: case SDQH_X_RUNNEW: return false;
         default: return true;
     }
 }
@@ -115,6 +115,11 @@ void closure(const sdqh_program* p, int k, std::vector<char>& seen) {       // t
     if (o.a < k) closure(p, o.a, seen);
     if (o.b < k) closure(p, o.b, seen);
     if (o.c < k) closure(p, o.c, seen);
+}
+
+bool has_runnew(const sdqh_program* p) {
+    for (int k = 0; k < p->nops; ++k) if (p->ops[k].code == SDQH_X_RUNNEW) return true;
+    return false;
 }
 
 void tight_plan(sdqh_ctx* ctx, int64_t nrows, XInfo* x);
@@ -167,6 +172,21 @@ int analyse(sdqh_ctx* ctx, int64_t nrows, const sdqh_program* p, int max_vals, b
                 }
                 break;
             case SDQH_X_CHAR: rc = need(o.col && o.col->dtype == SDQH_STR && o.col->nrows >= nrows && o.type == SDQH_T_I64 && o.aux >= 0, "CHAR needs a STR column"); break;
+            case SDQH_X_RUNNEW: {
+                rc = need(o.col && o.col->dtype == SDQH_I64 && o.col->nrows >= nrows && o.type == SDQH_T_BOOL && o.a >= 0 && o.a < k && p->ops[o.a].code == SDQH_X_COL && p->ops[o.a].type == SDQH_T_I64 &&
+                          (o.b == -1 || ty(o.b) == SDQH_T_BOOL), "RUNNEW needs an I64 key column covering nrows, an i64 COL value and no inner condition or a bool one");
+                if (!rc && o.b >= 0) {                                      // the inner condition is evaluated at OTHER rows: columns, constants and register arithmetic only
+                    std::vector<char> seen((size_t)p->nops, 0);
+                    closure(p, o.b, seen);
+                    bool movable = true;
+                    for (int j = 0; j < k; ++j) if (seen[(size_t)j]) movable = movable && op_is_light(p->ops[j]) && p->ops[j].code != SDQH_X_PACK2;
+                    rc = need(movable, "RUNNEW's inner condition may hold COL / CONST / arithmetic / comparison / AND / OR / NOT / SELECT operations only");
+                }
+                // equal keys must be neighbours: the rows in front of a row are then all the candidates (measured once per column, cached)
+                if (!rc && !ctx->compile_only && nrows > 1 && !column_nondecreasing(ctx, const_cast<sdqh_column*>(o.col)))
+                    rc = fail(ctx, SDQH_ERR_UNSUPPORTED, "program: operation " + std::to_string(k) + ": RUNNEW's key column is not stored in non-decreasing order");
+                break;
+            }
             default: rc = fail(ctx, SDQH_ERR_UNSUPPORTED, "program: unknown operation code " + std::to_string(o.code));
         }
         if (rc) return rc;
@@ -496,7 +516,7 @@ void tight_plan(sdqh_ctx* ctx, int64_t nrows, XInfo* x) {
         // columns the drain reads by row (keys and payloads of a build, operands of a probe hit): survivors are a few per cent of the
         // rows, scattered, so a gather moves whole lines for single values — through the 4-byte twin the same lines are half as many
         std::vector<char> by_row((size_t)x->ncols, 0);
-        for (int k = 0; k < p->nops; ++k) if (p->ops[k].code == SDQH_X_COL && !x->scope[(size_t)k]) by_row[(size_t)x->col_of[k]] = 1;
+        for (int k = 0; k < p->nops; ++k) if ((p->ops[k].code == SDQH_X_COL && !x->scope[(size_t)k]) || p->ops[k].code == SDQH_X_RUNNEW) by_row[(size_t)x->col_of[k]] = 1;
         for (int c = 0; c < x->ncols; ++c)
             if (by_row[(size_t)c] && x->cols[c]->dtype != SDQH_STR && column_narrow(ctx, const_cast<sdqh_column*>(x->cols[c]))) { x->gather32 |= 1u << c; any = true; }
     }
@@ -582,6 +602,7 @@ void tight_plan(sdqh_ctx* ctx, int64_t nrows, XInfo* x) {
 struct Gen {
     const XInfo& x; std::ostringstream os; std::vector<char> done; int mode = 0;      // mode 0: columns gathered by row r; 1: from streamed registers, half H; 2: stest (explicit .x / .y)
     const char* half = "";
+    std::string row = "r";                     // mode 0: the row the columns are read at (RUNNEW evaluates its inner condition at the rows in front of r)
     std::vector<int> slot_of;                  // column -> slot in the streamed register array
     std::vector<int> sres_of;                  // text operation -> its slot in the drain's staged results (-1: reads the column in global memory)
     // TIGHT (mode 3): an operation that depends on ONE byte-coded column and constants only is a table of <= 256 entries, filled once per
@@ -659,8 +680,8 @@ struct Gen {
         // (a column the loop also STREAMS through its 4-byte twin — the prefilter's key — is read again from that twin by the rows that
         //  are drained: the lines the wave has just streamed, still in L2, not the 8-byte original's)
         if (mode == 0 && (((x.gather32 | x.narrow_mask) >> c) & 1u))
-            return o.type == SDQH_T_F64 ? "narrow_decode(static_cast<const int32_t*>(a.ncol[" + std::to_string(c) + "])[r])" : "(int64_t)static_cast<const int32_t*>(a.ncol[" + std::to_string(c) + "])[r]";
-        if (mode == 0) return std::string("static_cast<const ") + (o.type == SDQH_T_F64 ? "double" : "int64_t") + "*>(a.col[" + std::to_string(c) + "])[r]";
+            return o.type == SDQH_T_F64 ? "narrow_decode(static_cast<const int32_t*>(a.ncol[" + std::to_string(c) + "])[" + row + "])" : "(int64_t)static_cast<const int32_t*>(a.ncol[" + std::to_string(c) + "])[" + row + "]";
+        if (mode == 0) return std::string("static_cast<const ") + (o.type == SDQH_T_F64 ? "double" : "int64_t") + "*>(a.col[" + std::to_string(c) + "])[" + row + "]";
         if (mode == 4) return o.type == SDQH_T_F64 ? "x_f(dv)" : "dv";         // tabulating: the dictionary entry
         if (mode == 3) {                                                   // TIGHT: row i of the lane's 8, out of the packed words s.c<slot>
             const std::string w = "s.c" + std::to_string(slot_of[(size_t)c]);
@@ -679,6 +700,11 @@ struct Gen {
         if (mode == 1) raw = "(H == 0 ? s[" + std::to_string(slot_of[(size_t)c]) + "].x : s[" + std::to_string(slot_of[(size_t)c]) + "].y)";
         else raw = "s[" + std::to_string(slot_of[(size_t)c]) + "]." + half;
         return o.type == SDQH_T_F64 ? "x_f(" + raw + ")" : raw;
+    }
+    // an I64 column read by row (mode 0), through its 4-byte twin where the drained rows read that
+    std::string i64_at(int c, const std::string& at) const {
+        if (((x.gather32 | x.narrow_mask) >> c) & 1u) return "(int64_t)static_cast<const int32_t*>(a.ncol[" + std::to_string(c) + "])[" + at + "]";
+        return "static_cast<const int64_t*>(a.col[" + std::to_string(c) + "])[" + at + "]";
     }
     void emit(int k) {
         if (k < 0 || done[(size_t)k]) return;
@@ -701,7 +727,7 @@ struct Gen {
         }
         switch (o.code) {
             case SDQH_X_COL: e = col_expr(k); break;
-            case SDQH_X_ROWID: e = "r"; break;
+            case SDQH_X_ROWID: e = mode == 0 ? row : "r"; break;
             case SDQH_X_CONST:
                 e = o.type == SDQH_T_F64 ? "a.cf[" + std::to_string(x.const_of[k]) + "]" : (o.type == SDQH_T_BOOL ? "(a.ci[" + std::to_string(x.const_of[k]) + "] != 0)" : "a.ci[" + std::to_string(x.const_of[k]) + "]");
                 break;
@@ -767,6 +793,30 @@ struct Gen {
                 }
                 const std::string c = std::to_string(x.col_of[k]);
                 e = text_op(k, "static_cast<const uint32_t*>(a.col[" + c + "]) + r * (int64_t)a.width[" + c + "], a.width[" + c + "]");
+                break;
+            }
+            case SDQH_X_RUNNEW: {
+                // Is this row the first of its run of equal keys that carries its value (among the rows that pass the inner condition)?
+                // The key column never decreases, so the candidates are the rows directly in front: walk back while the key matches.
+                // Global memory (or the 4-byte twins) only: tiles, waves, workgroups and segments end wherever they like.  Exact for any
+                // run length; a run of L rows costs its rows O(L) reads each.
+                if (mode != 0) { e = "false"; break; }                         // (never on streamed registers: op_is_light)
+                emit(o.a);
+                flush_pins();
+                const int kc = x.col_of[k], vc = x.col_of[o.a];
+                os << "        bool n" << K << " = true;\n        {\n";
+                os << "            const int64_t k0 = " << i64_at(kc, row) << ";\n";
+                os << "            for (int64_t q = " << row << " - 1; q >= 0; --q) {\n";
+                os << "                if (" << i64_at(kc, "q") << " != k0) break;\n";
+                os << "                if (" << i64_at(vc, "q") << " != " << v(o.a) << ") continue;\n";
+                if (o.b >= 0) {
+                    Gen inner(x);
+                    inner.mode = 0; inner.row = "q";
+                    inner.emit(o.b);
+                    os << "                {\n" << inner.os.str() << "        if (!" << v(o.b) << ") continue;\n                }\n";
+                }
+                os << "                n" << K << " = false;\n                break;\n            }\n        }\n";
+                e = "n" + K;
                 break;
             }
             default: e = "0";
@@ -1746,6 +1796,7 @@ int sdqh_xbuild(sdqh_ctx* ctx, int64_t nrows, const sdqh_program* prog, int64_t 
     auto lap = [&](const char* what) { if (phase_times) { auto t1 = t_now(); fprintf(stderr, "xbuild %-12s %6.1f us\n", what, std::chrono::duration<double, std::micro>(t1 - t0).count()); t0 = t1; } };
     XInfo x;
     if (int rc = analyse(ctx, nrows, prog, SDQH_MAX_PAYLOAD, true, false, &x)) return rc;
+    if (has_runnew(prog)) return fail(ctx, SDQH_ERR_UNSUPPORTED, "xbuild: RUNNEW is evaluated by the sum, group-by and probe-aggregate sinks only");
     lap("analyse");
     vstage_plan(ctx, nrows, &x);
     lap("vstage_plan");
@@ -1886,6 +1937,7 @@ int sdqh_xkey_set(sdqh_ctx* ctx, int64_t nrows, const sdqh_program* prog, int64_
     if (!ctx->compile_only) (void)hipSetDevice(ctx->device);
     XInfo x;
     if (int rc = analyse(ctx, nrows, prog, 0, true, false, &x)) return rc;
+    if (has_runnew(prog)) return fail(ctx, SDQH_ERR_UNSUPPORTED, "xkey_set: RUNNEW is evaluated by the sum, group-by and probe-aggregate sinks only");
     if (key_lo > key_hi) { if (nrows > 0) return fail(ctx, SDQH_ERR_UNSUPPORTED, "xkey_set: needs the key's bounds"); key_lo = key_hi = 0; }
     if (key_lo <= INT64_MIN / 2 || key_hi >= INT64_MAX / 2 || (uint64_t)(key_hi - key_lo) + 1 > (1ull << 31))
         return fail(ctx, SDQH_ERR_UNSUPPORTED, "xkey_set: key range too wide for a bitmap");

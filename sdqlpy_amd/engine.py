@@ -20,8 +20,8 @@ import weakref
 import numpy as np
 
 from . import abi, build
-from .frontend import (And, Bin, Call, Cmp, Col, Const, Contains, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField, RecordCons,
-                       ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WrapScalarOp)
+from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
+                       RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
 from .result import DeferredResultSet, Pending, DictResult, ResultSet, TextRefs, decode_text
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -142,6 +142,10 @@ class Engine:
         # sums over result dictionaries that ran on the HOST (xplan.run_host_dict): {(source line, result name): {"runs", "why"}}; with
         # strict_device such a loop raises UnsupportedQuery instead (tests run the shipped queries that way to say which ones take it)
         self.host_loops = {}
+        # dictionaries of sets (frontend.DistinctOp): {(source line, result name): {"route": "fast" | "generic", "runs", "why"}} — which of
+        # _prepare_distinct's two routes each such loop took, and what sent it to the generic one
+        self.distinct_loops = {}
+        self.distinct_fast = os.environ.get("SDQLPY_AMD_DISTINCT_FAST", "1") != "0"      # 0: every such loop takes the generic route (A/B measurements, tests)
         self.strict_device = os.environ.get("SDQLPY_AMD_STRICT_DEVICE", "0") == "1"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
@@ -170,6 +174,8 @@ class Engine:
         """What the engine did besides launching kernels: loops that ran on the host (and why), plan graphs recorded / launched /
         refused, resident bytes."""
         return {"host_loops": [{"line": k[0], "result": k[1], "runs": v["runs"], "why": v["why"]} for k, v in sorted(self.host_loops.items(), key=lambda kv: str(kv[0]))],
+                "distinct_loops": [{"line": k[0], "result": k[1], "route": v["route"], "runs": v["runs"], "why": v["why"]}
+                                   for k, v in sorted(self.distinct_loops.items(), key=lambda kv: str(kv[0]))],
                 "plan_graphs": dict(self.graph_stats), "resident_bytes": int(self.resident_bytes), "lanes": int(self.nlanes)}
 
     def synchronize(self):
@@ -1550,7 +1556,7 @@ def _lazy_rows_ok(bt, out_key_fields, fields_of, top):
         return False
     if not (any(src == "key" for _, src in out_key_fields) or bt.shared_groups) or bt.int_values:
         return False
-    return all(src == "key" or bt.decoder_of(fields_of.get(f), src) is None for f, src in out_key_fields)
+    return all((src == "key" and bt.key_decoder is None) or (src != "key" and bt.decoder_of(fields_of.get(f), src) is None) for f, src in out_key_fields)
 
 
 def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=False):
@@ -1613,13 +1619,19 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             raw = keys if src == "key" else payload[src]
             if sel is not None:
                 raw = raw[sel]
-            return raw if src == "key" else _decode_column(raw, bt.decoder_of(fields_of.get(fname), src), bt.payload_dtypes[src])
+            if src == "key":                                 # (a key that stands for text — a large group-by keyed by one text value — reads as the text)
+                return raw if bt.key_decoder is None else _decode_column(raw, bt.key_decoder, np.int64)
+            return _decode_column(raw, bt.decoder_of(fields_of.get(fname), src), bt.payload_dtypes[src])
         def decode_late(fname, src):                         # text of a large result is gathered when it is first read
-            dec = None if src == "key" else bt.decoder_of(fields_of.get(fname), src)
-            return decode_text(payload[src], dec) if dec is not None and dec.dtype.kind == "U" else decode(fname, src)
+            dec = bt.key_decoder if src == "key" else bt.decoder_of(fields_of.get(fname), src)
+            return decode_text(keys if src == "key" else payload[src], dec) if dec is not None and dec.dtype.kind == "U" else decode(fname, src)
         if entry_is_group or ordered:
             d = DictResult([(f, decode_late(f, src)) for f, src in out_key_fields], _value_arrays(vnames, count_idx, values, hits, bt.int_values),
                            key_is_record, val_is_record)
+            if bt.key_decoder is not None and any(src == "key" for _, src in out_key_fields) and not ordered:
+                from .result import Dictionary
+                if not isinstance(bt.key_decoder, Dictionary):
+                    d = _merge_equal_keys(d)                 # row references: two rows may hold the same text
             d.ordered = ordered
             if lazy:
                 d.ready = eng.ctx.result_wait                 # the rows are still on their way: whoever reads them first waits
@@ -1921,6 +1933,88 @@ def _record_set(eng, op, bt, env):
         bt.table.free()
 
 
+# =================================================================================================
+# Dictionaries of sets (frontend.DistinctOp: `{k: vector({v})}`, read back as dictSize(tbl[k])) — the reference's K-E shape, with the
+# set semantics of its Python mode.  All a later loop can ask of such a dictionary is the SIZE of an entry, so what is kept per key is
+# the number of distinct values: a table keyed by k whose row count (hits) is that number — exactly what an aggregation `{k: 1}` over
+# the distinct (k, v) pairs leaves behind, and what `tbl[k].distinct` (frontend.DistinctCount) reads through SDQH_X_ACC.  Two routes:
+#
+#   fast      ONE pass: `{k: 1}` over the rows that are the first of their key run to carry their value (frontend.RunNew ->
+#             SDQH_X_RUNNEW).  Needs the key column stored in non-decreasing order (lineitem by l_orderkey) and a library that has the
+#             operation; either refusal is SDQH_ERR_UNSUPPORTED and sends the loop to the generic route for good.
+#   generic   existing calls only, any row order, both libraries: the distinct (k, v) pairs as an aggregation keyed by the packed pair
+#             (as the shipped Q16 makes its combinations), then their number per k as a device loop over that dictionary's entries.
+#             The packing holds k in [0, 2^31) and v in [0, 2^32): anything wider is refused (UnsupportedQuery), never miscounted.
+# =================================================================================================
+def _prepare_distinct(eng, op, htab):
+    from . import xplan
+    root = getattr(eng, "_eng", eng)
+    vrec = RecordCons([(DISTINCT_FIELD, Const(1))])
+    state = {"route": None, "why": ""}
+
+    fast_scan = ScanOp(op.out, op.table, op.lineno)
+    fast_scan.kind, fast_scan.key, fast_scan.val = "dict", op.key, vrec
+    fast_scan.conds = list(op.conds) + [RunNew(op.key, op.value, list(op.conds))]
+    fast = xplan.prepare_scan(eng, fast_scan, htab, {}, False, as_table=True)
+
+    pairs_name = op.out + "$pairs"
+    pairs = ScanOp(pairs_name, op.table, op.lineno)
+    pairs.kind, pairs.conds, pairs.val = "dict", list(op.conds), Const(1)
+    pairs.key = RecordCons([("k", op.key), ("v", op.value)])
+    run_pairs = xplan.prepare_scan(eng, pairs, htab, {}, False, as_table=True)
+    counts = HostDictOp(op.out, pairs_name, [], WholeKey(0, "k"), vrec, False, op.lineno)
+    run_counts = xplan.prepare_dict_scan(eng, counts, as_table=True)
+    too_wide = "line %d: the (key, value) pairs of the dictionary of sets '%s' do not fit the pair packing (key in [0, 2^31), value in [0, 2^32))" % (op.lineno, op.out)
+
+    def empty(env):
+        """No pair at all: a table whose one entry no row reached — every key reads as absent, every size as 0."""
+        table = eng.ctx.hash_build_unique(1, abi.make_filter(), [], eng.iota_column(0, 1), [], accumulate=True)
+        bt = BuiltTable(table, "key", False, [], True, [])
+        bt.agg = ([("key", "key")], [DISTINCT_FIELD], 0, False, True, 0)
+        env[op.out + "$groups"] = bt
+        return ("aggregated", op.out + "$groups")
+
+    def generic(env):
+        try:
+            env[pairs_name] = run_pairs(env)
+            out = run_counts(env)
+        except abi.SdqhError as exc:
+            if exc.code != abi.ERR_UNSUPPORTED:
+                raise
+            raise UnsupportedQuery("%s: %s" % (too_wide, exc))
+        except UnsupportedQuery as exc:
+            raise UnsupportedQuery("%s: %s" % (too_wide, exc))
+        if out is NotImplemented:
+            return empty(env)
+        return out
+
+    def note(route):
+        rec = root.distinct_loops.setdefault((op.lineno, op.out), {"route": route, "runs": 0, "why": ""})
+        rec["route"], rec["why"] = route, state["why"]
+        rec["runs"] += 1
+
+    def run(env):
+        if state["route"] != "generic" and not getattr(eng, "distinct_fast", True):
+            state["route"], state["why"] = "generic", "the fast route is switched off (Engine.distinct_fast)"
+        if state["route"] != "generic":
+            try:
+                out = fast(env)
+                state["route"] = "fast"
+                note("fast")
+                return out
+            except abi.SdqhError as exc:
+                if exc.code != abi.ERR_UNSUPPORTED:
+                    raise
+                state["why"] = str(exc)
+            except UnsupportedQuery as exc:
+                state["why"] = str(exc)
+            state["route"] = "generic"                           # (remembered per prepared plan, like every other route decision)
+        out = generic(env)
+        note("generic")
+        return out
+    return run
+
+
 def _membership_only(plan):
     """Names of unique builds that are only used as `tbl[key] != None` / joinProbe index with no
     payload access, and are not the plan's result."""
@@ -2083,6 +2177,8 @@ class PreparedPlan:
             if isinstance(op, ScanOp):
                 self.steps.append((op.out, _prepare_scan(eng, op, tables[op.table], accumulate_into, op.out in member_only, op.out in looked_up,
                                                          coded_text=op.out in compared)))
+            elif isinstance(op, DistinctOp):
+                self.steps.append((op.out, _prepare_distinct(eng, op, tables[op.table])))
             elif isinstance(op, SelectKeysOp):
                 self.steps.append((op.out, (lambda env, op=op: _select_keys(eng, op, env))))
             elif isinstance(op, ScalarExprOp):

@@ -57,6 +57,31 @@ class PayloadField(Expr):
         return "Payload(%s[%r].%s)" % (self.lookup.dict_name, self.lookup.key, self.field)
 
 
+DISTINCT_FIELD = "distinct"     # the one value field of a dictionary of sets as the executor keeps it: the size of each set
+
+
+class DistinctCount(PayloadField):
+    """`dictSize(tbl[key])` where `tbl = T.sum(lambda p: {k: vector({v})})`: the number of DISTINCT v among the rows of key k (the
+    reference's Python mode keeps such vectors as sets: `vector.__add__` is a set union, lib/sdql_lib.py).  An integer; 0 for a key
+    the dictionary does not hold — the reference would raise there, and its own query only measures entries behind a guard.  To every
+    pass that walks expressions it is the field DISTINCT_FIELD of the looked-up entry."""
+    def __init__(self, lookup):
+        PayloadField.__init__(self, lookup, DISTINCT_FIELD)
+
+    def __repr__(self):
+        return "dictSize(%s[%r])" % (self.lookup.dict_name, self.lookup.key)
+
+
+class RunNew(Expr):
+    """Condition made by the EXECUTOR, never by the front end (engine.py: the fast route of a DistinctOp): this row is the first
+    of its run of equal `key` values that carries `value`, among the rows passing `conds` (SDQH_X_RUNNEW, include/sdqh.h)."""
+    def __init__(self, key, value, conds):
+        self.key, self.value, self.conds = key, value, conds
+
+    def __repr__(self):
+        return "RunNew(%r, %r, %r)" % (self.key, self.value, self.conds)
+
+
 class Lookup(Expr):
     """`tbl[key]`: key is an Expr or a RecordCons."""
     def __init__(self, dict_name, key):
@@ -206,6 +231,17 @@ class ScanOp:
     def __repr__(self):
         return "ScanOp(%s <- %s%s: if %r: {%r: %r}%s)" % (self.out, self.table, " probe " + repr(self.probe) if self.probe else "",
                                                           self.conds, self.key, self.val, " unique" if self.unique else "")
+
+
+class DistinctOp:
+    """`T.sum(lambda p: {K: vector({V})} [if C else None])` over a database table: per key the SET of its values (the reference's
+    K-E shape, generator_par.py's vector-valued dictionaries, as its Python mode evaluates them).  The only thing a later loop can do
+    with the result is measure an entry: `dictSize(out[k])` (DistinctCount)."""
+    def __init__(self, out, table, key, value, conds, lineno):
+        self.out, self.table, self.key, self.value, self.conds, self.lineno = out, table, key, value, conds, lineno
+
+    def __repr__(self):
+        return "DistinctOp(%s <- %s: if %r: {%r: vector({%r})})" % (self.out, self.table, self.conds, self.key, self.value)
 
 
 class ScalarField(Expr):
@@ -591,6 +627,7 @@ class _Lowerer:
         self.scalars = set()     # names bound to scalar / scalar-record sums
         self.params = []
         self.dicts = set()      # names bound to operator outputs
+        self.vectors = set()    # ... those that are dictionaries of sets (DistinctOp): only dictSize(name[key]) may read them
 
     def fail(self, node, why):
         ln = getattr(node, "lineno", 0)
@@ -636,6 +673,8 @@ class _Lowerer:
                 return PayloadField(inner, node.attr)
             self.fail(node, "unsupported attribute access")
         if isinstance(node, ast.Subscript):
+            if isinstance(node.value, ast.Name) and node.value.id in self.vectors:
+                self.fail(node, "an entry of '%s' is a set: only its size can be read, dictSize(%s[key])" % (node.value.id, node.value.id))
             if isinstance(node.value, ast.Name) and node.value.id in self.dicts:
                 key = self.expr(self._slice(node), env)
                 return Lookup(node.value.id, key)
@@ -730,6 +769,13 @@ class _Lowerer:
                     if isinstance(col, Col) and all(isinstance(x, Const) and isinstance(x.value, int) for x in (a, b)) and 0 <= a.value <= b.value:
                         return Call("substr", [col, a, b])
                     self.fail(node, "substr needs (<string column>, start, end) with literal bounds")
+                if fn.id == "dictSize" and len(node.args) == 1:
+                    arg = node.args[0]
+                    if isinstance(arg, ast.Subscript) and isinstance(arg.value, ast.Name) and arg.value.id in self.vectors:
+                        return DistinctCount(Lookup(arg.value.id, self.expr(self._slice(arg), env)))
+                    self.fail(node, "dictSize is only supported as dictSize(tbl[key]) with tbl a dictionary of sets, T.sum(lambda p: {k: vector({v})})")
+                if fn.id == "vector":
+                    self.fail(node, "vector({...}) is only supported as the whole value of a table sum's dictionary, {key: vector({value})}")
             if isinstance(fn, ast.Attribute) and fn.attr == "concat" and len(node.args) == 1:
                 a, b = self.expr(fn.value, env), self.expr(node.args[0], env)
                 if isinstance(a, WholeKey) and isinstance(b, WholeKey) and a.which == 0 and b.which == 1:
@@ -783,8 +829,8 @@ class _Lowerer:
             node = node.body
         return isinstance(node, ast.Dict)
 
-    def dict_body(self, op, node, env):
-        """{K: V}"""
+    def dict_body(self, op, node, env, vectors_ok=False):
+        """{K: V}; with vectors_ok, V may be vector({E}): op.val = ("vector", E)"""
         if not (isinstance(node, ast.Dict) and len(node.keys) == 1):
             self.fail(node, "expected a one-entry dictionary {key: value}")
         key = self.expr(node.keys[0], env)
@@ -796,8 +842,14 @@ class _Lowerer:
                 op.dense = key.args[0].value if isinstance(key.args[0], Const) else None
                 key = key.args[1]
         op.key = key
-        op.val = self.expr(node.values[0], env)
         op.kind = "dict"
+        v = node.values[0]
+        if isinstance(v, ast.Call) and isinstance(v.func, ast.Name) and v.func.id == "vector":
+            if not (vectors_ok and len(v.args) == 1 and isinstance(v.args[0], ast.Set) and len(v.args[0].elts) == 1):
+                self.fail(v, "vector({...}) is only supported as the value of a sum over a database table, holding one expression: {key: vector({value})}")
+            op.val = ("vector", self.expr(v.args[0].elts[0], env))
+            return
+        op.val = self.expr(v, env)
 
     # -- statements -------------------------------------------------------------------------
     def lambda_of(self, node, nparams):
@@ -819,7 +871,11 @@ class _Lowerer:
                 body, conds = self.split_ifelse(body, env)
                 op.conds = conds
                 if isinstance(body, ast.Dict):
-                    self.dict_body(op, body, env)
+                    self.dict_body(op, body, env, vectors_ok=True)
+                    if isinstance(op.val, tuple):                     # {K: vector({V})}: per key the set of its values
+                        if isinstance(op.key, RecordCons) or isinstance(op.val[1], RecordCons):
+                            self.fail(body, "a dictionary of sets needs a single key and a single value expression")
+                        return DistinctOp(out, table, op.key, op.val[1], conds, ln)
                 elif isinstance(body, ast.Call) and isinstance(body.func, ast.Name) and body.func.id == "record" \
                         and len(body.args) == 1 and isinstance(body.args[0], ast.Dict):
                     # record of independent sums, each possibly under its own condition (Q14: test/test_all.py:703-711)
@@ -858,6 +914,8 @@ class _Lowerer:
                     self.fail(call, "joinProbe takes (index, column, filter, outputFunc[, is_update])")
                 if not (isinstance(call.args[0], ast.Name) and call.args[0].id in self.dicts):
                     self.fail(call, "joinProbe's index must be the result of an earlier build")
+                if call.args[0].id in self.vectors:
+                    self.fail(call, "'%s' is a dictionary of sets: it cannot be a joinProbe index (only dictSize(%s[key]) reads it)" % (call.args[0].id, call.args[0].id))
                 colname = self._const_str(call.args[1])
                 (p,), fbody = self.lambda_of(call.args[2], 1)
                 cond = self.expr(fbody, {p: ("rowpair",)})
@@ -882,6 +940,8 @@ class _Lowerer:
                         op.unique = True        # 5th arg False => assignment sum (ref sdql_compiler.py:203-205)
                 return op
             self.fail(call, "unsupported table method '%s'" % fn.attr)
+        if table in self.vectors:
+            self.fail(call, "'%s' is a dictionary of sets: it cannot be summed over (only dictSize(%s[key]) reads it)" % (table, table))
         if table in self.dicts and fn.attr == "sum":
             (p,), body = self.lambda_of(call.args[0], 1)
             env = {p: ("kv",)}
@@ -964,6 +1024,8 @@ class _Lowerer:
                 if isinstance(val, ast.Call) and isinstance(val.func, ast.Attribute) and isinstance(val.func.value, ast.Name):
                     ops.append(self.lower_call(name, val))
                     self.dicts.add(name)
+                    if isinstance(ops[-1], DistinctOp):
+                        self.vectors.add(name)
                     continue
                 if isinstance(val, ast.Call) and isinstance(val.func, ast.Name) and val.func.id == "sr_dict" and len(val.args) == 1 \
                         and isinstance(val.args[0], ast.Dict) and len(val.args[0].keys) == 1:
@@ -982,6 +1044,8 @@ class _Lowerer:
                         continue
                 self.fail(st, "unsupported assignment")
             if isinstance(st, ast.Return):
+                if isinstance(st.value, ast.Name) and st.value.id in self.vectors:
+                    self.fail(st, "'%s' is a dictionary of sets: it cannot be returned (only dictSize(%s[key]) reads it)" % (st.value.id, st.value.id))
                 if isinstance(st.value, ast.Name) and st.value.id in self.dicts:
                     result = st.value.id
                     continue

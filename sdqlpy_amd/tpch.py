@@ -115,6 +115,27 @@ DERIVED = {   # table -> {column: (dtype, base columns, function(base arrays...)
                  "l_shipinstruct": ("U25", ["l_orderkey", "l_linenumber"], lambda k, n: _pick(_INSTRUCT, 25, _mix(k * 8 + n, 6)))},
 }
 
+# Derived columns produced ONLY when `columns=` names them: `generate(..., columns=None)` and every column list that does not
+# mention them return exactly what they did before these existed (the golden fixtures pin input fingerprints).
+#   o_orderstatus: dbgen's rule is 'F' if every line of the order has l_linestatus 'F', 'O' if none has, else 'P'.  The generator
+#   ships every line 1..121 days after o_orderdate and calls a line 'F' when it shipped on or before 1995-06-17 (csrc/tpchgen.cpp),
+#   so an order dated on or before 1995-02-16 (121 days earlier) can only have 'F' lines and one dated 1995-06-17 or later only 'O'
+#   lines; the four months in between are 'P'.  About 47 % 'F', 5 % 'P'.
+_ALL_SHIPPED_BY, _NONE_SHIPPED_FROM = 19950216, 19950617
+NAMED_ONLY = {
+    "orders": {"o_orderstatus": ("U1", ["o_orderdate"],
+                                 lambda d: np.where(d <= _ALL_SHIPPED_BY, "F", np.where(d >= _NONE_SHIPPED_FROM, "O", "P")).astype("<U1"))},
+}
+
+
+def _derived_of(table, columns):
+    """The derived columns of a table that a `columns=` list can produce: DERIVED always, NAMED_ONLY when the list names them."""
+    out = dict(DERIVED.get(table, {}))
+    if columns is not None:
+        out.update({c: d for c, d in NAMED_ONLY.get(table, {}).items() if c in columns})
+    return out
+
+
 # the columns each hot-path query references (SURVEY.md §8a); used to keep SF=10 generation small
 QUERY_COLUMNS = {
     "q6": {"lineitem": ["l_shipdate", "l_discount", "l_quantity", "l_extendedprice"]},
@@ -165,6 +186,8 @@ QUERY_COLUMNS = {
            "orders": ["o_orderkey", "o_orderdate"], "nation": ["n_nationkey", "n_name"],
            "supplier": ["s_suppkey", "s_nationkey"], "part": ["p_partkey", "p_name"],
            "partsupp": ["ps_partkey", "ps_suppkey", "ps_supplycost"]},
+    "q21": {"supplier": ["s_suppkey", "s_name", "s_nationkey"], "lineitem": ["l_orderkey", "l_suppkey", "l_commitdate", "l_receiptdate"],
+            "orders": ["o_orderkey", "o_orderstatus"], "nation": ["n_nationkey", "n_name"]},
 }
 
 
@@ -174,7 +197,7 @@ def columns_for(queries):
     for q in queries:
         for t, cols in QUERY_COLUMNS[q].items():
             need.setdefault(t, set()).update(cols)
-    return {t: [c for c, _ in GENERATED[t] if c in cs] + [c for c in DERIVED.get(t, {}) if c in cs] for t, cs in need.items()}
+    return {t: [c for c, _ in GENERATED[t] if c in cs] + [c for c in _derived_of(t, cs) if c in cs] for t, cs in need.items()}
 
 
 _lib = None
@@ -269,7 +292,7 @@ def generate_table(table, sf, seed=DEFAULT_SEED, columns=None, row_range=None, t
 
 def _with_derived(table, sf, seed, columns, row_range, threads):
     """generate_table + the DERIVED text columns that were asked for (or all, with columns=None)."""
-    derived = DERIVED.get(table, {})
+    derived = _derived_of(table, columns)
     want_d = [c for c in derived if columns is None or c in columns]
     if not want_d:
         return generate_table(table, sf, seed, columns, row_range, threads)

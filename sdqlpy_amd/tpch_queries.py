@@ -443,6 +443,30 @@ def q20(nation, supplier, part, partsupp, lineitem):
     return promotion
 
 
+# ---- q21: suppliers who kept orders waiting: the only late supplier of a failed multi-supplier order, one nation -------------------
+# (EXISTS another supplier on the order / NOT EXISTS another LATE supplier on it, as two dictionaries of sets per order — the distinct
+#  suppliers, and the distinct suppliers that delivered late — whose sizes the last loop reads: more than one supplier, and of the late
+#  ones only this row's own.  A size read for an order the dictionary does not hold is 0.)
+@sdql_compile({"supplier": supplier_type, "lineitem": lineitem_type, "orders": order_type, "nation": nation_type})
+def q21(supplier, lineitem, orders, nation):
+    saudi = nation.sum(lambda n: {unique(n[0].n_nationkey): True} if n[0].n_name == "SAUDI ARABIA" else None)
+    saudi_suppliers = supplier.sum(
+        lambda s: {unique(s[0].s_suppkey): record({"s_name": s[0].s_name})} if saudi[s[0].s_nationkey] != None else None)      # noqa: E711
+    failed_orders = orders.sum(lambda o: {unique(o[0].o_orderkey): True} if o[0].o_orderstatus == "F" else None)
+    suppliers_of_order = lineitem.sum(lambda l: {l[0].l_orderkey: vector({l[0].l_suppkey})})
+    late_suppliers_of_order = lineitem.sum(
+        lambda l: {l[0].l_orderkey: vector({l[0].l_suppkey})} if l[0].l_receiptdate > l[0].l_commitdate else None)
+    waiting = lineitem.sum(
+        lambda l: {record({"s_name": saudi_suppliers[l[0].l_suppkey].s_name}): record({"numwait": 1})}
+        if l[0].l_receiptdate > l[0].l_commitdate
+        and saudi_suppliers[l[0].l_suppkey] != None and failed_orders[l[0].l_orderkey] != None      # noqa: E711
+        and dictSize(suppliers_of_order[l[0].l_orderkey]) > 1
+        and dictSize(late_suppliers_of_order[l[0].l_orderkey]) <= 1
+        else None)
+    kept_waiting = waiting.sum(lambda g: {unique(g[0].concat(g[1])): True})
+    return kept_waiting
+
+
 # ---- q22: global sales opportunity: well-funded customers of seven country codes without orders -------------------------
 @sdql_compile({"orders": order_type, "customer": customer_type})
 def q22(orders, customer):
@@ -467,7 +491,7 @@ def q22(orders, customer):
 
 
 QUERIES = {"q6": q6, "q1": q1, "q3": q3, "q5": q5, "q9": q9, "q4": q4, "q14": q14, "q18": q18, "q10": q10,
-           "q2": q2, "q11": q11, "q7": q7, "q8": q8, "q12": q12, "q13": q13, "q15": q15, "q16": q16, "q17": q17, "q19": q19, "q20": q20, "q22": q22}
+           "q2": q2, "q11": q11, "q7": q7, "q8": q8, "q12": q12, "q13": q13, "q15": q15, "q16": q16, "q17": q17, "q19": q19, "q20": q20, "q21": q21, "q22": q22}
 
 _TABLE_OF_PARAM = {"lineitem": "lineitem", "orders": "orders", "customer": "customer", "supplier": "supplier", "part": "part",
                    "partsupp": "partsupp", "nation": "nation", "region": "region"}
@@ -513,5 +537,6 @@ TPCH_ORDER = {
     "q16": (100, [("supplier_cnt", "desc"), ("p_brand", "asc"), ("p_type", "asc"), ("p_size", "asc")]),
     "q15": (1, [("total_revenue", "desc")]),
     "q20": (100, [("s_name", "asc")]),
+    "q21": (100, [("numwait", "desc"), ("s_name", "asc")]),
     "q22": (100, [("cntrycode", "asc")]),
 }

@@ -16,7 +16,7 @@ program is reused while those layouts stay the same.
 import numpy as np
 
 from . import abi
-from .frontend import (And, Bin, Call, Cmp, Col, Const, Contains, IfElse, Lookup, Not, Or, PayloadField, RecordCons,
+from .frontend import (And, Bin, Call, Cmp, Col, Const, Contains, IfElse, Lookup, Not, Or, PayloadField, RecordCons, RunNew,
                        ScalarField, StrIn, UnsupportedQuery, WholeKey)
 from .result import Dictionary, DictResult, Pending, ResultSet, TextRefs, decode_text
 
@@ -231,7 +231,7 @@ class Compiler:
             return self.field(e.lookup, e.field)
         if isinstance(e, Lookup):
             return self.field(e, None)
-        if isinstance(e, (Cmp, And, Or, Not, Contains, StrIn)):
+        if isinstance(e, (Cmp, And, Or, Not, Contains, StrIn, RunNew)):
             return self.cond(e)
         if isinstance(e, IfElse):
             c = self.cond(e.cond)
@@ -346,6 +346,8 @@ class Compiler:
             return XV(self.P.op(abi.X_NOT, abi.T_BOOL, a=self.cond(e.term).id), "b")
         if isinstance(e, Contains):
             return XV(self.found(e.lookup), "b")
+        if isinstance(e, RunNew):
+            return self.run_new(e)
         if isinstance(e, StrIn):
             return self.text_pred(self.value(e.col), e.needle, {"in": abi.STR_CONTAINS, "prefix": abi.STR_PREFIX, "suffix": abi.STR_SUFFIX}[e.how])
         if isinstance(e, Cmp):
@@ -380,6 +382,24 @@ class Compiler:
         if isinstance(v, XV) and v.t == "b":
             return v
         self.fail("%r is not a condition" % (e,))
+
+    def run_new(self, e):
+        """SDQH_X_RUNNEW: key and value must be integer COLUMNS as they are stored (a text value of few distinct texts: its dictionary
+        codes), the inner conditions comparisons between numeric columns and numbers — the library evaluates them at other rows."""
+        def stored_column(x, what):
+            v = self.as_int(self.value(x), what)
+            o = self.P.ops[v.id]
+            if o["code"] != abi.X_COL or o["type"] != abi.T_I64:
+                self.fail("%s must be an integer column of the scanned table as it is stored: %r" % (what, x))
+            return v, o["col"]
+        if isinstance(self.htab, DictTable):
+            self.fail("first-of-run tests need a database table")
+        _, kcol = stored_column(e.key, "the key of a dictionary of sets")
+        val, _ = stored_column(e.value, "the value of a dictionary of sets")
+        if not all(_is_light(c) for c in e.conds):
+            self.fail("the conditions of a dictionary of sets must compare numeric columns and numbers to be tested at neighbouring rows")
+        inner = self.cond(And(list(e.conds))).id if e.conds else -1
+        return XV(self.P.op(abi.X_RUNNEW, abi.T_BOOL, a=val.id, b=inner, col=kcol), "b")
 
     # -- group / build keys --------------------------------------------------------------------------------
     def key_parts(self, exprs):
@@ -770,7 +790,8 @@ def prepare_scan(eng, op, htab, accumulate_into, member_only, as_table=False, sm
         is not alive when it runs."""
         def half(with_values):
             c = Compiler(eng, op, htab, env)
-            gates, _ = gates_of(c, op.conds)
+            # (the build half collects the KEYS: a first-of-run test removes rows, never keys — and builds do not evaluate it)
+            gates, _ = gates_of(c, op.conds if with_values else [x for x in op.conds if not isinstance(x, RunNew)])
             parts = c.key_parts(key_fields)
             flat = [v for _, vs, _ in parts for v in vs]
             bounds = (1, 0)
@@ -840,7 +861,14 @@ def prepare_scan(eng, op, htab, accumulate_into, member_only, as_table=False, sm
         find the keys and once to sum.  Keys no row carries keep hits = 0 and are not in the dictionary (K-F's min_hits, Compiler.found)."""
         bounds, composite = st[4], st[7]
         span = bounds[1] - bounds[0] + 1
-        if composite or state.get("radix") is not None or not (1 <= span <= max(1 << 16, htab.nrows // 4)):
+        limit = max(1 << 16, htab.nrows // 4)
+        if any(isinstance(x, RunNew) for x in op.conds):
+            # a first-of-run count (Q21's suppliers per order: 60 M rows at SF=10 over an l_orderkey range of 60 M): the entries over
+            # lo..hi are made in 0.71 ms, the keys collected from the rows by a build of their own in 3.1 ms, and the counting pass is
+            # the same 1.0 ms into either table (profiles/q21_distinct_routes.txt) — so the one-pass form up to a range of twice the rows,
+            # while the range's key column stays below a gigabyte
+            limit = max(limit, min(2 * htab.nrows, 1 << 27))
+        if composite or state.get("radix") is not None or not (1 <= span <= limit):
             return False
         return (eng.iota_column(bounds[0], span), span)
 
@@ -943,7 +971,11 @@ def prepare_scan(eng, op, htab, accumulate_into, member_only, as_table=False, sm
             cp.P.gates = list(cp.P.gates) + [look]
         else:
             cp.P.bind_table(look, table)
-        ctx.xprobe_aggregate(htab.nrows, cp.P, look, table)
+        try:
+            ctx.xprobe_aggregate(htab.nrows, cp.P, look, table)
+        except abi.SdqhError:
+            table.free()                                           # (refused — an operation this library does not have: the caller has another route)
+            raise
         vals = cp.P.vals
         bt = BuiltTable(table, key_names[0], key_is_record, [], val_is_record, [])
         if composite:
