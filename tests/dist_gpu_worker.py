@@ -21,7 +21,7 @@ def result_digest(res):
     return out
 
 
-def main(rank, world, port, sf, out_path, qs=None, parts=None, digest=False, shuffled=False):
+def main(rank, world, port, sf, out_path, qs=None, parts=None, digest=False, shuffled=False, q3_rows=False):
     import numpy as np
     import torch.distributed as dist
     from sdqlpy_amd import engine, tpch
@@ -70,6 +70,10 @@ def main(rank, world, port, sf, out_path, qs=None, parts=None, digest=False, shu
                     # (a million rows per run: this rank's key partition as a digest, the ranks' digests added)
                     r = r.wait() if hasattr(r, "wait") else r
                     parts_d = runner._all_gather_array(np.array(result_digest(r), np.float64))
+                    if q3_rows:
+                        # ... and this rank's rows themselves, a .npy per column beside the output file: the test compares every group
+                        for c in r.columns:
+                            np.save(os.path.join(os.path.dirname(out_path), "q3_%s_run%d_rank%d_%s.npy" % (part, again, rank, c)), np.asarray(r.column(c)))
                     out["runs"][tag] = {"columns": r.columns, "digest": [float(x) for x in np.sum(parts_d, axis=0)], "local_rows": r.size(),
                                         "partitioning": runner.last_partitioning, "exchanged": dict(runner.exchanged_rows)}
                     continue
@@ -92,4 +96,5 @@ if __name__ == "__main__":
     main(int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4]), sys.argv[5],
          qs=sys.argv[6].split(",") if len(sys.argv) > 6 and sys.argv[6] else None,
          parts=sys.argv[7].split(",") if len(sys.argv) > 7 and sys.argv[7] else None,
-         digest=len(sys.argv) > 8 and sys.argv[8] == "digest", shuffled=len(sys.argv) > 9 and sys.argv[9] == "shuffled")
+         digest=len(sys.argv) > 8 and sys.argv[8] in ("digest", "digest+rows"), shuffled=len(sys.argv) > 9 and sys.argv[9] == "shuffled",
+         q3_rows=len(sys.argv) > 8 and sys.argv[8] == "digest+rows")

@@ -10,6 +10,7 @@ only difference from the reference is the order in which doubles are added.
 import numpy as np
 import pytest
 
+import exact_reference as X
 import helpers
 from sdqlpy_amd import engine, frontend, tpch
 from sdqlpy_amd import tpch_queries as Q
@@ -59,6 +60,64 @@ def _need_memory(host_gib, hbm_gib, *engines):
     if total_hbm >= 256 * (1 << 30) and vm.total >= need_host + 32 * (1 << 30):
         pytest.fail("this box has the memory, something is holding it: " + msg)
     pytest.skip(msg)
+
+
+# ---- SF=100 against an exact reference (tests/exact_reference.py: int64 cents, plain numpy) --------------------------------------------
+# The exact results per query, computed once per session from the generated columns (the generator is deterministic: the row counts are
+# asserted), and used by all five SF=100 tests.  Figures the tests measure are printed as "sf100-exact:" lines (pytest -s shows them;
+# profiles/sf100_exact_reference.txt is a copy of one run).
+_SF100_ROWS = {"lineitem": 600_018_671, "orders": 150_000_000, "customer": 15_000_000, "supplier": 1_000_000, "part": 20_000_000,
+               "partsupp": 80_000_000, "nation": 25, "region": 5}
+_EXACT_SF100 = {}
+
+
+def _figure(text):
+    import resource
+    print("sf100-exact: %s | host peak of this process %.1f GiB" % (text, resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 2 ** 20), flush=True)
+
+
+def _exact_sf100(db, qs):
+    """{query: exact result} at SF=100 for `qs`, which `db` holds the columns of: those not computed yet in one pass over lineitem."""
+    import time
+    for t, table in db.items():
+        assert len(table.getContainer()["data"][0]) == _SF100_ROWS[t], t
+    missing = [q for q in qs if q not in _EXACT_SF100]
+    if missing:
+        t0 = time.perf_counter()
+        _EXACT_SF100.update(X.exact_results(db, missing))
+        _figure("exact reference of %s in one pass: %.1f s; %s" % ("+".join(missing), time.perf_counter() - t0, "; ".join(
+            "%s %d groups, %d of one row" % (q, _EXACT_SF100[q].size(), _EXACT_SF100[q].one_row_groups()) for q in missing)))
+    return {q: _EXACT_SF100[q] for q in qs}
+
+
+def _close_to_exact_sf100(got, q, db, what):
+    worst = X.assert_close_to_exact(got, _exact_sf100(db, (q,))[q], "sf100/%s/%s" % (what, q))
+    _figure("%s %s: largest err/bound %.3g" % (what, q, worst))
+    return worst
+
+
+def _cpu_leg_sf100(oracle_lib, got, q, db):
+    """The CPU implementation on the same SF=100 tables (16 threads at most; its engine lives for this one query): the HIP result against
+    it at REL — sharp on q1's groups of 10^7 - 10^8 rows, where the exact reference's worst-case bound is about 1e-8 — and the CPU
+    implementation itself against the exact reference."""
+    import os
+    import time
+    import bench
+    cpu = engine.Engine(oracle_lib.context(threads=min(16, os.cpu_count() or 1)))
+    try:
+        t0 = time.perf_counter()
+        want = helpers.run_query(cpu, q, db)
+        want = want.wait() if hasattr(want, "wait") else want
+        _figure("CPU implementation %s: %.1f s" % (q, time.perf_counter() - t0))
+        got = got.wait() if hasattr(got, "wait") else got
+        cmp = bench.compare_results(got, want)
+        assert cmp["rows_equal"] and cmp["counts_equal"] and cmp["max_rel"] <= REL, (q, cmp)
+        if not isinstance(want, float):
+            assert cmp["rows"] > 0
+        _figure("HIP against the CPU implementation %s: largest relative difference %.3e" % (q, cmp["max_rel"]))
+        _close_to_exact_sf100(want, q, db, "CPU implementation")
+    finally:
+        cpu.close()
 
 
 def test_backend_is_hip(hip_lib):
@@ -406,16 +465,20 @@ def test_full_size_sf10_against_the_cpu_implementation(hip_engine, oracle_lib):
         hip_engine.clear()
 
 
-def test_sf100_on_one_gpu_q3_q6(hip_engine):
+def test_sf100_on_one_gpu_q3_q6(hip_engine, oracle_lib):
     """BASELINE configs[3]'s data size (SF=100: 600 M lineitem rows, 150 M orders) on ONE device — what every rank of the 8-GPU
     configuration holds an eighth of, and the size at which bitmaps stop fitting LDS / L2 and 32-bit offsets start to matter.
     Q6 against a numpy reduction of the same columns; Q3 additive over a split of lineitem at an odd row, counts of groups exact,
-    ORDER BY ... LIMIT on the device equal to ordering the full result, a second run bit-identical."""
+    ORDER BY ... LIMIT on the device equal to ordering the full result, a second run bit-identical.
+    And against references that are not the HIP path: Q6, EVERY Q3 group, the top 10 and Q1 (600 M rows through the tight encodings)
+    against the exact integer reference (tests/exact_reference.py) under its derived bound, one-row groups bit for bit; and against the
+    CPU implementation on the same tables at REL, which is itself held to the exact reference."""
     import psutil
     import torch
-    _need_memory(96, 120, *_MODULE_ENGINES)
-    qs = ("q3", "q6")
+    _need_memory(150, 120, *_MODULE_ENGINES)
+    qs = ("q1", "q3", "q6")
     db = tpch.generate(100, tables=sorted(tpch.columns_for(qs)), columns=tpch.columns_for(qs))
+    exact = _exact_sf100(db, qs)
     li = db["lineitem"].getContainer()
     col = dict(zip(li["headers"], li["data"]))
     n = len(col["l_shipdate"])
@@ -427,8 +490,17 @@ def test_sf100_on_one_gpu_q3_q6(hip_engine):
     del m
     got6 = helpers.run_query(hip_engine, "q6", db)
     assert abs(got6 - want6) <= 1e-9 * abs(want6), (got6, want6)
+    _close_to_exact_sf100(got6, "q6", db, "HIP")
+    _cpu_leg_sf100(oracle_lib, got6, "q6", db)
+    got1 = helpers.run_query(hip_engine, "q1", db)
+    _close_to_exact_sf100(got1, "q1", db, "HIP")
+    assert len(exact["q1"].m) == 4 and max(exact["q1"].m) > 100_000_000   # (groups the bound alone is loose on: the CPU leg below is sharp there)
+    _cpu_leg_sf100(oracle_lib, got1, "q1", db)
+    del got1
     whole = helpers.run_query(hip_engine, "q3", db)
     assert whole.size() > 1_000_000
+    _close_to_exact_sf100(whole, "q3", db, "HIP")
+    _cpu_leg_sf100(oracle_lib, whole, "q3", db)
     again = helpers.run_query(hip_engine, "q3", db)
     assert again.size() == whole.size() and all(np.array_equal(again.column(c), whole.column(c)) for c in whole.columns)
     del again
@@ -438,6 +510,7 @@ def test_sf100_on_one_gpu_q3_q6(hip_engine):
     want_rows = whole.top(10, order_by).ordered_rows()
     assert [r[0] for r in got] == [r[0] for r in want_rows]
     helpers.assert_rows_match(got, want_rows, 1e-10, "q3 top 10 at SF=100")
+    assert [r[0] for r in got] == X.top_keys(exact["q3"], 10)                  # ... and the exact reference's own ordering
     # additivity over a split of the probe side, group by group (keys: l_orderkey)
     cut = n // 2 + 777
     keys = whole.column("l_orderkey")
@@ -1699,7 +1772,9 @@ def test_eight_ranks_share_one_gpu_at_sf100(hip_lib, tmp_path):
     runner's hybrid mode; RCCL over xGMI is what an 8-GPU node adds).  Each rank holds an SF=12.5 row shard; every query three times
     (exact sizes, then twice with device-sized exchanges / folded groups) against the single-process plan on the whole SF=100 database:
     Q5 / Q9 row for row, Q3's 1.1 M rows through a digest that adds up over the ranks' key partitions (rows, key / date sums exact,
-    revenue to 1e-9).  Needs ~150 GiB of host memory and ~120 GiB of HBM: fails, not skips, on a box that has them."""
+    revenue to 1e-9).  Every Q5 / Q9 row, and every Q3 group of every rank (the ranks write their rows as .npy files; the union of their
+    keys is the reference's key set), also against the exact integer reference (tests/exact_reference.py) under its derived bound.
+    Needs ~150 GiB of host memory and ~120 GiB of HBM: fails, not skips, on a box that has them."""
     import json
     import os
     import socket
@@ -1714,7 +1789,7 @@ def test_eight_ranks_share_one_gpu_at_sf100(hip_lib, tmp_path):
         port = sk.getsockname()[1]
     out = str(tmp_path / "ranks8.json")
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "dist_gpu_worker.py")
-    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(sf), out, "q5,q9,q3", "hash", "digest"],
+    procs = [subprocess.Popen([sys.executable, worker, str(r), str(world), str(port), str(sf), out, "q5,q9,q3", "hash", "digest+rows"],
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for r in range(world)]
     logs = [p.communicate(timeout=1500)[0] for p in procs]
     for p, log in zip(procs, logs):
@@ -1736,8 +1811,13 @@ def test_eight_ranks_share_one_gpu_at_sf100(hip_lib, tmp_path):
                     assert gd[0] == wd[0] > 1_000_000, (gd[0], wd[0])
                     for name, a, b in zip(want.columns, gd[1:], wd[1:]):
                         assert abs(a - b) <= 1e-9 * max(abs(b), 1.0), (q, again, name, a, b)
+                    # every group of every rank against the exact reference, and the union of the ranks' keys against its key set
+                    ranks = [{c: np.load(str(tmp_path / ("q3_hash_run%d_rank%d_%s.npy" % (again, r, c)))) for c in res["columns"]} for r in range(world)]
+                    assert all(len(rk["l_orderkey"]) > 0 for rk in ranks) and sum(len(rk["l_orderkey"]) for rk in ranks) == wd[0]
+                    _close_to_exact_sf100({c: np.concatenate([rk[c] for rk in ranks]) for c in res["columns"]}, q, db, "8 ranks, run %d" % again)
                 else:
                     helpers.assert_rows_match(sorted(tuple(r) for r in res["rows"]), helpers.result_rows(want, res["columns"]), REL, "8 ranks/%s/%d" % (q, again))
+                    _close_to_exact_sf100(dict(zip(res["columns"], zip(*res["rows"]))), q, db, "8 ranks, run %d" % again)
             eng.clear()
             del db, want
         assert got["hash"]["fast_retries"] == 0 and got["hash"]["fast_runs"] >= 4, got["hash"]
@@ -1772,6 +1852,7 @@ def test_distributed_hash_join_world1_sf100(hip_lib):
             cmp = bench.compare_results(got.wait() if hasattr(got, "wait") else got, single)
             assert cmp["rows_equal"] and cmp["max_rel"] <= REL, cmp
             assert runner.exchanged_rows["build"] > 10_000_000
+            _close_to_exact_sf100(got, "q3", big, "distributed hash join, world 1, run %d" % again)
         assert runner.fast_runs == 1 and runner.fast_retries == 0
     finally:
         for obj in runners:
@@ -1781,12 +1862,13 @@ def test_distributed_hash_join_world1_sf100(hip_lib):
         eng.close()
 
 
-def test_sf100_on_one_gpu_q5_q9(hip_engine):
+def test_sf100_on_one_gpu_q5_q9(hip_engine, oracle_lib):
     """BASELINE configs[4]'s data size (Q5 / Q9 at SF=100) on ONE device: totals against numpy reductions of the same columns where the
-    query allows, additivity over a split of lineitem at an odd row group by group, a second run identical."""
+    query allows, additivity over a split of lineitem at an odd row group by group, a second run identical.  Every group of both queries
+    against the exact integer reference under its derived bound, and against the CPU implementation on the same tables at REL."""
     import psutil
     import torch
-    _need_memory(110, 150, *_MODULE_ENGINES)
+    _need_memory(150, 150, *_MODULE_ENGINES)
     for q in ("q5", "q9"):
         cols = tpch.columns_for((q,))
         db = tpch.generate(100, tables=sorted(cols), columns=cols)
@@ -1796,6 +1878,8 @@ def test_sf100_on_one_gpu_q5_q9(hip_engine):
         whole = helpers.run_query(hip_engine, q, db)
         whole = whole.wait() if hasattr(whole, "wait") else whole
         assert whole.size() > 0
+        _close_to_exact_sf100(whole, q, db, "HIP")
+        _cpu_leg_sf100(oracle_lib, whole, q, db)
         again = helpers.run_query(hip_engine, q, db)
         _rows_match(again, whole, "sf100/%s/again" % q)                  # (group sums through LDS atomics: the order of the adds is not fixed)
         value_cols = [c for c in whole.columns if whole.column(c).dtype.kind == "f"]
@@ -1845,6 +1929,7 @@ def test_distributed_chain_world1_sf100(hip_lib):
             for again in range(2):
                 got = runner.run(q, db)
                 _rows_match(got, single, "sf100 distributed chain/%s/%d" % (q, again))
+                _close_to_exact_sf100(got, q, db, "distributed chain, world 1, run %d" % again)
             assert runner.collectives.get("all_gather", [0, 0])[1] > 0, runner.collectives      # replicas and partial groups really travelled, on device tensors
             eng.clear()
             del db, single, got
