@@ -19,6 +19,10 @@ TUPLE_A, TUPLE_AB, TUPLE_A_1MB, TUPLE_PRICING, TUPLE_A_1MB_M_CD, TUPLE_COUNT = 1
 TUPLE_MAX_VALUES = 4
 SORT_KEY, SORT_PAYLOAD, SORT_VALUE, SORT_HITS = 0, 1, 2, 3
 MAX_TOPK, MAX_SORT_KEYS = 128, 3
+# the HIP library's ordering extension (include/sdqh_sort.h): not part of EXPORTS — a library without these symbols still loads
+# (Library.has_sort is False there) and results are ordered on the host
+SORT_EXPORTS = ["sdqh_table_sorted", "sdqh_sort_geometry"]
+SORT_MAX_KEYS, SORT_ALL = 8, 1 << 62
 TUPLE_NVALUES = {TUPLE_A: 1, TUPLE_AB: 1, TUPLE_A_1MB: 1, TUPLE_PRICING: 4, TUPLE_A_1MB_M_CD: 1, TUPLE_COUNT: 0}
 TUPLE_NOPERANDS = {TUPLE_A: 1, TUPLE_AB: 2, TUPLE_A_1MB: 2, TUPLE_PRICING: 4, TUPLE_A_1MB_M_CD: 4, TUPLE_COUNT: 0}
 MAX_IPRED, MAX_FPRED, MAX_SPRED, MAX_STR_CONST = 4, 4, 1, 64
@@ -1114,6 +1118,41 @@ class Context:
         n = n.value
         return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
 
+    def table_sorted(self, table, min_hits, limit, sort, capacity_hint, want_hits=True):
+        """ORDER BY over the entries with at least min_hits rows, the first min(limit, n) of them (limit = SORT_ALL: all): sort as
+        table_topk takes it, up to SORT_MAX_KEYS columns, any number of rows.  The arrays are sized from capacity_hint; a result
+        that does not fit is fetched again with the exact size.  Returns (keys, payload, values, hits), in order."""
+        if not self.library.has_sort:
+            raise SdqhError(ERR_UNSUPPORTED, "table_sorted: %s has no ordering extension" % self.library.path)
+        arr = (SortKey * len(sort))()
+        for i, (kind, index, desc, is_f64) in enumerate(sort):
+            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
+        cap = max(1, min(int(capacity_hint), int(limit)))
+        for attempt in (0, 1):
+            keys = np.empty(cap, np.int64)
+            payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
+            values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
+            hits = np.empty(cap, np.int64) if want_hits else None
+            n = C.c_int64()
+            rc = self.lib.sdqh_table_sorted(self.handle, table.handle, C.c_int64(min_hits), C.c_int64(limit), C.c_int(len(sort)), arr, C.c_int64(cap),
+                                            _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), C.byref(n))
+            if rc == ERR_OVERFLOW and attempt == 0:
+                cap = max(1, n.value)
+                continue
+            self._check(rc)
+            break
+        self._after_call("table_sorted")
+        n = n.value
+        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
+
+    def sort_geometry(self):
+        """(largest n of the single-workgroup path, rows per tile of the radix path, smallest n with a second scan level or 0)."""
+        if not self.library.has_sort:
+            raise SdqhError(ERR_UNSUPPORTED, "sort_geometry: %s has no ordering extension" % self.library.path)
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self.lib.sdqh_sort_geometry(self.handle, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def table_entries(self, table):
         """(Columns [key, payload...], n): the table's entries as resident columns."""
         k = 1 + table.npayload
@@ -1305,6 +1344,11 @@ class Library:
         L.sdqh_lookup_aggregate.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.sdqh_lookup_aggregate_block.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        self.has_sort = all(hasattr(L, s) for s in SORT_EXPORTS)          # the ordering extension (include/sdqh_sort.h)
+        if self.has_sort:
+            L.sdqh_table_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p]
+            L.sdqh_sort_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
     def backend_name(self):
         return self.cdll.sdqh_backend_name().decode()

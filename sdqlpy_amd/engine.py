@@ -147,6 +147,9 @@ class Engine:
         self.distinct_loops = {}
         self.distinct_fast = os.environ.get("SDQLPY_AMD_DISTINCT_FAST", "1") != "0"      # 0: every such loop takes the generic route (A/B measurements, tests)
         self.strict_device = os.environ.get("SDQLPY_AMD_STRICT_DEVICE", "0") == "1"
+        # ORDER BY beyond sdqh_table_topk (more than 128 rows, more than 3 columns, no limit) on the device where the library has the
+        # ordering extension (abi.Context.table_sorted); 0: compact + host lexsort, as on a library without it (A/B measurements, tests)
+        self.device_sort = os.environ.get("SDQLPY_AMD_DEVICE_SORT", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1539,11 +1542,33 @@ def _device_sort_spec(bt, key_fields, vnames, count_idx, order):
     return spec
 
 
+def _device_sorts(eng, top, spec):
+    """Is `top` = (k, order) beyond sdqh_table_topk (more than MAX_TOPK rows or MAX_SORT_KEYS columns) and within the device's
+    ORDER BY (abi.Context.table_sorted: a library with the ordering extension, Engine.device_sort on)?"""
+    if top is None or spec is None or top[0] < 1 or len(spec) > abi.SORT_MAX_KEYS:
+        return False
+    if not (top[0] > abi.MAX_TOPK or len(spec) > abi.MAX_SORT_KEYS):
+        return False
+    return bool(getattr(eng, "device_sort", True)) and bool(getattr(eng.ctx.library, "has_sort", False))
+
+
+def _sorted(eng, table, min_hits, hint_key, top, spec, want_hits):
+    """ORDER BY (... LIMIT k) on the device in one waited-for call; the arrays are sized from the previous run of the same plan step."""
+    hint = eng.compact_hints.get(("sorted", hint_key))
+    cap = 4096 if hint is None else hint + hint // 8 + 1024
+    keys, payload, values, hits = eng.ctx.table_sorted(table, min_hits, min(int(top[0]), abi.SORT_ALL), spec, cap, want_hits=want_hits)
+    eng.compact_hints[("sorted", hint_key)] = len(keys)
+    return keys, payload, values, hits
+
+
 def _fetch_entries(eng, bt_table, min_hits, hint_key, top, spec, **want):
     """K-F rows of a table: all of them, or with `top` = (k, order) only the first k in that order
     when the device can order them (spec) — otherwise all, ordered afterwards on the host."""
     if top is not None and spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
         keys, payload, values, hits = eng.ctx.table_topk(bt_table, min_hits, top[0], spec, want_hits=want.get("want_hits", True))
+        return keys, payload, values, hits, True
+    if _device_sorts(eng, top, spec):
+        keys, payload, values, hits = _sorted(eng, bt_table, min_hits, hint_key, top, spec, want.get("want_hits", True))
         return keys, payload, values, hits, True
     keys, payload, values, hits = _compact(eng, bt_table, min_hits, hint_key, **want)
     return keys, payload, values, hits, False
@@ -1696,6 +1721,9 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             if top is not None and value.key_parts is None else None
         if top is not None and spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
             keys, payload, _, _ = eng.ctx.table_topk(value.table, 0, top[0], spec, want_hits=False)
+            ordered = True
+        elif _device_sorts(eng, top, spec):
+            keys, payload, _, _ = _sorted(eng, value.table, 0, hint_key, top, spec, False)
             ordered = True
         else:
             keys, payload, _, _ = _compact(eng, value.table, 0, hint_key, want_values=False, want_hits=False)

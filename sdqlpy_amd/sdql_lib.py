@@ -372,7 +372,13 @@ def sdql_compile(in_type):
             the reference (its Q3 returns the unordered set); ties keep build-row order."""
             return lambda *args: run(args, (k, list(order)))
 
+        def order_by(order):
+            """The same query finished with ORDER BY and no limit: every row, in order — ``top(abi.SORT_ALL, order)``."""
+            from . import abi
+            return top(abi.SORT_ALL, order)
+
         wrapper.top = top
+        wrapper.order_by = order_by
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
