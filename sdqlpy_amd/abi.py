@@ -23,6 +23,10 @@ MAX_TOPK, MAX_SORT_KEYS = 128, 3
 # (Library.has_sort is False there) and results are ordered on the host
 SORT_EXPORTS = ["sdqh_table_sorted", "sdqh_sort_geometry"]
 SORT_MAX_KEYS, SORT_ALL = 8, 1 << 62
+# the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
+# these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
+EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
+EXT_MIN, EXT_MAX = 0, 1
 TUPLE_NVALUES = {TUPLE_A: 1, TUPLE_AB: 1, TUPLE_A_1MB: 1, TUPLE_PRICING: 4, TUPLE_A_1MB_M_CD: 1, TUPLE_COUNT: 0}
 TUPLE_NOPERANDS = {TUPLE_A: 1, TUPLE_AB: 2, TUPLE_A_1MB: 2, TUPLE_PRICING: 4, TUPLE_A_1MB_M_CD: 4, TUPLE_COUNT: 0}
 MAX_IPRED, MAX_FPRED, MAX_SPRED, MAX_STR_CONST = 4, 4, 1, 64
@@ -1153,6 +1157,59 @@ class Context:
         self._check(self.lib.sdqh_sort_geometry(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def _need_extrema(self, what):
+        if not self.library.has_extrema:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
+
+    def table_extrema_begin(self, table, slots, ops):
+        """The named accumulator slots of `table` become extrema slots (ops: EXT_MIN / EXT_MAX): until table_extrema_end they hold
+        encoded values and must not be read."""
+        self._need_extrema("table_extrema_begin")
+        sl = (C.c_int32 * max(1, len(slots)))(*[int(x) for x in slots])
+        op = (C.c_int32 * max(1, len(ops)))(*[int(x) for x in ops])
+        self._check(self.lib.sdqh_table_extrema_begin(self.handle, table.handle, C.c_int(len(slots)), sl, op))
+        self._after_call("table_extrema_begin")
+
+    def table_extrema_fold(self, table, key, nrows, slot_values, count_hits=False):
+        """slot_values: [(slot, values Column, is_f64)] — for every row whose key is in the table, slot = op(slot, value)."""
+        self._need_extrema("table_extrema_fold")
+        n = len(slot_values)
+        sl = (C.c_int32 * max(1, n))(*[int(s) for s, _, _ in slot_values])
+        cols = (C.c_void_p * max(1, n))(*[None if c is None else c.handle.value for _, c, _ in slot_values])
+        f64 = (C.c_int32 * max(1, n))(*[int(bool(f)) for _, _, f in slot_values])
+        self._check(self.lib.sdqh_table_extrema_fold(self.handle, table.handle, C.c_int64(nrows), None if key is None else key.handle, C.c_int(n), sl, cols, f64,
+                                                     C.c_int(1 if count_hits else 0)))
+        self._after_call("table_extrema_fold")
+
+    def table_extrema_end(self, table):
+        """The extrema slots decoded back to doubles (a slot nothing reached: NaN).  Waits for the device."""
+        self._need_extrema("table_extrema_end")
+        self._check(self.lib.sdqh_table_extrema_end(self.handle, table.handle))
+        self._after_call("table_extrema_end")
+
+    def table_extrema(self, table, key, nrows, slot_ops, count_hits=False):
+        """begin + fold + end.  slot_ops: [(slot, op, values Column, is_f64)]."""
+        self.table_extrema_begin(table, [s for s, _, _, _ in slot_ops], [o for _, o, _, _ in slot_ops])
+        self.table_extrema_fold(table, key, nrows, [(s, c, f) for s, _, c, f in slot_ops], count_hits)
+        self.table_extrema_end(table)
+
+    def column_extrema(self, col, nrows, is_f64=None):
+        """(min, max, number of non-NaN values) of a column, as doubles; nothing to fold: (nan, nan, 0).  is_f64: an I64-typed column
+        holds the raw bits of doubles (default: the column's own dtype decides)."""
+        self._need_extrema("column_extrema")
+        lo, hi, n = C.c_double(), C.c_double(), C.c_int64()
+        f = (col.dtype == F64) if is_f64 is None else bool(is_f64)
+        self._check(self.lib.sdqh_column_extrema(self.handle, C.c_int64(nrows), col.handle, C.c_int(1 if f else 0), C.byref(lo), C.byref(hi), C.byref(n)))
+        self._after_call("column_extrema")
+        return lo.value, hi.value, n.value
+
+    def extrema_geometry(self):
+        """Rows one workgroup takes per step of the fold (what the tests size their cases from)."""
+        self._need_extrema("extrema_geometry")
+        a = C.c_int64()
+        self._check(self.lib.sdqh_extrema_geometry(self.handle, C.byref(a)))
+        return a.value
+
     def table_entries(self, table):
         """(Columns [key, payload...], n): the table's entries as resident columns."""
         k = 1 + table.npayload
@@ -1349,6 +1406,13 @@ class Library:
             L.sdqh_table_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
             L.sdqh_sort_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
+        if self.has_extrema:
+            L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+            L.sdqh_table_extrema_fold.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+            L.sdqh_table_extrema_end.argtypes = [C.c_void_p, C.c_void_p]
+            L.sdqh_column_extrema.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_extrema_geometry.argtypes = [C.c_void_p, C.c_void_p]
 
     def backend_name(self):
         return self.cdll.sdqh_backend_name().decode()

@@ -20,14 +20,16 @@ TBL_LIB = os.path.join(CSRC, "libsdqltbl.so")
 # instances), and the row-program path (code generation + hiprtc; seconds).  Objects are kept next to the
 # sources so a change to one does not recompile the other.
 HIP_UNITS = [("sdqh_hip.hip", "sdqh_hip.o"), ("sdqh_x.hip", "sdqh_x.o"), ("sdqh_codes.hip", "sdqh_codes.o"), ("sdqh_aux.hip", "sdqh_aux.o"),
-             ("sdqh_sort.hip", "sdqh_sort.o")]       # the ordering extension (include/sdqh_sort.h): its own kernels, seconds to compile
+             ("sdqh_sort.hip", "sdqh_sort.o"),       # the ordering extension (include/sdqh_sort.h): its own kernels, seconds to compile
+             ("sdqh_extrema.hip", "sdqh_extrema.o")]  # the extrema extension (include/sdqh_extrema.h): likewise
 HIP_SOURCES = [os.path.join(CSRC, src) for src, _ in HIP_UNITS]
 HIP_HEADERS = [os.path.join(INCLUDE, "sdqh.h"), os.path.join(CSRC, "sdqh_kernels.hpp"), os.path.join(CSRC, "sdqh_host.hpp"),
                os.path.join(CSRC, "sdqh_xkernels.hpp")]      # sdqh_x.hip packs XArgs / sink arguments from its structs
 # what each unit includes: the run-time skeletons (sdqh_xkernels.hpp) are compiled into sdqh_x.hip only — editing them must not
 # recompile the ahead-of-time unit (a quarter of an hour)
 SORT_HEADER = os.path.join(INCLUDE, "sdqh_sort.h")
-UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER]}
+EXTREMA_HEADER = os.path.join(INCLUDE, "sdqh_extrema.h")
+UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER], "sdqh_extrema.hip": HIP_HEADERS[:3] + [EXTREMA_HEADER]}
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-ffp-contract=off",          # keep the reference's a*(1.0-b) association: no FMA contraction
@@ -98,7 +100,7 @@ def hipcc_path():
 def build_hip(force=False, save_temps=False):
     """Compile the HIP kernels + C ABI for gfx950.  hipcc cross-compiles without a GPU."""
     objs = [os.path.join(CSRC, obj) for _, obj in HIP_UNITS]
-    if not (force or _stale(HIP_LIB, HIP_SOURCES + HIP_HEADERS + [SORT_HEADER]) or not all(os.path.exists(o) for o in objs)):
+    if not (force or _stale(HIP_LIB, HIP_SOURCES + HIP_HEADERS + [SORT_HEADER, EXTREMA_HEADER]) or not all(os.path.exists(o) for o in objs)):
         return HIP_LIB                                  # (a unit without its object: the library predates the unit)
     hipcc = hipcc_path()
     if hipcc is None:

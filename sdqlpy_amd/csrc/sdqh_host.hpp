@@ -230,6 +230,11 @@ struct sdqh_table {
     WordExc* wexc = nullptr;                       // row index (DevTable): exception records, one slot per segment
     uint32_t* coarse = nullptr; int coarse_words = 0, coarse_shift = 0;     // coarse key filter (see DevLookups), built on first need
     bool stage_only = false;                       // sdqh_xstage: every passing row staged (equal keys included), never indexed — the source of a redistribution step, nothing else
+    // extrema slots (sdqh_extrema.hip): between sdqh_table_extrema_begin and _end the named accumulator slots hold ENCODED values
+    bool ext_open = false;
+    int ext_nslots = 0;
+    int32_t ext_slot[SDQH_TUPLE_MAX_VALUES] = {0, 0, 0, 0}, ext_op[SDQH_TUPLE_MAX_VALUES] = {0, 0, 0, 0};
+    unsigned long long* ext_status = nullptr;      // device word (the table's own block): != 0 once an integer value beyond +-2^53 was folded
 };
 
 

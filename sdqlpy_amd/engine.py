@@ -20,7 +20,7 @@ import weakref
 import numpy as np
 
 from . import abi, build
-from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
+from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
 from .result import DeferredResultSet, Pending, DictResult, ResultSet, TextRefs, decode_text
 
@@ -145,6 +145,9 @@ class Engine:
         # dictionaries of sets (frontend.DistinctOp): {(source line, result name): {"route": "fast" | "generic", "runs", "why"}} — which of
         # _prepare_distinct's two routes each such loop took, and what sent it to the generic one
         self.distinct_loops = {}
+        # MIN / MAX loops (frontend.ExtremaOp): {(source line, result name): {"route": "columns" | "compacted", "runs"}} — did the fold read the
+        # table's own columns, or the rows compacted by the loop's conditions (one extra pass)
+        self.extrema_loops = {}
         self.distinct_fast = os.environ.get("SDQLPY_AMD_DISTINCT_FAST", "1") != "0"      # 0: every such loop takes the generic route (A/B measurements, tests)
         self.strict_device = os.environ.get("SDQLPY_AMD_STRICT_DEVICE", "0") == "1"
         # ORDER BY beyond sdqh_table_topk (more than 128 rows, more than 3 columns, no limit) on the device where the library has the
@@ -179,6 +182,8 @@ class Engine:
         return {"host_loops": [{"line": k[0], "result": k[1], "runs": v["runs"], "why": v["why"]} for k, v in sorted(self.host_loops.items(), key=lambda kv: str(kv[0]))],
                 "distinct_loops": [{"line": k[0], "result": k[1], "route": v["route"], "runs": v["runs"], "why": v["why"]}
                                    for k, v in sorted(self.distinct_loops.items(), key=lambda kv: str(kv[0]))],
+                "extrema_loops": [{"line": k[0], "result": k[1], "route": v["route"], "runs": v["runs"]}
+                                  for k, v in sorted(self.extrema_loops.items(), key=lambda kv: str(kv[0]))],
                 "plan_graphs": dict(self.graph_stats), "resident_bytes": int(self.resident_bytes), "lanes": int(self.nlanes)}
 
     def synchronize(self):
@@ -1793,17 +1798,39 @@ def _shape_result(op, d, top):
     return rs
 
 
+def _as_plain_op(op):
+    """What the plan analyses below see of an ExtremaOp: the loop it is — a table loop, or a sum over a result dictionary — whichever
+    of its values are extrema."""
+    if not isinstance(op, ExtremaOp):
+        return op
+    val = RecordCons([(nm or "value", e) for nm, _, e in op.fields])
+    if op.source_is_table:
+        scan = ScanOp(op.out, op.source, op.lineno)
+        scan.conds, scan.kind, scan.key, scan.val = list(op.conds), ("scalar" if op.key is None else "dict"), op.key, val
+        return scan
+    return HostDictOp(op.out, op.source, list(op.conds), op.key if op.key is not None else Const(0), val, False, op.lineno)
+
+
 def _looked_up(plan):
     """Names of the results that a table loop looks up (`d[key]`, joinProbe index)."""
     found = []
+    extrema_sources = set()
     for op in plan.ops:
+        if isinstance(op, ExtremaOp) and not op.source_is_table:
+            # an extrema loop over a result dictionary is a device loop over its entries: the dictionary, and what the loop looks up, must be tables
+            extrema_sources.add(op.source)
+            for e in list(op.conds) + [op.key] + [x for _, _, x in op.fields]:
+                if e is not None:
+                    _walk_lookups(e, found)
+            continue
+        op = _as_plain_op(op)
         if isinstance(op, ScanOp):
             if op.probe is not None:
                 _walk_lookups(op.probe, found)
             for e in list(op.conds) + [op.key, op.val] + [x for _, x, _ in (op.fields or [])] + [c for _, _, fc in (op.fields or []) for c in fc]:
                 if e is not None:
                     _walk_lookups(e, found)
-    return {lk.dict_name for lk in found}
+    return {lk.dict_name for lk in found} | extrema_sources
 
 
 def _compared_lookups(plan):
@@ -1839,7 +1866,7 @@ def _compared_lookups(plan):
         elif isinstance(e, (Lookup, PayloadField)):
             walk(e.key if isinstance(e, Lookup) else e.lookup.key)
 
-    for op in plan.ops:
+    for op in map(_as_plain_op, plan.ops):
         if isinstance(op, (ScanOp, HostDictOp)):                  # (a sum over a result dictionary compares looked-up text too: the reference's own q12)
             for e in list(op.conds) + [op.key, op.val]:
                 if e is not None:
@@ -2043,6 +2070,130 @@ def _prepare_distinct(eng, op, htab):
     return run
 
 
+# =================================================================================================
+# MIN / MAX (frontend.ExtremaOp: smin / smax), on a library that has the extrema extension (include/sdqh_extrema.h).  Per key: the loop
+# runs as the aggregation it would be with every extremum replaced by a constant — that leaves the table of its distinct keys, the
+# ordinary sums that share the loop and hits = passing rows per key — and the extrema are then folded into their accumulator slots
+# (abi.Context.table_extrema) from (key, value) rows that are either the scanned table's own columns (route "columns": no condition,
+# key and values plain columns: no extra pass) or the rows compacted by the loop's conditions (route "compacted": one extra pass,
+# xplan.prepare_extrema_rows).  A scalar is sdqh_column_extrema over the column, or over the compacted values.  A sum over a result
+# dictionary reads the views sdqh_table_columns gives of its entries (xplan.DictTable), always compacted.  No host fallback.
+# =================================================================================================
+def _prepare_extrema(eng, op, htab):
+    from . import xplan
+    root = getattr(eng, "_eng", eng)
+    lib = eng.ctx.library
+    if not getattr(lib, "has_extrema", False):
+        raise UnsupportedQuery("line %d: smin / smax need the library's extrema extension (include/sdqh_extrema.h), which %s does not have"
+                               % (op.lineno, lib.path))
+    ctx = eng.ctx
+    ext = [(i, nm, how, e) for i, (nm, how, e) in enumerate(op.fields) if how]
+    dtab = None if op.source_is_table else xplan.DictTable(eng, op)
+    src = htab if op.source_is_table else dtab
+    rows = xplan.prepare_extrema_rows(eng, op, src, [e for _, _, _, e in ext])
+
+    def plain_col(e, kinds):
+        arr = htab.cols.get(e.name) if isinstance(e, Col) else None
+        return arr is not None and arr.dtype in kinds
+    plain = op.source_is_table and not op.conds and (op.key is None or plain_col(op.key, (np.int64,))) \
+        and all(plain_col(e, (np.int64, np.float64)) for _, _, _, e in ext)
+    run_base = None
+    if op.key is not None:
+        base = ScanOp(op.out, op.source, op.lineno)
+        vals = [(nm, Const(0.0) if how else e) for nm, how, e in op.fields]
+        base.kind, base.conds, base.key, base.val = "dict", list(op.conds), op.key, (RecordCons(vals) if op.val_is_record else vals[0][1])
+        run_base = xplan.prepare_scan(eng, base, src, {}, False, as_table=True)
+
+    def note(route):
+        rec = root.extrema_loops.setdefault((op.lineno, op.out), {"route": route, "runs": 0})
+        rec["route"] = route
+        rec["runs"] += 1
+
+    def fold_rows(env):
+        """(key Column | None, value Columns, value is a double, rows, columns to free, route)"""
+        if plain:
+            vcols = [eng.column(htab.array(e.name, op)) for _, _, _, e in ext]
+            return (eng.column(htab.array(op.key.name, op)) if op.key is not None else None), vcols, [c.dtype == abi.F64 for c in vcols], htab.nrows, [], "columns"
+        cols, f64, n = rows(env)
+        return cols[0], cols[1:], f64, n, cols, "compacted"
+
+    def refused(exc):
+        if exc.code != abi.ERR_UNSUPPORTED:
+            raise exc
+        raise UnsupportedQuery("line %d: smin / smax of '%s': %s" % (op.lineno, op.out, exc))
+
+    def empty_groups(env):
+        """A source dictionary without entries: a table whose one entry no row reached — every key reads as absent."""
+        table = ctx.hash_build_unique(1, abi.make_filter(), [], eng.iota_column(0, 1), [], accumulate=True)
+        bt = BuiltTable(table, "key", isinstance(op.key, RecordCons), [], op.val_is_record, [])
+        bt.agg = ([("key", "key")], [nm for nm, _, _ in op.fields], None, isinstance(op.key, RecordCons), op.val_is_record, len(op.fields))
+        env[op.out + "$groups"] = bt
+        return ("aggregated", op.out + "$groups")
+
+    def run_keyed(env):
+        if dtab is not None and dtab.nrows == 0:
+            return empty_groups(env)
+        out = run_base(env)
+        bt = env[out[1]]
+        _, _, count_idx, _, _, _ = bt.agg
+        key, vcols, f64, n, owned, route = fold_rows(env)
+        try:
+            slots = [(i - (1 if count_idx is not None and count_idx < i else 0), abi.EXT_MIN if how == "min" else abi.EXT_MAX, col, f)
+                     for (i, _, how, _), col, f in zip(ext, vcols, f64)]
+            ctx.table_extrema(bt.table, key, n, slots, count_hits=False)
+        except abi.SdqhError as exc:
+            refused(exc)
+        finally:
+            for c in owned:
+                c.free()
+        bt.int_values = frozenset(set(bt.int_values) | {nm for (_, nm, _, _), f in zip(ext, f64) if not f})
+        note(route)
+        return out
+
+    def run_scalar(env):
+        _, vcols, f64, n, owned, route = fold_rows(env)
+        try:
+            lo, hi, cnt = ctx.column_extrema(vcols[0], n, is_f64=f64[0])
+        except abi.SdqhError as exc:
+            refused(exc)
+        finally:
+            for c in owned:
+                c.free()
+        note(route)
+        v = lo if ext[0][2] == "min" else hi
+        return int(v) if cnt and not f64[0] else v
+
+    body = run_scalar if op.key is None else run_keyed
+    if op.source_is_table:
+        return body
+
+    def run_over_dict(env):
+        made, inner = None, env
+        if isinstance(env.get(op.source), DictResult):
+            # a handful of groups the small group-by kernels delivered to the host: made resident again, as for every device loop over a result dictionary
+            made = _resident_groups(eng, env[op.source], op)
+            if made is None:
+                raise UnsupportedQuery("line %d: smin / smax over '%s': its groups are on the host in a shape no device loop reads" % (op.lineno, op.source))
+            inner = dict(env)
+            inner[op.source + "$resident"] = made
+            inner[op.source] = ("aggregated", op.source + "$resident")
+        try:
+            dtab.load(inner)
+            try:
+                out = body(inner)
+            finally:
+                dtab.release()
+            if inner is not env:
+                for k, v in inner.items():
+                    if k not in env and k != op.source + "$resident":
+                        env[k] = v
+            return out
+        finally:
+            if made is not None:
+                made.table.free()
+    return run_over_dict
+
+
 def _membership_only(plan):
     """Names of unique builds that are only used as `tbl[key] != None` / joinProbe index with no
     payload access, and are not the plan's result."""
@@ -2077,7 +2228,7 @@ def _membership_only(plan):
             for _, x in e.fields:
                 walk(x)
 
-    for op in plan.ops:
+    for op in map(_as_plain_op, plan.ops):
         if isinstance(op, ScanOp):
             for c in op.conds:
                 walk(c, as_cond=True)
@@ -2207,6 +2358,8 @@ class PreparedPlan:
                                                          coded_text=op.out in compared)))
             elif isinstance(op, DistinctOp):
                 self.steps.append((op.out, _prepare_distinct(eng, op, tables[op.table])))
+            elif isinstance(op, ExtremaOp):
+                self.steps.append((op.out, _prepare_extrema(eng, op, tables[op.source] if op.source_is_table else None)))
             elif isinstance(op, SelectKeysOp):
                 self.steps.append((op.out, (lambda env, op=op: _select_keys(eng, op, env))))
             elif isinstance(op, ScalarExprOp):
@@ -2224,6 +2377,8 @@ class PreparedPlan:
         """The steps whose device call may be launched without being waited for: the plan's LAST table loop when it is an aggregation
         that only the final reshaping sum reads, and that sum itself (its K-F) — nothing else of the plan runs after them."""
         ops = plan.ops
+        if any(isinstance(op, ExtremaOp) for op in ops):
+            return frozenset()                                   # sdqh_table_extrema_end / sdqh_column_extrema wait for the device: such a plan is issued call by call, never recorded
         if len(ops) >= 2 and isinstance(ops[-1], FinalizeOp) and ops[-1].out == plan.result and ops[-1].source == ops[-2].out \
                 and isinstance(ops[-2], ScanOp) and ops[-2].kind == "dict" and not ops[-2].unique:
             return frozenset([ops[-2].out, ops[-1].out])

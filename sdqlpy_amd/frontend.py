@@ -244,6 +244,33 @@ class DistinctOp:
         return "DistinctOp(%s <- %s: if %r: {%r: vector({%r})})" % (self.out, self.table, self.conds, self.key, self.value)
 
 
+EXTREMA = {"smin": "min", "smax": "max"}
+EXTREMA_WHERE = ("smin / smax are only supported as the whole value of a sum's dictionary, {key: smin(v)}, as a field of its record value, "
+                 "{key: record({\"lo\": smin(v), ...})}, or as the whole body of a scalar sum, T.sum(lambda p: smax(v) [if c else None]) "
+                 "- over a database table or a result dictionary, never in a condition, a key, arithmetic, another smin / smax, or a unique / join build")
+
+
+class ExtremaOp:
+    """`S.sum(lambda p: {K: smin(V)} ...)`, `{K: record({"lo": smin(V1), "hi": smax(V2), "total": W})}` or the scalar `smax(V)`, each
+    possibly `if C else None`, over a database table (source_is_table) or a result dictionary: MIN / MAX aggregation, an extension
+    of the language (the reference has sums only).  fields: [(name | None, "min" | "max" | None, Expr)] - None: an ordinary sum that
+    shares the loop; key None: a scalar, read by later loops as any scalar sum (ScalarField).  NaN values are skipped; a key whose
+    values were all NaN, or a scalar over no row, is NaN."""
+    def __init__(self, out, source, source_is_table, key, fields, val_is_record, conds, lineno):
+        self.out, self.source, self.source_is_table, self.key, self.fields = out, source, source_is_table, key, fields
+        self.val_is_record, self.conds, self.lineno = val_is_record, conds, lineno
+        self.table = source if source_is_table else None         # (Plan.fingerprint numbers the table parameters by this)
+
+    def __repr__(self):
+        def f(nm, how, e):
+            body = "%s(%r)" % ("s" + how, e) if how else repr(e)
+            return body if nm is None else "%s=%s" % (nm, body)
+        val = ", ".join(f(*x) for x in self.fields)
+        if self.val_is_record:
+            val = "record(%s)" % val
+        return "ExtremaOp(%s <- %s: if %r: %s)" % (self.out, self.source, self.conds, val if self.key is None else "{%r: %s}" % (self.key, val))
+
+
 class ScalarField(Expr):
     """`name.field` of an earlier scalar-record sum (or `name` itself for a plain scalar sum)."""
     def __init__(self, name, field):
@@ -774,6 +801,8 @@ class _Lowerer:
                     if isinstance(arg, ast.Subscript) and isinstance(arg.value, ast.Name) and arg.value.id in self.vectors:
                         return DistinctCount(Lookup(arg.value.id, self.expr(self._slice(arg), env)))
                     self.fail(node, "dictSize is only supported as dictSize(tbl[key]) with tbl a dictionary of sets, T.sum(lambda p: {k: vector({v})})")
+                if fn.id in EXTREMA:
+                    self.fail(node, EXTREMA_WHERE)
                 if fn.id == "vector":
                     self.fail(node, "vector({...}) is only supported as the whole value of a table sum's dictionary, {key: vector({value})}")
             if isinstance(fn, ast.Attribute) and fn.attr == "concat" and len(node.args) == 1:
@@ -851,6 +880,46 @@ class _Lowerer:
             return
         op.val = self.expr(v, env)
 
+    # -- MIN / MAX ---------------------------------------------------------------------------
+    @staticmethod
+    def _extremum(node):
+        """smin(V) / smax(V) -> ("min" | "max", V node), else None"""
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Name) and node.func.id in EXTREMA and len(node.args) == 1 and not node.keywords:
+            return EXTREMA[node.func.id], node.args[0]
+        return None
+
+    def extrema_op(self, out, source, is_table, body, conds, env, ln):
+        """The ExtremaOp of a sum's body (conditions already split off) when smin / smax stands in one of its positions, else None
+        (an smin / smax anywhere else is refused where the expression is lowered: expr)."""
+        key, val_is_record = None, False
+        if isinstance(body, ast.Dict) and len(body.keys) == 1:
+            v = body.values[0]
+            rec = _record_fields(v)
+            if self._extremum(v) is not None:
+                pairs = [(None, v)]
+            elif rec is not None and any(self._extremum(x) is not None for _, x in rec):
+                pairs, val_is_record = rec, True
+            else:
+                return None
+            key = self.expr(body.keys[0], env)
+            while isinstance(key, Call) and key.fn in ("unique", "dense"):
+                if key.fn == "unique":
+                    self.fail(body, "smin / smax under a unique() key: a first-row-wins build aggregates nothing")
+                key = key.args[1]
+        elif self._extremum(body) is not None:
+            pairs = [(None, body)]
+        else:
+            return None
+        fields = []
+        for nm, x in pairs:
+            how = self._extremum(x)
+            fields.append((nm, how[0], self.expr(how[1], env)) if how is not None else (nm, None, self.expr(x, env)))
+        if len(fields) > 4:                                          # SDQH_TUPLE_MAX_VALUES
+            self.fail(body, "more than 4 values (extrema and sums together) in one loop")
+        if key is None:
+            self.scalars.add(out)
+        return ExtremaOp(out, source, is_table, key, fields, val_is_record, conds, ln)
+
     # -- statements -------------------------------------------------------------------------
     def lambda_of(self, node, nparams):
         if not (isinstance(node, ast.Lambda) and len(node.args.args) == nparams):
@@ -870,6 +939,11 @@ class _Lowerer:
                 env = {p: ("rowpair",)}
                 body, conds = self.split_ifelse(body, env)
                 op.conds = conds
+                ext = self.extrema_op(out, table, True, body, conds, env, ln)
+                if ext is not None:
+                    if len(call.args) == 2 and isinstance(call.args[1], ast.Constant) and call.args[1].value is False:
+                        self.fail(call, "smin / smax in an assignment sum (is_update False): a first-row-wins build aggregates nothing")
+                    return ext
                 if isinstance(body, ast.Dict):
                     self.dict_body(op, body, env, vectors_ok=True)
                     if isinstance(op.val, tuple):                     # {K: vector({V})}: per key the set of its values
@@ -947,6 +1021,9 @@ class _Lowerer:
             env = {p: ("kv",)}
             tmp = ScanOp(out, table, ln)
             body, kv_conds = self.split_ifelse(body, env)
+            ext = self.extrema_op(out, table, False, body, kv_conds, env, ln)
+            if ext is not None:
+                return ext
             if not isinstance(body, ast.Dict):
                 self.fail(call, "a sum over a result dictionary must build a dictionary {key: value}")
             self.dict_body(tmp, body, env)

@@ -29,7 +29,7 @@ import numpy as np
 
 __all__ = [
     "string", "date", "read_csv", "write_columns", "read_columns", "shard_rows", "sr_dict", "record", "vector",
-    "extractYear", "firstIndex", "startsWith", "endsWith", "dictSize", "substr", "unique", "dense",
+    "extractYear", "firstIndex", "startsWith", "endsWith", "dictSize", "substr", "unique", "dense", "smin", "smax",
     "sdqlpy_init", "sdql_compile", "benchmark", "invalidate",
 ]
 
@@ -213,6 +213,18 @@ def unique(arg):
 
 def dense(arg1, arg2):
     return arg2
+
+
+def smin(value):
+    """MIN aggregate: as the value of a sum's dictionary (`{k: smin(v)}`, a field of its record value) or as the whole body of a
+    scalar sum, the MINIMUM of `value` over the loop's rows instead of their total.  An extension of the language (the reference has
+    no min / max): it only has a meaning to the @sdql_compile front end, which reads it from the source."""
+    raise TypeError("smin() only has a meaning inside an @sdql_compile function")
+
+
+def smax(value):
+    """MAX aggregate; see smin."""
+    raise TypeError("smax() only has a meaning inside an @sdql_compile function")
 
 
 # ------------------------------------------------------------------------------------------------

@@ -176,6 +176,11 @@ QUERY_COLUMNS = {
             "partsupp": ["ps_partkey", "ps_suppkey"]},
     "q15": {"lineitem": ["l_suppkey", "l_shipdate", "l_extendedprice", "l_discount"], "supplier": ["s_suppkey", "s_name", "s_address", "s_phone"]},
     "q17": {"lineitem": ["l_partkey", "l_quantity", "l_extendedprice"], "part": ["p_partkey", "p_brand", "p_container"]},
+    "q2_min": {"part": ["p_partkey", "p_size", "p_type", "p_mfgr"],
+               "supplier": ["s_suppkey", "s_nationkey", "s_acctbal", "s_name", "s_address", "s_phone", "s_comment"],
+               "partsupp": ["ps_partkey", "ps_suppkey", "ps_supplycost"], "nation": ["n_nationkey", "n_regionkey", "n_name"],
+               "region": ["r_regionkey", "r_name"]},
+    "q15_max": {"lineitem": ["l_suppkey", "l_shipdate", "l_extendedprice", "l_discount"], "supplier": ["s_suppkey", "s_name", "s_address", "s_phone"]},
     "q19": {"lineitem": ["l_partkey", "l_quantity", "l_extendedprice", "l_discount", "l_shipinstruct", "l_shipmode"],
             "part": ["p_partkey", "p_brand", "p_size", "p_container"]},
     "q20": {"supplier": ["s_suppkey", "s_name", "s_address", "s_nationkey"], "nation": ["n_nationkey", "n_name"],

@@ -996,6 +996,53 @@ def _is_key_set(bt):
     return bt.table.npayload == 0 and not bt.table.accumulate
 
 
+def prepare_extrema_rows(eng, op, htab, values):
+    """closure(env) -> ([key Column, value Columns...], [value is a double], n) for an extrema loop (frontend.ExtremaOp): the rows that
+    pass the loop's conditions as resident columns — their key and the extremum values, duplicate keys kept (sdqh_xcompact; 8-byte
+    bit patterns, so a double value is read by its flag).  The key is computed exactly as the large aggregation of prepare_scan
+    computes its build key (one part as it is, two packed, more as one mixed-radix integer): what engine._prepare_extrema folds these
+    rows into is the table that aggregation made.  A scalar loop (op.key None) is keyed by the row number."""
+    ctx = eng.ctx
+    state = {}
+    key_fields = [] if op.key is None else (op.key.fields if isinstance(op.key, RecordCons) else [(None, op.key)])
+
+    def compile_rows(env):
+        c = Compiler(eng, op, htab, env)
+        conds = [x for x in op.conds if _is_light(x)] + [x for x in op.conds if not _is_light(x)]
+        gates = [c.cond(x).id for x in conds]
+        if len(gates) > abi.MAX_XGATES:
+            gates = gates[:abi.MAX_XGATES - 1] + [c.fold(abi.X_AND, gates[abi.MAX_XGATES - 1:])]
+        if key_fields:
+            parts = c.key_parts(key_fields)
+            flat = [v for _, vs, _ in parts for v in vs]
+            if len(flat) > 2:
+                kid, _ = c.pack_radix(parts)
+            elif len(flat) == 1:
+                kid = flat[0].id
+            else:
+                kid = c.P.op(abi.X_PACK2, abi.T_I64, a=flat[0].id, b=flat[1].id)
+        else:
+            kid = c.P.op(abi.X_ROWID, abi.T_I64)
+        vals, f64 = [], []
+        for e in values:
+            v = c.value(e)
+            if not isinstance(v, XV) or v.t not in "if" or v.dec is not None:
+                raise UnsupportedQuery("line %d: smin / smax need an integer or floating-point value: %r" % (op.lineno, e))
+            vals.append(v.id); f64.append(v.t == "f")
+        c.P.gates, c.P.key, c.P.vals = gates, kid, vals
+        return c, f64
+
+    def run_rows(env):
+        st = state.get("c")
+        if st is None or not st[0].still_valid(env):
+            st = state["c"] = compile_rows(env)
+        c, f64 = st
+        c.bind(env)
+        cols, n = ctx.xcompact(htab.nrows, c.P)
+        return cols, f64, n
+    return run_rows
+
+
 # =================================================================================================
 # Sums over RESULT dictionaries (frontend.HostDictOp) on the device.  The reference compiles such a loop like any
 # other (lib/sdql_ir_cpp_generator_par.py:520-568: iteration over a dictionary that is not a database table); here the
