@@ -23,6 +23,10 @@ MAX_TOPK, MAX_SORT_KEYS = 128, 3
 # (Library.has_sort is False there) and results are ordered on the host
 SORT_EXPORTS = ["sdqh_table_sorted", "sdqh_sort_geometry"]
 SORT_MAX_KEYS, SORT_ALL = 8, 1 << 62
+# ... and its second half (include/sdqh_sort_terms.h), bound when present in the same way (Library.has_sort_terms): ORDER BY over derived
+# columns — the halves of a packed key, the digits of a mixed-radix key, text behind row references or codes — and the ranking of a text column
+SORT_TERMS_EXPORTS = ["sdqh_text_ranks", "sdqh_table_sorted_by"]
+TEXT_RANK_MAX_WIDTH = 128
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -79,6 +83,12 @@ class Probe(C.Structure):
 
 class SortKey(C.Structure):
     _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("descending", C.c_int32), ("is_f64", C.c_int32)]
+
+
+class SortTerm(C.Structure):
+    """sdqh_sort_term: a sort column and the derivation of what is ordered — field = (uint64(source) / div) % mod + add, then ranks[field]."""
+    _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("descending", C.c_int32), ("is_f64", C.c_int32),
+                ("div", C.c_int64), ("mod", C.c_int64), ("add", C.c_int64), ("ranks", C.c_void_p)]
 
 
 SRC_COLUMN, SRC_LOOKUP, SRC_LOOKUP_YEAR = 0, 1, 2
@@ -1122,6 +1132,28 @@ class Context:
         n = n.value
         return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
 
+    def _sorted_call(self, name, table, min_hits, limit, ncols, arr, capacity_hint, want_hits):
+        """What sdqh_table_sorted and sdqh_table_sorted_by share: arrays sized from capacity_hint, one retry with the exact size after
+        SDQH_ERR_OVERFLOW, the rows sliced to what was written.  arr: the marshalled sort columns / terms."""
+        fn = getattr(self.lib, "sdqh_" + name)
+        cap = max(1, min(int(capacity_hint), int(limit)))
+        for attempt in (0, 1):
+            keys = np.empty(cap, np.int64)
+            payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
+            values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
+            hits = np.empty(cap, np.int64) if want_hits else None
+            n = C.c_int64()
+            rc = fn(self.handle, table.handle, C.c_int64(min_hits), C.c_int64(limit), C.c_int(ncols), arr, C.c_int64(cap),
+                    _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), C.byref(n))
+            if rc == ERR_OVERFLOW and attempt == 0:
+                cap = max(1, n.value)
+                continue
+            self._check(rc)
+            break
+        self._after_call(name)
+        n = n.value
+        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
+
     def table_sorted(self, table, min_hits, limit, sort, capacity_hint, want_hits=True):
         """ORDER BY over the entries with at least min_hits rows, the first min(limit, n) of them (limit = SORT_ALL: all): sort as
         table_topk takes it, up to SORT_MAX_KEYS columns, any number of rows.  The arrays are sized from capacity_hint; a result
@@ -1131,23 +1163,31 @@ class Context:
         arr = (SortKey * len(sort))()
         for i, (kind, index, desc, is_f64) in enumerate(sort):
             arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
-        cap = max(1, min(int(capacity_hint), int(limit)))
-        for attempt in (0, 1):
-            keys = np.empty(cap, np.int64)
-            payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
-            values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
-            hits = np.empty(cap, np.int64) if want_hits else None
-            n = C.c_int64()
-            rc = self.lib.sdqh_table_sorted(self.handle, table.handle, C.c_int64(min_hits), C.c_int64(limit), C.c_int(len(sort)), arr, C.c_int64(cap),
-                                            _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), C.byref(n))
-            if rc == ERR_OVERFLOW and attempt == 0:
-                cap = max(1, n.value)
-                continue
-            self._check(rc)
-            break
-        self._after_call("table_sorted")
-        n = n.value
-        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
+        return self._sorted_call("table_sorted", table, min_hits, limit, len(sort), arr, capacity_hint, want_hits)
+
+    def text_ranks(self, column, nrows):
+        """(resident I64 Column of nrows dense ranks, number of distinct texts) of a STR column, in numpy's order of '<U' arrays: rank[r] <
+        rank[s] iff text r sorts before text s, equal ranks iff equal text.  Waits for the device."""
+        if not self.library.has_sort_terms:
+            raise SdqhError(ERR_UNSUPPORTED, "text_ranks: %s has no sort-terms extension" % self.library.path)
+        h, distinct = C.c_void_p(), C.c_int64()
+        self._check(self.lib.sdqh_text_ranks(self.handle, column.handle, C.c_int64(nrows), C.byref(h), C.byref(distinct)))
+        self._after_call("text_ranks")
+        return Column(self, h, nrows, I64, 0), distinct.value
+
+    def table_sorted_by(self, table, min_hits, limit, terms, capacity_hint, want_hits=True):
+        """table_sorted over sort TERMS: [(kind, index, descending, is_f64, div, mod, add, ranks)] — the column table_sorted takes, then
+        field = (uint64(source) / div) % mod + add (div <= 1: no division, mod == 0: no modulo) and, with ranks an I64 Column, the value
+        ordered is ranks[field].  A 4-tuple is an underived term.  Returns (keys, payload, values, hits), in order."""
+        if not self.library.has_sort_terms:
+            raise SdqhError(ERR_UNSUPPORTED, "table_sorted_by: %s has no sort-terms extension" % self.library.path)
+        arr = (SortTerm * len(terms))()
+        for i, term in enumerate(terms):
+            kind, index, desc, is_f64 = term[:4]
+            div, mod, add, ranks = term[4:] if len(term) > 4 else (0, 0, 0, None)
+            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
+            arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = int(div), int(mod), int(add), None if ranks is None else ranks.handle
+        return self._sorted_call("table_sorted_by", table, min_hits, limit, len(terms), arr, capacity_hint, want_hits)
 
     def sort_geometry(self):
         """(largest n of the single-workgroup path, rows per tile of the radix path, smallest n with a second scan level or 0)."""
@@ -1406,6 +1446,11 @@ class Library:
             L.sdqh_table_sorted.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
             L.sdqh_sort_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_sort_terms = self.has_sort and all(hasattr(L, s) for s in SORT_TERMS_EXPORTS)      # ... and its terms (include/sdqh_sort_terms.h)
+        if self.has_sort_terms:
+            L.sdqh_text_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+            L.sdqh_table_sorted_by.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -22,6 +22,11 @@
 //                     One form for every n a stage can hold (references are 32 bits): no second scan level.
 //   k_sort_emit       the first min(limit, n) rows in order, columns as sdqh_table_compact lays them out
 //
+// include/sdqh_sort_terms.h on top of it: sdqh_table_sorted_by orders by DERIVED columns — k_sort_term_keys is k_sort_keys with
+// field = (uint64(source) / div) % mod + add and a bounds-checked gather through a ranks column in front of sort_bits; everything behind
+// the key kernel is shared — and sdqh_text_ranks makes such a ranks column of a text column (k_text_masks / k_text_pack, the passes
+// above, k_rank_count / k_rank_place: see there).
+//
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
 // Nothing here has a counterpart in the reference, whose results are unordered sets.
@@ -33,7 +38,7 @@
 
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
-#include "sdqh_sort.h"
+#include "sdqh_sort_terms.h"
 
 using namespace sdqh_host;
 
@@ -50,9 +55,15 @@ namespace {
 constexpr int SORT_SMALL = 1024;                     // largest n the single-workgroup kernel takes
 constexpr int SORT_SMALL_WAVE = SORT_SMALL / (TPB / WAVE);
 constexpr int SORT_TILE = 512;                       // positions a wave counts / places per pass (a result of 100 K rows still spreads over 200 waves)
-constexpr int SORT_INFO = 1 + 2 * SDQH_SORT_MAX_KEYS;      // [n | AND of the keys per column | OR of the keys per column]
+constexpr int SORT_INFO = 2 + 2 * SDQH_SORT_MAX_KEYS;      // [n | AND of the keys per column | OR of the keys per column | terms whose field fell outside its ranks column, a bit each]
+constexpr int SORT_INFO_BAD = 1 + 2 * SDQH_SORT_MAX_KEYS;
+constexpr int TEXT_WORD_BYTES = 8;                   // varying bytes of a text row packed into one 64-bit sort key
 
-struct DevSortSpec { DevSortKey key[SDQH_SORT_MAX_KEYS]; int32_t nsort, _pad; };
+// a sort column with its derivation (include/sdqh_sort_terms.h); nranks = rows of `ranks`
+struct DevSortTerm { DevSortKey sk; uint64_t div, mod; int64_t add; const int64_t* ranks; int64_t nranks; };
+inline bool term_derived(const DevSortTerm& t) { return t.div > 1 || t.mod != 0 || t.add != 0 || t.ranks != nullptr; }
+// the bytes of a text row that make up one 64-bit key, most significant first: byte (24 - 8 * part) of code unit `unit`
+struct DevTextWord { uint16_t unit[TEXT_WORD_BYTES]; uint8_t shift[TEXT_WORD_BYTES]; int32_t nbytes, _pad; };
 struct DevSortOut { int64_t* keys; int64_t* pay[SDQH_MAX_PAYLOAD]; double* val[SDQH_TUPLE_MAX_VALUES]; int64_t* hits; int32_t npay, nval; };
 
 // the selection predicate of k_compact_count / k_topk_scan
@@ -94,7 +105,7 @@ __global__ __launch_bounds__(TPB) void k_sort_count(DevTable t, DevStage st, uin
     }
     if (lane_id() == 0) seg_kept[seg] = n;
 }
-// 2. one workgroup: exclusive scan of the per-segment counts, in place; info = [n | ~0 x 8 | 0 x 8]
+// 2. one workgroup: exclusive scan of the per-segment counts, in place; info = [n | ~0 x 8 | 0 x 8 | 0]
 __global__ __launch_bounds__(TPB) void k_sort_scan(uint32_t* __restrict__ seg_kept, int nseg, unsigned long long* __restrict__ info) {
     __shared__ uint32_t s_part[TPB];
     const int per = (nseg + TPB - 1) / TPB;
@@ -104,6 +115,7 @@ __global__ __launch_bounds__(TPB) void k_sort_scan(uint32_t* __restrict__ seg_ke
     const uint32_t incl = block_scan_incl(sum, s_part);
     if (threadIdx.x == TPB - 1) info[0] = incl;
     if (threadIdx.x < SDQH_SORT_MAX_KEYS) { info[1 + threadIdx.x] = ~0ull; info[1 + SDQH_SORT_MAX_KEYS + threadIdx.x] = 0ull; }
+    if (threadIdx.x == SDQH_SORT_MAX_KEYS) info[SORT_INFO_BAD] = 0ull;
     uint32_t run = incl - sum;
     for (int b = b0; b < b1; ++b) { const uint32_t v = seg_kept[b]; seg_kept[b] = run; run += v; }
 }
@@ -139,6 +151,35 @@ __global__ __launch_bounds__(TPB) void k_sort_keys(DevStage st, DevSortKey sk, c
 #pragma unroll
     for (int off = 1; off < WAVE; off <<= 1) { all &= (uint64_t)__shfl_xor((long long)all, off, WAVE); any |= (uint64_t)__shfl_xor((long long)any, off, WAVE); }
     if (lane_id() == 0 && (all != ~0ull || any != 0ull)) { atomicAnd(&info[1 + col], (unsigned long long)all); atomicOr(&info[1 + SDQH_SORT_MAX_KEYS + col], (unsigned long long)any); }
+}
+
+// 4b. the same for a derived term: field = (uint64(source) / div) % mod + add, then — if the term has a ranks column — ranks[field],
+// read only after field was found inside [0, nranks): an entry whose field lies outside raises the term's bit in info[SORT_INFO_BAD]
+// (the host reads the block anyway and fails the call) and takes key 0.
+__global__ __launch_bounds__(TPB) void k_sort_term_keys(DevStage st, DevSortTerm tm, const uint32_t* __restrict__ refs, uint64_t* __restrict__ key, unsigned long long* __restrict__ info, int col) {
+    const uint64_t n = info[0];
+    uint64_t all = ~0ull, any = 0ull;
+    bool bad = false;
+    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
+        const int64_t idx = (int64_t)refs[i];
+        int64_t raw;
+        if (tm.sk.kind == SDQH_SORT_KEY) raw = st.key[idx];
+        else if (tm.sk.kind == SDQH_SORT_PAYLOAD) { const int64_t* p = tm.sk.index == 0 ? st.pay[0] : (tm.sk.index == 1 ? st.pay[1] : (tm.sk.index == 2 ? st.pay[2] : st.pay[3])); raw = p[idx]; }
+        else raw = (int64_t)(st.shits ? st.shits[idx] : 0u);
+        uint64_t f = (uint64_t)raw;
+        if (tm.div > 1) f /= tm.div;
+        if (tm.mod) f %= tm.mod;
+        int64_t v = (int64_t)(f + (uint64_t)tm.add);
+        uint64_t k = 0ull;
+        if (tm.ranks) {
+            if (v >= 0 && v < tm.nranks) k = sort_bits(tm.ranks[v], 0, tm.sk.desc); else bad = true;
+        } else k = sort_bits(v, 0, tm.sk.desc);
+        key[i] = k; all &= k; any |= k;
+    }
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) { all &= (uint64_t)__shfl_xor((long long)all, off, WAVE); any |= (uint64_t)__shfl_xor((long long)any, off, WAVE); }
+    if (lane_id() == 0 && (all != ~0ull || any != 0ull)) { atomicAnd(&info[1 + col], (unsigned long long)all); atomicOr(&info[1 + SDQH_SORT_MAX_KEYS + col], (unsigned long long)any); }
+    if (__ballot(bad) && lane_id() == 0) atomicOr(&info[SORT_INFO_BAD], 1ull << col);
 }
 
 // One wave's 64 positions of a pass placed: lane's place = cursor of its digit + lanes below it with the same digit; the lowest lane
@@ -264,6 +305,83 @@ __global__ __launch_bounds__(TPB) void k_sort_emit(DevStage st, const uint32_t* 
     }
 }
 
+// ---- text ranking (sdqh_text_ranks) ----------------------------------------------------------------------------------------------
+// A text column is nrows x width 32-bit code units.  (a) k_text_masks: per position the AND and the OR of the unit over all rows —
+// OR & ~AND = the bits that differ between any two rows; the host reads the block and lists the BYTES that vary at all, most
+// significant first ("Supplier#000012345": the low byte of six to nine positions out of 25).  (b) k_text_pack: up to eight of those
+// bytes of every row as one uint64.  (c) the stable LSD passes above (k_sort_hist / _bins / _scatter) over that word, last word
+// first, one key buffer reused; every packed byte varies, so every pass is needed and none is looked for.  (d) dense ranks in the
+// count -> scan -> place shape: a sorted row that differs from its predecessor (compared on the text itself) opens a new rank;
+// k_rank_count counts those per tile, k_sort_scan scans the tiles, k_rank_place writes ranks[perm[i]].  One form for every n.
+constexpr int TEXT_MAX_WIDTH = SDQH_TEXT_RANK_MAX_WIDTH;
+static_assert(TEXT_MAX_WIDTH <= TPB, "a workgroup holds at least one row of code units");
+
+__global__ __launch_bounds__(TPB) void k_text_masks(const uint32_t* __restrict__ text, uint64_t nrows, int width, uint32_t* __restrict__ masks) {
+    __shared__ uint32_t s_and[TEXT_MAX_WIDTH], s_or[TEXT_MAX_WIDTH];
+    if (threadIdx.x < TEXT_MAX_WIDTH) { s_and[threadIdx.x] = ~0u; s_or[threadIdx.x] = 0u; }
+    __syncthreads();
+    const int rows_per = TPB / width;                                 // whole rows a workgroup reads per step: consecutive threads, consecutive units
+    const int p = (int)threadIdx.x % width, sub = (int)threadIdx.x / width;
+    if (sub < rows_per) {
+        uint32_t all = ~0u, any = 0u;
+        for (uint64_t r = (uint64_t)blockIdx.x * rows_per + sub; r < nrows; r += (uint64_t)gridDim.x * rows_per) { const uint32_t u = text[r * (uint64_t)width + p]; all &= u; any |= u; }
+        atomicAnd(&s_and[p], all); atomicOr(&s_or[p], any);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < width) { atomicAnd(&masks[threadIdx.x], s_and[threadIdx.x]); atomicOr(&masks[TEXT_MAX_WIDTH + threadIdx.x], s_or[threadIdx.x]); }
+}
+__global__ __launch_bounds__(TPB) void k_text_pack(const uint32_t* __restrict__ text, uint64_t nrows, int width, DevTextWord w, uint64_t* __restrict__ key) {
+    for (uint64_t r = (uint64_t)blockIdx.x * TPB + threadIdx.x; r < nrows; r += (uint64_t)gridDim.x * TPB) {
+        const uint32_t* __restrict__ row = text + r * (uint64_t)width;
+        uint64_t k = 0ull;
+#pragma unroll
+        for (int b = 0; b < TEXT_WORD_BYTES; ++b) if (b < w.nbytes && (int)w.unit[b] < width) k |= (uint64_t)((row[w.unit[b]] >> w.shift[b]) & 255u) << (56 - 8 * b);
+        key[r] = k;
+    }
+}
+// does the row at sorted position r (>= 1) differ from the one before it?
+__device__ __forceinline__ bool text_head(const uint32_t* __restrict__ text, int width, const uint32_t* __restrict__ perm, uint64_t r, uint32_t n, uint32_t& g) {
+    g = perm ? perm[r] : (uint32_t)r;
+    if (r == 0) return false;
+    const uint32_t h = perm ? perm[r - 1] : (uint32_t)(r - 1);
+    if (g >= n || h >= n) return false;                              // (a permutation of [0, n): never taken)
+    const uint32_t* __restrict__ a = text + (uint64_t)g * width;
+    const uint32_t* __restrict__ b = text + (uint64_t)h * width;
+    bool differ = false;
+    for (int p = 0; p < width; ++p) differ |= a[p] != b[p];
+    return differ;
+}
+__global__ __launch_bounds__(TPB) void k_rank_count(const uint32_t* __restrict__ text, int width, const uint32_t* __restrict__ perm, uint32_t n, uint32_t* __restrict__ tile_heads, uint32_t ntiles) {
+    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return;
+    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t heads = 0;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        uint32_t g = 0;
+        const bool head = r < r1 && text_head(text, width, perm, r, n, g);
+        heads += (uint32_t)__popcll(__ballot(head));
+    }
+    if (lane_id() == 0) tile_heads[w] = heads;
+}
+__global__ __launch_bounds__(TPB) void k_rank_place(const uint32_t* __restrict__ text, int width, const uint32_t* __restrict__ perm, uint32_t n, const uint32_t* __restrict__ tile_off, uint32_t ntiles,
+                                                   int64_t* __restrict__ ranks) {
+    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return;
+    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    const uint64_t le = lanemask_lt() | (1ull << lane_id());
+    uint32_t run = tile_off[w];                                       // ranks opened before this tile
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        uint32_t g = 0;
+        const bool live = r < r1;
+        const bool head = live && text_head(text, width, perm, r, n, g);
+        const uint64_t m = __ballot(head);
+        if (live && g < n) ranks[g] = (int64_t)(run + (uint32_t)__popcll(m & le));
+        run += (uint32_t)__popcll(m);
+    }
+}
+
 struct Scratch {                                     // pool blocks of one call, returned on every way out
     sdqh_ctx* ctx; void* p[3] = {nullptr, nullptr, nullptr};
     explicit Scratch(sdqh_ctx* c) : ctx(c) {}
@@ -281,25 +399,19 @@ int sdqh_sort_geometry(sdqh_ctx* ctx, int64_t* single_wg_max, int64_t* tile_rows
     return SDQH_OK;
 }
 
-int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
-                      int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
-    sdqh_table* table = const_cast<sdqh_table*>(ctable);
-    if (!ctx || !table || !out_n || !sort || nsort < 1 || nsort > SDQH_SORT_MAX_KEYS || limit < 1 || capacity < 0)
-        return fail(ctx, SDQH_ERR_INVALID, "table_sorted: bad arguments");
-    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: compile-only context");
-    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: bitmap-only table");
-    (void)hipSetDevice(ctx->device);
-    DevSortSpec spec; std::memset(&spec, 0, sizeof(spec));
-    spec.nsort = nsort;
+// one pass of the radix path over `key` at `shift`: perm (nullptr: the identity) -> out
+static void radix_pass(sdqh_ctx* ctx, const uint64_t* key, const uint32_t* perm, uint32_t n, int shift, uint32_t* hist, uint32_t* bin_total, uint32_t ntiles, uint32_t* out) {
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    LAUNCH(ctx, "k_sort_hist", k_sort_hist, tgrid, key, perm, n, shift, hist, ntiles);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 256, hist, ntiles, bin_total);
+    LAUNCH(ctx, "k_sort_scatter", k_sort_scatter, tgrid, key, perm, n, shift, hist, bin_total, ntiles, out);
+}
+
+// sdqh_table_sorted / sdqh_table_sorted_by behind their argument checks; who: the entry point's name in messages
+static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms,
+                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    const std::string me(who);
     const int nv = table->accumulate ? table->nv : 0;
-    for (int i = 0; i < nsort; ++i) {
-        const sdqh_sort_key& sk = sort[i];
-        const bool ok = (sk.kind == SDQH_SORT_KEY) || (sk.kind == SDQH_SORT_PAYLOAD && sk.index >= 0 && sk.index < table->npay) ||
-                        (sk.kind == SDQH_SORT_VALUE && sk.index >= 0 && sk.index < nv) || (sk.kind == SDQH_SORT_HITS && table->accumulate);
-        if (!ok) return fail(ctx, SDQH_ERR_INVALID, "table_sorted: sort key names a field the table does not have");
-        spec.key[i].kind = sk.kind; spec.key[i].index = sk.index; spec.key[i].desc = sk.descending ? 1 : 0;
-        spec.key[i].is_f64 = sk.kind == SDQH_SORT_VALUE ? 1 : (sk.kind == SDQH_SORT_PAYLOAD ? (sk.is_f64 ? 1 : 0) : 0);
-    }
     call_begin(ctx);
     if (int rc = index_ensure(ctx, table)) return rc;
     Scratch scratch(ctx);
@@ -308,7 +420,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
     const int nseg = table->stage.nseg;
     const size_t seg_bytes = round_up((size_t)std::max(nseg, 1) * 4), info_bytes = round_up(SORT_INFO * 8), ref_bytes = round_up(rows * 4), key_bytes = round_up(rows * 8);
     char* blob = static_cast<char*>(scratch.p[0] = pool_alloc(ctx, seg_bytes + info_bytes + ref_bytes + key_bytes * (size_t)nsort));
-    if (!blob) return fail(ctx, SDQH_ERR_NOMEM, "table_sorted: out of device memory");
+    if (!blob) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
     uint32_t* seg_off = reinterpret_cast<uint32_t*>(blob);
     unsigned long long* info = reinterpret_cast<unsigned long long*>(blob + seg_bytes);
     uint32_t* refs = reinterpret_cast<uint32_t*>(blob + seg_bytes + info_bytes);
@@ -320,15 +432,24 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
     LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, seg_off, nseg, info);
     LAUNCH(ctx, "k_sort_gather", k_sort_gather, seg_grid, table->dev, table->stage, mh, seg_off, refs);
     const unsigned key_grid = (unsigned)std::max<size_t>(1, std::min<size_t>((rows + TPB - 1) / TPB, (size_t)ctx->num_cu * 8));
-    for (int c = 0; c < nsort; ++c) LAUNCH(ctx, "k_sort_keys", k_sort_keys, key_grid, table->stage, spec.key[c], refs, keys + (size_t)c * key_stride, info, c);
+    for (int c = 0; c < nsort; ++c) {
+        if (term_derived(terms[c])) LAUNCH(ctx, "k_sort_term_keys", k_sort_term_keys, key_grid, table->stage, terms[c], refs, keys + (size_t)c * key_stride, info, c);
+        else LAUNCH(ctx, "k_sort_keys", k_sort_keys, key_grid, table->stage, terms[c].sk, refs, keys + (size_t)c * key_stride, info, c);
+    }
     HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, info, SORT_INFO * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     unsigned long long h[SORT_INFO];
     std::memcpy(h, ctx->result_host, sizeof(h));
+    if (h[SORT_INFO_BAD]) {                                           // before anything is written, *out_n included
+        int c = 0;
+        while (c < nsort - 1 && !((h[SORT_INFO_BAD] >> c) & 1ull)) ++c;
+        call_end(ctx);
+        return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(c) + " derives a field outside its ranks column (" + std::to_string((long long)terms[c].nranks) + " rows)");
+    }
     const int64_t n = (int64_t)h[0], m = std::min<int64_t>(limit, n);
     *out_n = m;
     if (!out_keys && !out_payload && !out_values && !out_hits) { call_end(ctx); return SDQH_OK; }      // count-only call
-    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, "table_sorted: capacity too small"); }
+    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
     if (m == 0) { call_end(ctx); return SDQH_OK; }
     // the passes: last column first, low digit first; a digit whose bits are the same in every key orders nothing
     int pass_col[8 * SDQH_SORT_MAX_KEYS], pass_shift[8 * SDQH_SORT_MAX_KEYS], npass = 0;
@@ -344,7 +465,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
     if (npass) {
         const size_t perm_bytes = round_up((size_t)n * 4), hist_bytes = small ? 0 : round_up((size_t)ntiles * 256 * 4);
         char* b1 = static_cast<char*>(scratch.p[1] = pool_alloc(ctx, perm_bytes * (small ? 1 : 2) + hist_bytes + 1024));
-        if (!b1) return fail(ctx, SDQH_ERR_NOMEM, "table_sorted: out of device memory");
+        if (!b1) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         uint32_t* pa = reinterpret_cast<uint32_t*>(b1);
         if (small) {
             LAUNCH(ctx, "k_sort_small", k_sort_small, 1, keys, key_stride, nsort, un, info, pa);
@@ -353,12 +474,8 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
             uint32_t* pb = reinterpret_cast<uint32_t*>(b1 + perm_bytes);
             uint32_t* hist = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes);
             uint32_t* bin_total = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes + hist_bytes);
-            const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
             for (int p = 0; p < npass; ++p) {
-                const uint64_t* key = keys + (size_t)pass_col[p] * key_stride;
-                LAUNCH(ctx, "k_sort_hist", k_sort_hist, tgrid, key, perm, un, pass_shift[p], hist, ntiles);
-                LAUNCH(ctx, "k_sort_bins", k_sort_bins, 256, hist, ntiles, bin_total);
-                LAUNCH(ctx, "k_sort_scatter", k_sort_scatter, tgrid, key, perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
+                radix_pass(ctx, keys + (size_t)pass_col[p] * key_stride, perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
                 perm = pa; std::swap(pa, pb);
             }
         }
@@ -368,7 +485,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
     const size_t nb = (size_t)m * 8, need = nb * (size_t)narr;
     if (narr) {
         char* dev = static_cast<char*>(scratch.p[2] = pool_alloc(ctx, need + 64));
-        if (!dev) return fail(ctx, SDQH_ERR_NOMEM, "table_sorted: out of device memory");
+        if (!dev) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         DevSortOut o; std::memset(&o, 0, sizeof(o));
         size_t at = 0;
         if (out_keys) { o.keys = reinterpret_cast<int64_t*>(dev + at); at += nb; }
@@ -398,6 +515,131 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
         if (pinned) for (int a = 0; a < nd; ++a) std::memcpy(dst[a], static_cast<const char*>(ctx->bulk_host) + (size_t)a * nb, nb);
     }
     if (out_values) for (int v = nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, nb);
+    return SDQH_OK;
+}
+
+// the checks both entry points make of a sort column; the term's derivation is left as it is
+static bool sort_column_ok(const sdqh_table* table, int kind, int index) {
+    const int nv = table->accumulate ? table->nv : 0;
+    return (kind == SDQH_SORT_KEY) || (kind == SDQH_SORT_PAYLOAD && index >= 0 && index < table->npay) ||
+           (kind == SDQH_SORT_VALUE && index >= 0 && index < nv) || (kind == SDQH_SORT_HITS && table->accumulate);
+}
+static void sort_column_set(DevSortKey& k, int kind, int index, int descending, int is_f64) {
+    k.kind = kind; k.index = index; k.desc = descending ? 1 : 0;
+    k.is_f64 = kind == SDQH_SORT_VALUE ? 1 : (kind == SDQH_SORT_PAYLOAD ? (is_f64 ? 1 : 0) : 0);
+}
+
+int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
+                      int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    sdqh_table* table = const_cast<sdqh_table*>(ctable);
+    if (!ctx || !table || !out_n || !sort || nsort < 1 || nsort > SDQH_SORT_MAX_KEYS || limit < 1 || capacity < 0)
+        return fail(ctx, SDQH_ERR_INVALID, "table_sorted: bad arguments");
+    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: compile-only context");
+    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: bitmap-only table");
+    (void)hipSetDevice(ctx->device);
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
+    for (int i = 0; i < nsort; ++i) {
+        if (!sort_column_ok(table, sort[i].kind, sort[i].index)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted: sort key names a field the table does not have");
+        sort_column_set(terms[i].sk, sort[i].kind, sort[i].index, sort[i].descending, sort[i].is_f64);
+    }
+    return sorted_impl(ctx, table, "table_sorted", min_hits, limit, nsort, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
+                         int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    sdqh_table* table = const_cast<sdqh_table*>(ctable);
+    if (!ctx || !table || !out_n || !in || nterms < 1 || nterms > SDQH_SORT_MAX_KEYS || limit < 1 || capacity < 0)
+        return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: bad arguments");
+    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted_by: compile-only context");
+    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted_by: bitmap-only table");
+    (void)hipSetDevice(ctx->device);
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
+    for (int i = 0; i < nterms; ++i) {
+        const sdqh_sort_term& t = in[i];
+        if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " names a field the table does not have");
+        sort_column_set(terms[i].sk, t.kind, t.index, t.descending, t.is_f64);
+        if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " has a negative divisor or modulus");
+        if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + ": ranks must be an I64 column");
+        terms[i].div = (uint64_t)t.div; terms[i].mod = (uint64_t)t.mod; terms[i].add = t.add;
+        terms[i].ranks = t.ranks ? static_cast<const int64_t*>(t.ranks->data) : nullptr;
+        terms[i].nranks = t.ranks ? t.ranks->nrows : 0;
+        if (term_derived(terms[i]) && terms[i].sk.is_f64) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " derives from a double");
+    }
+    return sorted_impl(ctx, table, "table_sorted_by", min_hits, limit, nterms, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_column** out_ranks, int64_t* out_distinct) {
+    if (!ctx || !text || !out_ranks || !out_distinct || nrows < 0) return fail(ctx, SDQH_ERR_INVALID, "text_ranks: bad arguments");
+    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "text_ranks: compile-only context");
+    if (text->dtype != SDQH_STR || text->width < 1 || text->nrows < nrows || (nrows && !text->data)) return fail(ctx, SDQH_ERR_INVALID, "text_ranks: needs a STR column covering nrows");
+    if (text->width > TEXT_MAX_WIDTH) return fail(ctx, SDQH_ERR_UNSUPPORTED, "text_ranks: more than " + std::to_string(TEXT_MAX_WIDTH) + " code units per row");
+    if (nrows > 0xFFFFFFF0ll) return fail(ctx, SDQH_ERR_UNSUPPORTED, "text_ranks: row references are 32 bits");
+    (void)hipSetDevice(ctx->device);
+    sdqh_column* rk = nullptr;
+    if (int rc = sdqh_column_alloc(ctx, nrows, SDQH_I64, 0, &rk)) return rc;
+    *out_distinct = 0;
+    if (nrows == 0) { *out_ranks = rk; return SDQH_OK; }
+    struct Drop { sdqh_ctx* ctx; sdqh_column* c; ~Drop() { if (c) sdqh_column_free(ctx, c); } } drop{ctx, rk};      // on every way out but the last
+    call_begin(ctx);
+    Scratch scratch(ctx);
+    const int width = text->width;
+    const uint32_t* units = static_cast<const uint32_t*>(text->data);
+    const uint32_t un = (uint32_t)nrows;
+    const uint32_t ntiles = (uint32_t)((nrows + SORT_TILE - 1) / SORT_TILE);
+    // one block: [masks | info | tile heads | keys | permutation x 2 | digit counts per tile | digit totals]
+    const size_t mask_bytes = round_up(2 * TEXT_MAX_WIDTH * 4), info_bytes = round_up(SORT_INFO * 8), tile_bytes = round_up((size_t)ntiles * 4), key_bytes = round_up((size_t)nrows * 8),
+                 perm_bytes = round_up((size_t)nrows * 4), hist_bytes = round_up((size_t)ntiles * 256 * 4);
+    char* blob = static_cast<char*>(scratch.p[0] = pool_alloc(ctx, mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes + hist_bytes + 1024));
+    if (!blob) return fail(ctx, SDQH_ERR_NOMEM, "text_ranks: out of device memory");
+    uint32_t* masks = reinterpret_cast<uint32_t*>(blob);
+    unsigned long long* info = reinterpret_cast<unsigned long long*>(blob + mask_bytes);
+    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes);
+    uint64_t* key = reinterpret_cast<uint64_t*>(blob + mask_bytes + info_bytes + tile_bytes);
+    uint32_t* pa = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes);
+    uint32_t* pb = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + perm_bytes);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes);
+    uint32_t* bin_total = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes + hist_bytes);
+    // (a) which bytes vary at all
+    HIP_TRYS(ctx, hipMemsetAsync(masks, 0xFF, TEXT_MAX_WIDTH * 4, ctx->stream));
+    HIP_TRYS(ctx, hipMemsetAsync(masks + TEXT_MAX_WIDTH, 0, TEXT_MAX_WIDTH * 4, ctx->stream));
+    const int rows_per = TPB / width;
+    const unsigned mgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nrows + rows_per - 1) / rows_per, (int64_t)ctx->num_cu * 8));
+    LAUNCH(ctx, "k_text_masks", k_text_masks, mgrid, units, (uint64_t)nrows, width, masks);
+    HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, masks, 2 * TEXT_MAX_WIDTH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    uint32_t hm[2 * TEXT_MAX_WIDTH];
+    std::memcpy(hm, ctx->result_host, sizeof(hm));
+    uint16_t vunit[TEXT_MAX_WIDTH * 4]; uint8_t vshift[TEXT_MAX_WIDTH * 4]; int nvb = 0;
+    for (int p = 0; p < width; ++p) {
+        const uint32_t vary = hm[TEXT_MAX_WIDTH + p] & ~hm[p];
+        for (int shift = 24; shift >= 0; shift -= 8) if ((vary >> shift) & 255u) { vunit[nvb] = (uint16_t)p; vshift[nvb] = (uint8_t)shift; ++nvb; }
+    }
+    // (b) + (c): last word first; within a word the last byte (the lowest digit) first
+    const uint32_t* perm = nullptr;
+    const unsigned pgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nrows + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+    const int nwords = (nvb + TEXT_WORD_BYTES - 1) / TEXT_WORD_BYTES;
+    if (nrows > 1) for (int w = nwords - 1; w >= 0; --w) {
+        DevTextWord tw; std::memset(&tw, 0, sizeof(tw));
+        tw.nbytes = std::min(TEXT_WORD_BYTES, nvb - w * TEXT_WORD_BYTES);
+        for (int b = 0; b < tw.nbytes; ++b) { tw.unit[b] = vunit[w * TEXT_WORD_BYTES + b]; tw.shift[b] = vshift[w * TEXT_WORD_BYTES + b]; }
+        LAUNCH(ctx, "k_text_pack", k_text_pack, pgrid, units, (uint64_t)nrows, width, tw, key);
+        for (int b = tw.nbytes - 1; b >= 0; --b) {
+            radix_pass(ctx, key, perm, un, 56 - 8 * b, hist, bin_total, ntiles, pa);
+            perm = pa; std::swap(pa, pb);
+        }
+    }
+    // (d) dense ranks
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    LAUNCH(ctx, "k_rank_count", k_rank_count, tgrid, units, width, perm, un, tile_heads, ntiles);
+    LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_heads, (int)ntiles, info);
+    LAUNCH(ctx, "k_rank_place", k_rank_place, tgrid, units, width, perm, un, tile_heads, ntiles, static_cast<int64_t*>(rk->data));
+    HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, info, 8, hipMemcpyDeviceToHost, ctx->stream));
+    call_end(ctx);
+    if (int rc = sync_stream(ctx)) return rc;
+    unsigned long long heads;
+    std::memcpy(&heads, ctx->result_host, 8);
+    *out_distinct = (int64_t)heads + 1;
+    *out_ranks = rk; drop.c = nullptr;
     return SDQH_OK;
 }
 

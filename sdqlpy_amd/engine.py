@@ -14,6 +14,7 @@ Mapping of the reference's emitted loop shapes (src/sdqlpy/lib/sdql_ir_cpp_gener
 
 Anything else raises frontend.UnsupportedQuery.  There is no CPU execution path here.
 """
+import collections
 import os
 import weakref
 
@@ -109,6 +110,8 @@ class Engine:
         self._dicts = {}           # id(string ndarray) -> (ndarray, codes int64 ndarray, distinct values)
         self._range_cache = {}     # id(int64 ndarray) -> (ndarray, (min, span))
         self._distinct_cache = {}  # id(ndarray) -> (ndarray, has no repeated value)
+        self._increasing_cache = {}  # id(ndarray) -> (ndarray, is strictly increasing: a code / row reference into it orders as the text it stands for)
+        self._text_ranks = {}      # id(text ndarray) -> (ndarray, resident I64 column of its rows' dense ranks, distinct texts): beside its resident column
         self._frozen = {}          # id(ndarray) -> ndarray made read-only on adoption (see column())
         self._prepared = weakref.WeakSet()      # prepared plans bound to this engine (their recordings — PlanGraph — are dropped with the columns they read)
         self._outstanding = weakref.WeakSet()   # results launched and not looked at yet (DeferredResultSet): finished before the data they were computed from is dropped
@@ -153,6 +156,10 @@ class Engine:
         # ORDER BY beyond sdqh_table_topk (more than 128 rows, more than 3 columns, no limit) on the device where the library has the
         # ordering extension (abi.Context.table_sorted); 0: compact + host lexsort, as on a library without it (A/B measurements, tests)
         self.device_sort = os.environ.get("SDQLPY_AMD_DEVICE_SORT", "1") != "0"
+        # ... and over text, packed keys and mixed-radix keys where it also has the sort terms (abi.Context.table_sorted_by, text_ranks).
+        # order_routes: per result finalised with an ORDER BY where it was ordered — {"route": "topk" | "sorted" | "sorted_by" | "host",
+        # "ranked": the order columns that went through a rank table} (the last 256)
+        self.order_routes = collections.deque(maxlen=256)
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -184,6 +191,7 @@ class Engine:
                                    for k, v in sorted(self.distinct_loops.items(), key=lambda kv: str(kv[0]))],
                 "extrema_loops": [{"line": k[0], "result": k[1], "route": v["route"], "runs": v["runs"]}
                                   for k, v in sorted(self.extrema_loops.items(), key=lambda kv: str(kv[0]))],
+                "order_routes": [dict(r) for r in self.order_routes],
                 "plan_graphs": dict(self.graph_stats), "resident_bytes": int(self.resident_bytes), "lanes": int(self.nlanes)}
 
     def synchronize(self):
@@ -228,10 +236,14 @@ class Engine:
         for _, col in self._columns.values():
             col.free()
         self._columns.clear()
+        for _, ranks, _ in self._text_ranks.values():
+            ranks.free()
+        self._text_ranks.clear()
         self._thaw(list(self._frozen.values()))
         self._frozen.clear()
         self._range_cache.clear()
         self._distinct_cache.clear()
+        self._increasing_cache.clear()
         self.__dict__.get("_dict_futures", {}).clear()        # (a pass still running finishes into nothing: its arrays stay alive in the task)
         self.resident_bytes = 0
         self.generation += 1
@@ -286,7 +298,7 @@ class Engine:
         if self.ctx.handle is not None:
             self.finish_outstanding()
             self.drop_recordings()
-        if any(id(arr) in self._columns for arr in arrays) and self.ctx.handle is not None:
+        if any(id(arr) in self._columns or id(arr) in self._text_ranks for arr in arrays) and self.ctx.handle is not None:
             self.ctx.synchronize()                              # (queries launched and not waited for may still read them)
         for arr in arrays:
             key = id(arr)
@@ -298,12 +310,43 @@ class Engine:
             d = self._dicts.pop(key, None)
             if d is not None and d[1] is not None:
                 self.invalidate(d[1])                        # the code column built from it
+                self.invalidate(d[2])                        # ... and what was derived from its distinct values (their ranks)
+            ranked = self._text_ranks.pop(key, None)
+            if ranked is not None:
+                ranked[1].free()
+                self.resident_bytes -= 8 * ranked[1].nrows
             self._range_cache.pop(key, None)
             self._distinct_cache.pop(key, None)
+            self._increasing_cache.pop(key, None)
             frozen = self._frozen.pop(key, None)
             if frozen is not None:
                 self._thaw([frozen])
         self.generation += 1
+
+    def rank_column(self, text):
+        """Resident int64 column of the dense ranks of a text array's rows (abi.Context.text_ranks: rank[r] < rank[s] iff text r sorts
+        before text s): what ORDER BY reads through when a result carries row references / codes into `text`.  Computed once per
+        host array, cached beside its resident column and dropped with it by invalidate()."""
+        hit = self._text_ranks.get(id(text))
+        if hit is None or hit[0] is not text:
+            if hit is not None:                                  # (the identity was reused by another array)
+                hit[1].free()
+                self.resident_bytes -= 8 * hit[1].nrows
+            resident = self._columns.get(id(text))
+            if resident is not None and resident[0] is text:
+                ranks, distinct = self.ctx.text_ranks(resident[1], len(text))
+            else:                                                # only the ranks stay: the text itself is uploaded for the call alone
+                col = self.ctx.upload(text)
+                try:
+                    ranks, distinct = self.ctx.text_ranks(col, len(text))
+                finally:
+                    col.free()
+                if text.flags.writeable:                         # (as column(): an in-place edit would leave the ranks describing the old text)
+                    text.flags.writeable = False
+                    self._frozen[id(text)] = text
+            hit = self._text_ranks[id(text)] = (text, ranks, distinct)
+            self.resident_bytes += 8 * ranks.nrows
+        return hit[1]
 
     def rowid_column(self, nrows):
         """Resident int64 column 0..nrows-1: how a string column travels as a payload or a group key
@@ -1519,32 +1562,126 @@ def _compact(eng, table, min_hits, hint_key, **want):
     return keys, payload, values, hits
 
 
-def _device_sort_spec(bt, key_fields, vnames, count_idx, order):
-    """[(kind, index, descending, is_f64)] for sdqh_table_topk, or None when a column of `order`
-    cannot be ordered on the device (text travels as row references; composite keys are packed)."""
+def _increasing_cached(eng, arr):
+    """Is every entry of the decoder `arr` greater than the one before it (a sorted Dictionary: the code orders as the text)?"""
+    cache = eng._increasing_cache
+    hit = cache.get(id(arr))
+    if hit is None or hit[0] is not arr:
+        a = np.asarray(arr)
+        hit = cache[id(arr)] = (arr, bool(len(a) < 2 or (a[1:] > a[:-1]).all()))
+    return hit[1]
+
+
+def _sort_terms_on(eng):
+    return eng is not None and bool(getattr(eng, "device_sort", True)) and bool(getattr(eng.ctx.library, "has_sort_terms", False))
+
+
+def _sort_term(eng, kind, index, desc, dec, div=0, mod=0, add=0, is_key=False):
+    """One integer sort column of the device's ORDER BY: the plain 4-tuple sdqh_table_topk / _sorted take when nothing is derived, else
+    the term (kind, index, descending, False, div, mod, add, text) of abi.Context.table_sorted_by — field = (source / div) % mod + add,
+    and with `text` (the decoder the field indexes, when its order is not the field's own) the field's RANK is what is ordered.  None:
+    not provably order-preserving here (a decoder that is not text, too wide to rank, or no library to take terms) — or, for a (part
+    of a) KEY, a decoder in which a text may come twice: row references into a table's own column, where entries that hold equal text
+    are still to be merged on the host (_merge_equal_keys), which ORDER BY / LIMIT must not run ahead of."""
+    text = None
+    if dec is not None:
+        if eng is None or not isinstance(dec, np.ndarray) or dec.dtype.kind != "U" or dec.ndim != 1:
+            return None
+        if is_key:
+            from .result import Dictionary
+            if not isinstance(dec, Dictionary) and not _distinct_cached(eng, dec):
+                return None
+        if not _increasing_cached(eng, dec):                 # (strictly increasing: the code is the rank)
+            if dec.dtype.itemsize // 4 > abi.TEXT_RANK_MAX_WIDTH:
+                return None
+            text = dec
+    if div <= 1 and mod == 0 and add == 0 and text is None:
+        return (kind, index, desc, False)
+    if not _sort_terms_on(eng):
+        return None
+    return (kind, index, desc, False, int(max(div, 0)), int(mod), int(add), text)
+
+
+def _radix_term(eng, bt, name, desc):
+    """The term for field `name` of a mixed-radix group key (bt.key_radix): div = the product of the spans below it, mod = its span
+    (none for an open top digit), add = its lowest value; a part of several digits (substr: one per code unit, most significant
+    first) is ONE term over the product of their spans — the digits' own offsets do not change the order."""
+    parts, radix = bt.key_radix
+    strides, stride = [], 1
+    for lo, span in reversed(radix):
+        strides.append(stride)
+        stride *= span if span is not None else 1
+    strides.reverse()
+    at = 0
+    for pname, vs, kind in parts:
+        digits = list(range(at, at + len(vs)))
+        at += len(vs)
+        if pname != name:
+            continue
+        if kind[0] == "chars":
+            if any(radix[i][1] is None for i in digits):
+                return None
+            width = 1
+            for i in digits:
+                width *= radix[i][1]
+            return _sort_term(eng, abi.SORT_KEY, 0, desc, None, strides[digits[-1]], width if digits[0] > 0 else 0, 0)
+        if len(digits) != 1:
+            return None
+        lo, span = radix[digits[0]]
+        top_digit = digits[0] == 0                           # nothing above it: the quotient is the digit
+        return _sort_term(eng, abi.SORT_KEY, 0, desc, kind[1], strides[digits[0]], 0 if (span is None or top_digit) else span, lo, is_key=True)
+    return None
+
+
+def _device_sort_spec(bt, key_fields, vnames, count_idx, order, eng=None, fields_of=None):
+    """The sort columns of `order` for the device: [(kind, index, descending, is_f64)] as sdqh_table_topk / sdqh_table_sorted take them,
+    with (kind, index, descending, False, div, mod, add, text) — a term of abi.Context.table_sorted_by — for a column that is derived:
+    text behind row references or codes, a half of a packed key, a field of a mixed-radix key (needs `eng`: its caches and a library
+    with the sort terms).  None when some column cannot be ordered on the device."""
     spec = []
     for name, direction in order:
         desc = direction == "desc"
         hit = [src for fname, src in key_fields if fname == name]
-        if hit:
+        term = False
+        if getattr(bt, "key_radix", None) is not None and any(pname == name for pname, _, _ in bt.key_radix[0]):
+            term = _radix_term(eng, bt, name, desc)
+        elif bt.key_parts is not None and name in bt.key_parts:
+            i = list(bt.key_parts).index(name)
+            decs = getattr(bt, "key_part_decoders", None) or [None, None]
+            term = _sort_term(eng, abi.SORT_KEY, 0, desc, decs[i], div=(1 << 32) if i == 0 else 0, mod=0 if i == 0 else (1 << 32), is_key=True)
+        elif hit:
             src = hit[0]
             if src == "key":
-                if bt.key_parts is not None or bt.key_decoder is not None:
+                if bt.key_parts is not None or getattr(bt, "key_radix", None) is not None:
+                    return None                              # (the packed integer itself is no column of the result)
+                term = _sort_term(eng, abi.SORT_KEY, 0, desc, bt.key_decoder, is_key=True)
+            elif np.dtype(bt.payload_dtypes[src]).kind == "f":
+                if bt.decoder_of(fields_of.get(name) if fields_of is not None else name, src) is not None:
                     return None
-                spec.append((abi.SORT_KEY, 0, desc, False))
+                term = (abi.SORT_PAYLOAD, src, desc, True)
             else:
-                if bt.decoders.get(src) is not None:
-                    return None
-                spec.append((abi.SORT_PAYLOAD, src, desc, np.dtype(bt.payload_dtypes[src]).kind == "f"))
+                term = _sort_term(eng, abi.SORT_PAYLOAD, src, desc, bt.decoder_of(fields_of.get(name) if fields_of is not None else name, src))
         elif name in vnames:
             i = vnames.index(name)
             if count_idx is not None and i == count_idx:
-                spec.append((abi.SORT_HITS, 0, desc, False))
+                term = (abi.SORT_HITS, 0, desc, False)
             else:
-                spec.append((abi.SORT_VALUE, i - (1 if count_idx is not None and count_idx < i else 0), desc, True))
-        else:
+                term = (abi.SORT_VALUE, i - (1 if count_idx is not None and count_idx < i else 0), desc, True)
+        if term is False:
             raise KeyError("top: the result has no column %r" % name)
+        if term is None:
+            return None
+        spec.append(term)
     return spec
+
+
+def _derived(spec):
+    return spec is not None and any(len(t) > 4 for t in spec)
+
+
+def _note_order_route(eng, top, spec, route):
+    eng.order_routes.append({"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
+                             "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route == "sorted_by" and len(t) > 4 and t[7] is not None]})
 
 
 def _device_sorts(eng, top, spec):
@@ -1566,15 +1703,46 @@ def _sorted(eng, table, min_hits, hint_key, top, spec, want_hits):
     return keys, payload, values, hits
 
 
+def _sorted_by(eng, table, min_hits, hint_key, top, spec, want_hits):
+    """_sorted for a spec with derived terms (abi.Context.table_sorted_by, whatever k is: sdqh_table_topk cannot take them); the text a
+    term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
+    terms = [t if len(t) == 4 or t[7] is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
+    hint = eng.compact_hints.get(("sorted", hint_key))
+    cap = 4096 if hint is None else hint + hint // 8 + 1024
+    keys, payload, values, hits = eng.ctx.table_sorted_by(table, min_hits, min(int(top[0]), abi.SORT_ALL), terms, cap, want_hits=want_hits)
+    eng.compact_hints[("sorted", hint_key)] = len(keys)
+    return keys, payload, values, hits
+
+
+def _fetch_ordered(eng, bt_table, min_hits, hint_key, top, spec, want_hits):
+    """The first k rows of a table in the order of `top` = (k, order) where the device can order them (spec): (keys, payload, values,
+    hits), or None — the caller compacts and the host orders.  Which way it went is noted in Engine.order_routes."""
+    if top is None:
+        return None
+    route = "host"
+    if _derived(spec):
+        if top[0] >= 1 and len(spec) <= abi.SORT_MAX_KEYS and _sort_terms_on(eng):
+            route = "sorted_by"
+    elif spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
+        route = "topk"
+    elif _device_sorts(eng, top, spec):
+        route = "sorted"
+    _note_order_route(eng, top, spec, route)
+    if route == "topk":
+        return eng.ctx.table_topk(bt_table, min_hits, top[0], spec, want_hits=want_hits)
+    if route == "sorted":
+        return _sorted(eng, bt_table, min_hits, hint_key, top, spec, want_hits)
+    if route == "sorted_by":
+        return _sorted_by(eng, bt_table, min_hits, hint_key, top, spec, want_hits)
+    return None
+
+
 def _fetch_entries(eng, bt_table, min_hits, hint_key, top, spec, **want):
     """K-F rows of a table: all of them, or with `top` = (k, order) only the first k in that order
     when the device can order them (spec) — otherwise all, ordered afterwards on the host."""
-    if top is not None and spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
-        keys, payload, values, hits = eng.ctx.table_topk(bt_table, min_hits, top[0], spec, want_hits=want.get("want_hits", True))
-        return keys, payload, values, hits, True
-    if _device_sorts(eng, top, spec):
-        keys, payload, values, hits = _sorted(eng, bt_table, min_hits, hint_key, top, spec, want.get("want_hits", True))
-        return keys, payload, values, hits, True
+    got = _fetch_ordered(eng, bt_table, min_hits, hint_key, top, spec, want.get("want_hits", True))
+    if got is not None:
+        return got[0], got[1], got[2], got[3], True
     keys, payload, values, hits = _compact(eng, bt_table, min_hits, hint_key, **want)
     return keys, payload, values, hits, False
 
@@ -1593,13 +1761,15 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
     """Device-resident intermediate -> DictResult on the host (K-F's input).  With `top`, the
     DictResult carries `.ordered = True` when the device already applied ORDER BY / LIMIT."""
     if isinstance(value, DictResult):
+        if top is not None:
+            _note_order_route(eng, top, None, "host")
         return value
     if isinstance(value, tuple) and value and value[0] == "aggregated":
         bt = env[value[1]]
         out_key_fields, vnames, count_idx, key_is_record, val_is_record, nv = bt.agg
         entry_is_group = any(src == "key" for _, src in out_key_fields) or bt.shared_groups
-        spec = _device_sort_spec(bt, out_key_fields, vnames, count_idx, top[1]) if top is not None and entry_is_group and bt.key_radix is None else None
         fields_of = bt.agg_fields
+        spec = _device_sort_spec(bt, out_key_fields, vnames, count_idx, top[1], eng, fields_of) if top is not None and entry_is_group else None
         lazy = lazy_ok and bool(getattr(eng, "lazy_results", False)) and _lazy_rows_ok(bt, out_key_fields, fields_of, top)
         want_hits = count_idx is not None or (spec is not None and any(s[0] == abi.SORT_HITS for s in spec))
         hint = eng.compact_hints.get(hint_key)
@@ -1636,7 +1806,7 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:    # several key fields in one mixed-radix integer
             from . import xplan
             d = DictResult(xplan._decode_radix(keys, bt.key_radix[0], bt.key_radix[1]), _value_arrays(vnames, count_idx, values, hits, bt.int_values), True, val_is_record)
-            d.ordered = False
+            d.ordered = ordered
             return d
         if bt.key_parts is not None and out_key_fields == [(bt.key_name, "key")]:        # a composite group key: its two packed parts
             decs = getattr(bt, "key_part_decoders", None) or [None, None]
@@ -1722,13 +1892,11 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         d.ordered = sel is not None
         return d
     if isinstance(value, BuiltTable):
-        spec = _device_sort_spec(value, [(value.key_name, "key")] + [(f, src) for f, src in value.val_fields if src != "key"], [], None, top[1]) \
-            if top is not None and value.key_parts is None else None
-        if top is not None and spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
-            keys, payload, _, _ = eng.ctx.table_topk(value.table, 0, top[0], spec, want_hits=False)
-            ordered = True
-        elif _device_sorts(eng, top, spec):
-            keys, payload, _, _ = _sorted(eng, value.table, 0, hint_key, top, spec, False)
+        spec = _device_sort_spec(value, [(value.key_name, "key")] + [(f, src) for f, src in value.val_fields if src != "key"], [], None, top[1], eng) \
+            if top is not None else None
+        got = _fetch_ordered(eng, value.table, 0, hint_key, top, spec, False)
+        if got is not None:
+            keys, payload = got[0], got[1]
             ordered = True
         else:
             keys, payload, _, _ = _compact(eng, value.table, 0, hint_key, want_values=False, want_hits=False)
@@ -1768,7 +1936,12 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_top = (top[0], [(names.get(n, n), d) for n, d in top[1]])
+    noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
+    if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
+        route = eng.order_routes[-1]
+        ranked = {i for i, (nm, _) in enumerate(inner_top[1]) if nm in route["ranked"]}
+        route["order"], route["ranked"] = [nm for nm, _ in top[1]], [nm for i, (nm, _) in enumerate(top[1]) if i in ranked]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)
@@ -1880,6 +2053,7 @@ def _host_dict(eng, op, env, is_result):
     out = xplan.run_host_dict(eng, op, env, lambda v: _materialize(eng, v, env, hint_key=(id(op), id(v) if isinstance(v, BuiltTable) else 0)))
     top = env.get("__top__") if is_result else None
     if top is not None and isinstance(out, ResultSet):
+        _note_order_route(eng, top, None, "host")          # (the loop ran on the host: so does its ORDER BY)
         out = out.top(top[0], top[1])
     return out
 
