@@ -27,6 +27,10 @@ SORT_MAX_KEYS, SORT_ALL = 8, 1 << 62
 # columns — the halves of a packed key, the digits of a mixed-radix key, text behind row references or codes — and the ranking of a text column
 SORT_TERMS_EXPORTS = ["sdqh_text_ranks", "sdqh_table_sorted_by"]
 TEXT_RANK_MAX_WIDTH = 128
+# ... and its third (include/sdqh_sort_window.h, Library.has_window): ranks inside partitions of the ordered entries — ROW_NUMBER / RANK /
+# DENSE_RANK OVER (PARTITION BY ... ORDER BY ...) — and the first k rows of every partition
+WINDOW_EXPORTS = ["sdqh_table_window", "sdqh_window_geometry"]
+WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK = 0, 1, 2
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -1197,6 +1201,50 @@ class Context:
         self._check(self.lib.sdqh_sort_geometry(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def _need_window(self, what):
+        if not self.library.has_window:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window extension (include/sdqh_sort_window.h)" % (what, self.library.path))
+
+    def table_window(self, table, min_hits, npartition, terms, kind, per_limit, limit, capacity, want_hits=True, want_rank=True):
+        """Ranks inside partitions of the ordered entries: terms as table_sorted_by takes them, the first npartition of them PARTITION
+        BY; kind in WIN_ROW_NUMBER / WIN_RANK / WIN_DENSE_RANK; the rows with rank <= per_limit (SORT_ALL: every row), in sorted order,
+        the first min(limit, kept) of them.  The arrays are sized from `capacity`; a result that does not fit is fetched again with the
+        exact size.  Returns (keys, payload, values, hits, ranks) — ranks None without want_rank."""
+        self._need_window("table_window")
+        arr = (SortTerm * max(1, len(terms)))()
+        for i, term in enumerate(terms):
+            kind_i, index, desc, is_f64 = term[:4]
+            div, mod, add, ranks = term[4:] if len(term) > 4 else (0, 0, 0, None)
+            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind_i), int(index), int(bool(desc)), int(bool(is_f64))
+            arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = int(div), int(mod), int(add), None if ranks is None else ranks.handle
+        cap = max(1, min(int(capacity), int(limit))) if limit >= 1 else 1
+        for attempt in (0, 1):
+            keys = np.empty(cap, np.int64)
+            payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
+            values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
+            hits = np.empty(cap, np.int64) if want_hits else None
+            rank = np.empty(cap, np.int64) if want_rank else None
+            n = C.c_int64()
+            rc = self.lib.sdqh_table_window(self.handle, table.handle, C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), arr, C.c_int(kind),
+                                            C.c_int64(per_limit), C.c_int64(limit), C.c_int64(cap),
+                                            _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), _np_ptr(rank), C.byref(n))
+            if rc == ERR_OVERFLOW and attempt == 0:
+                cap = max(1, n.value)
+                continue
+            self._check(rc)
+            break
+        self._after_call("table_window")
+        n = n.value
+        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n],
+                None if rank is None else rank[:n])
+
+    def window_geometry(self):
+        """Sorted positions one wave ranks per step of sdqh_table_window's tile scan (what the tests size their cases from)."""
+        self._need_window("window_geometry")
+        a = C.c_int64()
+        self._check(self.lib.sdqh_window_geometry(self.handle, C.byref(a)))
+        return a.value
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1451,6 +1499,11 @@ class Library:
             L.sdqh_text_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
             L.sdqh_table_sorted_by.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
+        self.has_window = self.has_sort_terms and all(hasattr(L, s) for s in WINDOW_EXPORTS)      # ... and ranks inside partitions (include/sdqh_sort_window.h)
+        if self.has_window:
+            L.sdqh_table_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_geometry.argtypes = [C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -27,6 +27,27 @@
 // the key kernel is shared — and sdqh_text_ranks makes such a ranks column of a text column (k_text_masks / k_text_pack, the passes
 // above, k_rank_count / k_rank_place: see there).
 //
+// include/sdqh_sort_window.h on top of both: sdqh_table_window ranks the ordered entries inside PARTITIONS (maximal runs of sorted
+// positions whose first npartition keys are equal) and keeps the rows whose rank is <= per_limit — ROW_NUMBER / RANK / DENSE_RANK
+// OVER (PARTITION BY ... ORDER BY ...).  Selection, keys and passes are the ones above; between them and the emit:
+//
+//   k_win_heads       a wave owns a tile of SORT_TILE sorted positions: position i reads its keys and those of i - 1 through the
+//                     permutation and sets two flags (a byte per position) — part_head: a partition key differs, tie_head: any key
+//                     differs, position 0 both — and the wave folds its ballots into the tile's CARRY: {a partition head seen,
+//                     positions since the last partition head (no head: the tile's length), position of the last tie head relative
+//                     to the partition start, tie heads since the last partition head}
+//   k_win_scan        one workgroup: exclusive scan of the carries over the tiles with the segmented-scan operator (win_join: a
+//                     right side with a partition head wins, one without adds its length and tie heads to the left side — a tile
+//                     with no head at all passes the incoming carry through, longer), in place
+//   k_win_rank        the tile again with its carry-in, 64 positions at a time: the three ranks are read off the two ballots and
+//                     the running carry (row_number = distance to the last partition head + 1, rank = distance of the last tie head
+//                     to it + 1, dense_rank = tie heads between them); the kind asked for is stored per position (32 bits) and
+//                     the positions with rank <= per_limit are counted per tile
+//   k_sort_scan / k_win_place
+//                     those counts scanned over the tiles, then the kept positions placed in order (ballot + lanes below: no atomic
+//                     cursor, because order is the contract).  per_limit >= n keeps everything: both are skipped
+//   k_win_emit        k_sort_emit through the kept positions, with the rank column
+//
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
 // Nothing here has a counterpart in the reference, whose results are unordered sets.
@@ -38,7 +59,7 @@
 
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
-#include "sdqh_sort_terms.h"
+#include "sdqh_sort_window.h"
 
 using namespace sdqh_host;
 
@@ -382,8 +403,159 @@ __global__ __launch_bounds__(TPB) void k_rank_place(const uint32_t* __restrict__
     }
 }
 
+// ---- ranks inside partitions (sdqh_table_window) ---------------------------------------------------------------------------------
+// The carry of a run of sorted positions [a, b).  cnt: positions since the last partition head, that head included (none in the
+// run: b - a).  tie_off: the last tie head's distance from that partition head (no partition head: from a); only meaningful with
+// WIN_TIE.  ties: tie heads since the last partition head, itself included (none: in the whole run).  A partition head is a tie head.
+constexpr uint32_t WIN_PART = 1u, WIN_TIE = 2u;
+struct WinCarry { uint32_t flags, cnt, tie_off, ties; };
+static_assert(sizeof(WinCarry) == 16, "a carry is one 16-byte load");
+
+// the carry of [a, b) followed by [b, c): the segmented-scan operator (associative; {0, 0, 0, 0} is its left identity)
+__device__ __forceinline__ WinCarry win_join(const WinCarry& l, const WinCarry& r) {
+    if (r.flags & WIN_PART) return r;
+    WinCarry o;
+    o.flags = l.flags | r.flags;
+    o.cnt = l.cnt + r.cnt;
+    o.tie_off = (r.flags & WIN_TIE) ? l.cnt + r.tie_off : l.tie_off;
+    o.ties = l.ties + r.ties;
+    return o;
+}
+// `run` moved over one wave's batch of `live` positions (lanes [0, live)) with partition heads mp and tie heads mt
+__device__ __forceinline__ void win_step(WinCarry& run, uint64_t mp, uint64_t mt, uint32_t live) {
+    if (mp) {
+        const uint32_t p = 63u - (uint32_t)__clzll((long long)mp);
+        run.flags = WIN_PART | WIN_TIE;
+        run.cnt = live - p;
+        run.tie_off = (63u - (uint32_t)__clzll((long long)mt)) - p;         // (mt has bit p: the distance is >= 0)
+        run.ties = (uint32_t)__popcll(mt >> p);
+    } else {
+        if (mt) { run.flags |= WIN_TIE; run.tie_off = run.cnt + (63u - (uint32_t)__clzll((long long)mt)); }
+        run.ties += (uint32_t)__popcll(mt);
+        run.cnt += live;
+    }
+}
+
+// 1. heads + the carry of every tile.  keys[c * key_stride + g]: term c's key of gathered entry g.
+__global__ __launch_bounds__(TPB) void k_win_heads(const uint64_t* __restrict__ keys, size_t key_stride, int npart, int nterms, const uint32_t* __restrict__ perm, uint32_t n,
+                                                  uint8_t* __restrict__ heads, WinCarry* __restrict__ carry, uint32_t ntiles) {
+    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return;
+    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    WinCarry run = {0u, 0u, 0u, 0u};
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        const bool live = r < r1;
+        bool ph = false, th = false;
+        if (live) {
+            if (r == 0) ph = th = true;
+            else {
+                const uint32_t g = perm ? perm[r] : (uint32_t)r, h = perm ? perm[r - 1] : (uint32_t)(r - 1);
+                if (g < n && h < n)                                      // (a permutation of [0, n): always)
+                    for (int c = 0; c < nterms; ++c) {
+                        const bool differ = keys[(size_t)c * key_stride + g] != keys[(size_t)c * key_stride + h];
+                        th |= differ;
+                        ph |= differ && c < npart;
+                    }
+            }
+            heads[r] = (uint8_t)((ph ? WIN_PART : 0u) | (th ? WIN_TIE : 0u));
+        }
+        win_step(run, __ballot(ph), __ballot(th), (uint32_t)min((uint64_t)WAVE, r1 - b));
+    }
+    if (lane_id() == 0) carry[w] = run;
+}
+// 2. one workgroup: exclusive scan of the tile carries under win_join, in place (thread t folds a run of consecutive tiles, the runs
+// are scanned in LDS — Hillis-Steele, the operator is not commutative: left operand = lower tiles — and each run is then rewritten)
+__global__ __launch_bounds__(TPB) void k_win_scan(WinCarry* __restrict__ carry, uint32_t ntiles) {
+    __shared__ WinCarry s_c[TPB];
+    const uint32_t per = (ntiles + TPB - 1) / TPB;
+    const uint64_t b0 = (uint64_t)threadIdx.x * per, b1 = min((uint64_t)ntiles, b0 + per);
+    WinCarry sum = {0u, 0u, 0u, 0u};
+    for (uint64_t b = b0; b < b1; ++b) sum = win_join(sum, carry[b]);
+    s_c[threadIdx.x] = sum;
+    __syncthreads();
+    for (int off = 1; off < TPB; off <<= 1) {
+        WinCarry a = {0u, 0u, 0u, 0u};
+        if ((int)threadIdx.x >= off) a = s_c[threadIdx.x - off];
+        __syncthreads();
+        s_c[threadIdx.x] = win_join(a, s_c[threadIdx.x]);
+        __syncthreads();
+    }
+    WinCarry run = {0u, 0u, 0u, 0u};
+    if (threadIdx.x > 0) run = s_c[threadIdx.x - 1];
+    for (uint64_t b = b0; b < b1; ++b) { const WinCarry v = carry[b]; carry[b] = run; run = win_join(run, v); }
+}
+// 3. the rank of `kind` of every position, and per tile the positions with rank <= per_limit
+__global__ __launch_bounds__(TPB) void k_win_rank(const uint8_t* __restrict__ heads, const WinCarry* __restrict__ carry, uint32_t n, int kind, uint64_t per_limit,
+                                                 uint32_t* __restrict__ rank, uint32_t* __restrict__ tile_kept, uint32_t ntiles) {
+    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return;
+    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    WinCarry run = carry[w];
+    uint32_t kept = 0;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const uint32_t f = live ? heads[r] : 0u;
+        const uint64_t mp = __ballot(f & WIN_PART), mt = __ballot(f & WIN_TIE);
+        const uint64_t pl = mp & le, tl = mt & le;
+        uint32_t v;
+        if (pl) {                                                       // the partition starts in this batch, at lane p
+            const uint32_t p = 63u - (uint32_t)__clzll((long long)pl);
+            if (kind == SDQH_WIN_ROW_NUMBER) v = lane - p + 1u;
+            else if (kind == SDQH_WIN_RANK) v = (63u - (uint32_t)__clzll((long long)tl)) - p + 1u;
+            else v = (uint32_t)__popcll(tl >> p);
+        } else {                                                        // ... before it: the carry knows where
+            if (kind == SDQH_WIN_ROW_NUMBER) v = run.cnt + lane + 1u;
+            else if (kind == SDQH_WIN_RANK) v = (tl ? run.cnt + (63u - (uint32_t)__clzll((long long)tl)) : run.tie_off) + 1u;
+            else v = run.ties + (uint32_t)__popcll(tl);
+        }
+        if (live) rank[r] = v;
+        kept += (uint32_t)__popcll(__ballot(live && (uint64_t)v <= per_limit));
+        win_step(run, mp, mt, (uint32_t)min((uint64_t)WAVE, r1 - b));
+    }
+    if (lane == 0) tile_kept[w] = kept;
+}
+// 4. the kept positions, in order: sel[0 .. kept) (tile_off: k_sort_scan of tile_kept); only the first m are asked for
+__global__ __launch_bounds__(TPB) void k_win_place(const uint32_t* __restrict__ rank, uint32_t n, uint64_t per_limit, const uint32_t* __restrict__ tile_off, uint32_t ntiles,
+                                                  uint32_t* __restrict__ sel, uint32_t m) {
+    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return;
+    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    const uint64_t lt = lanemask_lt();
+    uint64_t at0 = tile_off[w];
+    for (uint64_t b = r0; b < r1 && at0 < m; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        const bool keep = r < r1 && (uint64_t)rank[r] <= per_limit;
+        const uint64_t k = __ballot(keep);
+        const uint64_t at = at0 + (uint64_t)__popcll(k & lt);
+        if (keep && at < m) sel[at] = (uint32_t)r;
+        at0 += (uint64_t)__popcll(k);
+    }
+}
+// 5. k_sort_emit through the kept positions (sel == nullptr: every position is kept), with the rank column
+__global__ __launch_bounds__(TPB) void k_win_emit(DevStage st, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ sel,
+                                                 const uint32_t* __restrict__ rank, uint32_t n, uint32_t m, DevSortOut o, int64_t* __restrict__ out_rank) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t i = sel ? sel[j] : (uint32_t)j;
+        if (i >= n) continue;                                            // (kept positions are positions: never taken)
+        const uint32_t g = perm ? perm[i] : i;
+        if (g >= n) continue;
+        const int64_t idx = (int64_t)refs[g];
+        if (o.keys) o.keys[j] = st.key[idx];
+#pragma unroll
+        for (int p = 0; p < SDQH_MAX_PAYLOAD; ++p) if (p < o.npay && o.pay[p]) o.pay[p][j] = st.pay[p][idx];
+#pragma unroll
+        for (int v = 0; v < SDQH_TUPLE_MAX_VALUES; ++v) if (v < o.nval && o.val[v]) o.val[v][j] = st.sacc[(size_t)idx * st.acc_stride + v];
+        if (o.hits) o.hits[j] = st.shits ? (int64_t)st.shits[idx] : 0;
+        if (out_rank) out_rank[j] = (int64_t)rank[i];
+    }
+}
+
 struct Scratch {                                     // pool blocks of one call, returned on every way out
-    sdqh_ctx* ctx; void* p[3] = {nullptr, nullptr, nullptr};
+    sdqh_ctx* ctx; void* p[4] = {nullptr, nullptr, nullptr, nullptr};
     explicit Scratch(sdqh_ctx* c) : ctx(c) {}
     ~Scratch() { for (void* q : p) if (q) pool_free(ctx, q); }
 };
@@ -407,14 +579,22 @@ static void radix_pass(sdqh_ctx* ctx, const uint64_t* key, const uint32_t* perm,
     LAUNCH(ctx, "k_sort_scatter", k_sort_scatter, tgrid, key, perm, n, shift, hist, bin_total, ntiles, out);
 }
 
-// sdqh_table_sorted / sdqh_table_sorted_by behind their argument checks; who: the entry point's name in messages
-static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms,
-                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
-    const std::string me(who);
-    const int nv = table->accumulate ? table->nv : 0;
+// What the first half of an ORDER BY leaves on the device — the references of the selected entries in stage order, the keys of every
+// term beside them, the permutation that orders them (nullptr: stage order is the order) — and what the host knows of it.
+struct SortState {
+    unsigned long long h[SORT_INFO];                 // the info block: n, the AND / OR masks
+    unsigned long long* info = nullptr;
+    uint32_t* refs = nullptr;
+    uint64_t* keys = nullptr;
+    size_t key_stride = 0;
+    const uint32_t* perm = nullptr;
+    int64_t n = 0;
+};
+
+// first half, (a): selection, keys, the info block read (one wait).  Opens the call (call_begin); blocks go to scratch.p[0].
+static int sort_select(sdqh_ctx* ctx, sdqh_table* table, const std::string& me, int64_t min_hits, int nsort, const DevSortTerm* terms, Scratch& scratch, SortState& s) {
     call_begin(ctx);
     if (int rc = index_ensure(ctx, table)) return rc;
-    Scratch scratch(ctx);
     // block 0: [segment offsets | info | references | keys per column], sized for every staged row (the count is the device's)
     const size_t rows = (size_t)std::max<int64_t>(table->nrows_build, 1) + 1;
     const int nseg = table->stage.nseg;
@@ -422,10 +602,10 @@ static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_
     char* blob = static_cast<char*>(scratch.p[0] = pool_alloc(ctx, seg_bytes + info_bytes + ref_bytes + key_bytes * (size_t)nsort));
     if (!blob) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
     uint32_t* seg_off = reinterpret_cast<uint32_t*>(blob);
-    unsigned long long* info = reinterpret_cast<unsigned long long*>(blob + seg_bytes);
-    uint32_t* refs = reinterpret_cast<uint32_t*>(blob + seg_bytes + info_bytes);
-    uint64_t* keys = reinterpret_cast<uint64_t*>(blob + seg_bytes + info_bytes + ref_bytes);
-    const size_t key_stride = key_bytes / 8;
+    unsigned long long* info = s.info = reinterpret_cast<unsigned long long*>(blob + seg_bytes);
+    uint32_t* refs = s.refs = reinterpret_cast<uint32_t*>(blob + seg_bytes + info_bytes);
+    uint64_t* keys = s.keys = reinterpret_cast<uint64_t*>(blob + seg_bytes + info_bytes + ref_bytes);
+    const size_t key_stride = s.key_stride = key_bytes / 8;
     const uint32_t mh = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_hits, 0), 0xFFFFFFFFll);
     const unsigned seg_grid = (unsigned)std::max(1, (nseg + TPB / WAVE - 1) / (TPB / WAVE));
     LAUNCH(ctx, "k_sort_count", k_sort_count, seg_grid, table->dev, table->stage, mh, seg_off);
@@ -438,83 +618,174 @@ static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_
     }
     HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, info, SORT_INFO * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
-    unsigned long long h[SORT_INFO];
-    std::memcpy(h, ctx->result_host, sizeof(h));
-    if (h[SORT_INFO_BAD]) {                                           // before anything is written, *out_n included
+    std::memcpy(s.h, ctx->result_host, sizeof(s.h));
+    if (s.h[SORT_INFO_BAD]) {                                         // before anything is written, *out_n included
         int c = 0;
-        while (c < nsort - 1 && !((h[SORT_INFO_BAD] >> c) & 1ull)) ++c;
+        while (c < nsort - 1 && !((s.h[SORT_INFO_BAD] >> c) & 1ull)) ++c;
         call_end(ctx);
         return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(c) + " derives a field outside its ranks column (" + std::to_string((long long)terms[c].nranks) + " rows)");
     }
-    const int64_t n = (int64_t)h[0], m = std::min<int64_t>(limit, n);
-    *out_n = m;
-    if (!out_keys && !out_payload && !out_values && !out_hits) { call_end(ctx); return SDQH_OK; }      // count-only call
-    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
-    if (m == 0) { call_end(ctx); return SDQH_OK; }
-    // the passes: last column first, low digit first; a digit whose bits are the same in every key orders nothing
+    s.n = (int64_t)s.h[0];
+    return SDQH_OK;
+}
+
+// first half, (b): the passes (n >= 1) — last column first, low digit first; a digit whose bits are the same in every key orders
+// nothing.  Leaves s.perm; block 1 = [permutation x 2 | digit counts per tile | digit totals] goes to scratch.p[1].
+static int sort_passes(sdqh_ctx* ctx, const std::string& me, int nsort, Scratch& scratch, SortState& s) {
+    const int64_t n = s.n;
     int pass_col[8 * SDQH_SORT_MAX_KEYS], pass_shift[8 * SDQH_SORT_MAX_KEYS], npass = 0;
     if (n > 1) for (int c = nsort - 1; c >= 0; --c) {
-        const uint64_t vary = h[1 + SDQH_SORT_MAX_KEYS + c] & ~h[1 + c];
+        const uint64_t vary = s.h[1 + SDQH_SORT_MAX_KEYS + c] & ~s.h[1 + c];
         for (int shift = 0; shift < 64; shift += 8) if ((vary >> shift) & 255ull) { pass_col[npass] = c; pass_shift[npass] = shift; ++npass; }
     }
-    // block 1: [permutation x 2 | digit counts per tile | digit totals]; block 2: the result rows
-    const uint32_t un = (uint32_t)n, um = (uint32_t)m;
+    const uint32_t un = (uint32_t)n;
     const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
     const bool small = n <= SORT_SMALL;
-    const uint32_t* perm = nullptr;
+    s.perm = nullptr;
     if (npass) {
         const size_t perm_bytes = round_up((size_t)n * 4), hist_bytes = small ? 0 : round_up((size_t)ntiles * 256 * 4);
         char* b1 = static_cast<char*>(scratch.p[1] = pool_alloc(ctx, perm_bytes * (small ? 1 : 2) + hist_bytes + 1024));
         if (!b1) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         uint32_t* pa = reinterpret_cast<uint32_t*>(b1);
         if (small) {
-            LAUNCH(ctx, "k_sort_small", k_sort_small, 1, keys, key_stride, nsort, un, info, pa);
-            perm = pa;
+            LAUNCH(ctx, "k_sort_small", k_sort_small, 1, s.keys, s.key_stride, nsort, un, s.info, pa);
+            s.perm = pa;
         } else {
             uint32_t* pb = reinterpret_cast<uint32_t*>(b1 + perm_bytes);
             uint32_t* hist = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes);
             uint32_t* bin_total = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes + hist_bytes);
             for (int p = 0; p < npass; ++p) {
-                radix_pass(ctx, keys + (size_t)pass_col[p] * key_stride, perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
-                perm = pa; std::swap(pa, pb);
+                radix_pass(ctx, s.keys + (size_t)pass_col[p] * s.key_stride, s.perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
+                s.perm = pa; std::swap(pa, pb);
             }
         }
     }
-    const int npay = out_payload ? table->npay : 0, nval = out_values ? nv : 0;
-    const int narr = (out_keys ? 1 : 0) + npay + nval + (out_hits ? 1 : 0);
-    const size_t nb = (size_t)m * 8, need = nb * (size_t)narr;
-    if (narr) {
-        char* dev = static_cast<char*>(scratch.p[2] = pool_alloc(ctx, need + 64));
-        if (!dev) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        DevSortOut o; std::memset(&o, 0, sizeof(o));
-        size_t at = 0;
-        if (out_keys) { o.keys = reinterpret_cast<int64_t*>(dev + at); at += nb; }
-        for (int p = 0; p < npay; ++p) { o.pay[p] = reinterpret_cast<int64_t*>(dev + at); at += nb; }
-        for (int v = 0; v < nval; ++v) { o.val[v] = reinterpret_cast<double*>(dev + at); at += nb; }
-        if (out_hits) { o.hits = reinterpret_cast<int64_t*>(dev + at); at += nb; }
-        o.npay = npay; o.nval = nval;
-        const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-        LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, refs, perm, un, um, o);
-        call_end(ctx);
-        // the rows land in pinned memory in one copy (a copy into pageable memory is several times slower), then one memcpy per array
-        if (need > ctx->bulk_bytes && need <= ((size_t)1 << 30)) {
-            if (ctx->bulk_host) (void)hipHostFree(ctx->bulk_host);
-            ctx->bulk_host = nullptr; ctx->bulk_bytes = 0;
-            const size_t want = std::max<size_t>(need * 2, (size_t)8 << 20);
-            if (hipHostMalloc(&ctx->bulk_host, want, hipHostMallocDefault) == hipSuccess) ctx->bulk_bytes = want; else (void)hipGetLastError();
-        }
-        const bool pinned = need <= ctx->bulk_bytes;
-        int64_t* dst[2 + SDQH_MAX_PAYLOAD + SDQH_TUPLE_MAX_VALUES]; int nd = 0;
-        if (out_keys) dst[nd++] = out_keys;
-        for (int p = 0; p < npay; ++p) dst[nd++] = out_payload + (size_t)p * (size_t)capacity;
-        for (int v = 0; v < nval; ++v) dst[nd++] = reinterpret_cast<int64_t*>(out_values + (size_t)v * (size_t)capacity);
-        if (out_hits) dst[nd++] = out_hits;
-        if (pinned) HIP_TRYS(ctx, hipMemcpyAsync(ctx->bulk_host, dev, need, hipMemcpyDeviceToHost, ctx->stream));
-        else for (int a = 0; a < nd; ++a) HIP_TRYS(ctx, hipMemcpyAsync(dst[a], dev + (size_t)a * nb, nb, hipMemcpyDeviceToHost, ctx->stream));
-        if (int rc = sync_stream(ctx)) return rc;
-        if (pinned) for (int a = 0; a < nd; ++a) std::memcpy(dst[a], static_cast<const char*>(ctx->bulk_host) + (size_t)a * nb, nb);
+    return SDQH_OK;
+}
+
+// second half: the arrays of a result of m rows on the device (block 2: scratch.p[2]; each array m x 8 bytes, in the order keys,
+// payload columns, value columns, hits, extra) ...
+struct SortRows { char* dev = nullptr; DevSortOut o; int64_t* extra = nullptr; int npay = 0, nval = 0, narr = 0; size_t nb = 0, need = 0; };
+static int sort_rows_alloc(sdqh_ctx* ctx, sdqh_table* table, const std::string& me, int64_t m, bool keys, bool payload, bool values, bool hits, bool extra, Scratch& scratch, SortRows& r) {
+    const int nv = table->accumulate ? table->nv : 0;
+    r.npay = payload ? table->npay : 0; r.nval = values ? nv : 0;
+    r.narr = (keys ? 1 : 0) + r.npay + r.nval + (hits ? 1 : 0) + (extra ? 1 : 0);
+    r.nb = (size_t)m * 8; r.need = r.nb * (size_t)r.narr;
+    std::memset(&r.o, 0, sizeof(r.o));
+    if (!r.narr) return SDQH_OK;
+    char* dev = r.dev = static_cast<char*>(scratch.p[2] = pool_alloc(ctx, r.need + 64));
+    if (!dev) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+    size_t at = 0;
+    if (keys) { r.o.keys = reinterpret_cast<int64_t*>(dev + at); at += r.nb; }
+    for (int p = 0; p < r.npay; ++p) { r.o.pay[p] = reinterpret_cast<int64_t*>(dev + at); at += r.nb; }
+    for (int v = 0; v < r.nval; ++v) { r.o.val[v] = reinterpret_cast<double*>(dev + at); at += r.nb; }
+    if (hits) { r.o.hits = reinterpret_cast<int64_t*>(dev + at); at += r.nb; }
+    if (extra) { r.extra = reinterpret_cast<int64_t*>(dev + at); at += r.nb; }
+    r.o.npay = r.npay; r.o.nval = r.nval;
+    return SDQH_OK;
+}
+// ... and their way to the caller's arrays (after call_end; waits for the stream)
+static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_extra) {
+    const size_t nb = r.nb, need = r.need;
+    // the rows land in pinned memory in one copy (a copy into pageable memory is several times slower), then one memcpy per array
+    if (need > ctx->bulk_bytes && need <= ((size_t)1 << 30)) {
+        if (ctx->bulk_host) (void)hipHostFree(ctx->bulk_host);
+        ctx->bulk_host = nullptr; ctx->bulk_bytes = 0;
+        const size_t want = std::max<size_t>(need * 2, (size_t)8 << 20);
+        if (hipHostMalloc(&ctx->bulk_host, want, hipHostMallocDefault) == hipSuccess) ctx->bulk_bytes = want; else (void)hipGetLastError();
     }
-    if (out_values) for (int v = nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, nb);
+    const bool pinned = need <= ctx->bulk_bytes;
+    int64_t* dst[3 + SDQH_MAX_PAYLOAD + SDQH_TUPLE_MAX_VALUES]; int nd = 0;
+    if (out_keys) dst[nd++] = out_keys;
+    for (int p = 0; p < r.npay; ++p) dst[nd++] = out_payload + (size_t)p * (size_t)capacity;
+    for (int v = 0; v < r.nval; ++v) dst[nd++] = reinterpret_cast<int64_t*>(out_values + (size_t)v * (size_t)capacity);
+    if (out_hits) dst[nd++] = out_hits;
+    if (out_extra) dst[nd++] = out_extra;
+    if (pinned) HIP_TRYS(ctx, hipMemcpyAsync(ctx->bulk_host, r.dev, need, hipMemcpyDeviceToHost, ctx->stream));
+    else for (int a = 0; a < nd; ++a) HIP_TRYS(ctx, hipMemcpyAsync(dst[a], r.dev + (size_t)a * nb, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    if (pinned) for (int a = 0; a < nd; ++a) std::memcpy(dst[a], static_cast<const char*>(ctx->bulk_host) + (size_t)a * nb, nb);
+    return SDQH_OK;
+}
+
+// sdqh_table_sorted / sdqh_table_sorted_by behind their argument checks; who: the entry point's name in messages
+static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms,
+                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    const std::string me(who);
+    Scratch scratch(ctx);
+    SortState s;
+    if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;
+    const int64_t n = s.n, m = std::min<int64_t>(limit, n);
+    *out_n = m;
+    if (!out_keys && !out_payload && !out_values && !out_hits) { call_end(ctx); return SDQH_OK; }      // count-only call
+    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
+    if (m == 0) { call_end(ctx); return SDQH_OK; }
+    if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
+    SortRows r;
+    if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, false, scratch, r)) return rc;
+    if (r.narr) {
+        const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+        LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, (uint32_t)n, (uint32_t)m, r.o);
+        call_end(ctx);
+        if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, nullptr)) return rc;
+    }
+    if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
+    return SDQH_OK;
+}
+
+// sdqh_table_window behind its argument checks
+static int window_impl(sdqh_ctx* ctx, sdqh_table* table, int64_t min_hits, int npart, int nsort, const DevSortTerm* terms, int kind, int64_t per_limit, int64_t limit,
+                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_rank, int64_t* out_n) {
+    const std::string me("table_window");
+    Scratch scratch(ctx);
+    SortState s;
+    if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;
+    const int64_t n = s.n;
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank;
+    const bool all_kept = per_limit >= n;                            // a rank is at most n: nothing to filter
+    if (n == 0 || (count_only && all_kept)) { *out_n = std::min<int64_t>(limit, n); call_end(ctx); return SDQH_OK; }
+    if (all_kept && std::min<int64_t>(limit, n) > capacity) { *out_n = std::min<int64_t>(limit, n); call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
+    if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
+    // block 3: [heads | tile carries | ranks | kept per tile | kept positions]
+    const uint32_t un = (uint32_t)n;
+    const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    const size_t head_bytes = round_up((size_t)n), carry_bytes = round_up((size_t)ntiles * sizeof(WinCarry)), rank_bytes = round_up((size_t)n * 4), kept_bytes = round_up((size_t)ntiles * 4);
+    char* b3 = static_cast<char*>(scratch.p[3] = pool_alloc(ctx, head_bytes + carry_bytes + rank_bytes + kept_bytes + (all_kept ? 0 : rank_bytes) + 256));
+    if (!b3) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+    uint8_t* heads = reinterpret_cast<uint8_t*>(b3);
+    WinCarry* carry = reinterpret_cast<WinCarry*>(b3 + head_bytes);
+    uint32_t* rank = reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes);
+    uint32_t* tile_kept = reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes + rank_bytes);
+    uint32_t* sel = all_kept ? nullptr : reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes + rank_bytes + kept_bytes);
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    const uint64_t pl = (uint64_t)per_limit;
+    LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, npart, nsort, s.perm, un, heads, carry, ntiles);
+    LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+    LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, kind, pl, rank, tile_kept, ntiles);
+    int64_t kept = n;
+    if (!all_kept) {
+        LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
+        HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (int rc = sync_stream(ctx)) return rc;
+        unsigned long long k0;
+        std::memcpy(&k0, ctx->result_host, 8);
+        kept = (int64_t)k0;
+    }
+    const int64_t m = std::min<int64_t>(limit, kept);
+    *out_n = m;
+    if (count_only) { call_end(ctx); return SDQH_OK; }
+    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
+    if (m == 0) { call_end(ctx); return SDQH_OK; }
+    const uint32_t um = (uint32_t)m;
+    if (!all_kept) LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, um);
+    SortRows r;
+    if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, out_rank != nullptr, scratch, r)) return rc;
+    if (!r.narr) { call_end(ctx); return SDQH_OK; }                  // (only columns the table does not have were asked for)
+    const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+    LAUNCH(ctx, "k_win_emit", k_win_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, um, r.o, r.extra);
+    call_end(ctx);
+    if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
+    if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
     return SDQH_OK;
 }
 
@@ -545,6 +816,22 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits,
     return sorted_impl(ctx, table, "table_sorted", min_hits, limit, nsort, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+// the terms of sdqh_table_sorted_by / sdqh_table_window checked and marshalled; SDQH_OK or the failed call's code
+static int sort_terms_set(sdqh_ctx* ctx, const sdqh_table* table, const std::string& me, int nterms, const sdqh_sort_term* in, DevSortTerm* terms) {
+    for (int i = 0; i < nterms; ++i) {
+        const sdqh_sort_term& t = in[i];
+        if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " names a field the table does not have");
+        sort_column_set(terms[i].sk, t.kind, t.index, t.descending, t.is_f64);
+        if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " has a negative divisor or modulus");
+        if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + ": ranks must be an I64 column");
+        terms[i].div = (uint64_t)t.div; terms[i].mod = (uint64_t)t.mod; terms[i].add = t.add;
+        terms[i].ranks = t.ranks ? static_cast<const int64_t*>(t.ranks->data) : nullptr;
+        terms[i].nranks = t.ranks ? t.ranks->nrows : 0;
+        if (term_derived(terms[i]) && terms[i].sk.is_f64) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " derives from a double");
+    }
+    return SDQH_OK;
+}
+
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
                          int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     sdqh_table* table = const_cast<sdqh_table*>(ctable);
@@ -554,18 +841,29 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hi
     if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted_by: bitmap-only table");
     (void)hipSetDevice(ctx->device);
     DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
-    for (int i = 0; i < nterms; ++i) {
-        const sdqh_sort_term& t = in[i];
-        if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " names a field the table does not have");
-        sort_column_set(terms[i].sk, t.kind, t.index, t.descending, t.is_f64);
-        if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " has a negative divisor or modulus");
-        if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + ": ranks must be an I64 column");
-        terms[i].div = (uint64_t)t.div; terms[i].mod = (uint64_t)t.mod; terms[i].add = t.add;
-        terms[i].ranks = t.ranks ? static_cast<const int64_t*>(t.ranks->data) : nullptr;
-        terms[i].nranks = t.ranks ? t.ranks->nrows : 0;
-        if (term_derived(terms[i]) && terms[i].sk.is_f64) return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: term " + std::to_string(i) + " derives from a double");
-    }
+    if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, terms)) return rc;
     return sorted_impl(ctx, table, "table_sorted_by", min_hits, limit, nterms, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                      int kind, int64_t per_limit, int64_t limit, int64_t capacity,
+                      int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_rank, int64_t* out_n) {
+    sdqh_table* table = const_cast<sdqh_table*>(ctable);
+    if (!ctx || !table || !out_n || !in || nterms < 1 || nterms > SDQH_SORT_MAX_KEYS || npartition < 0 || npartition > nterms || per_limit < 1 || limit < 1 || capacity < 0 ||
+        (kind != SDQH_WIN_ROW_NUMBER && kind != SDQH_WIN_RANK && kind != SDQH_WIN_DENSE_RANK))
+        return fail(ctx, SDQH_ERR_INVALID, "table_window: bad arguments");
+    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_window: compile-only context");
+    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_window: bitmap-only table");
+    (void)hipSetDevice(ctx->device);
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
+    if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, terms)) return rc;
+    return window_impl(ctx, table, min_hits, npartition, nterms, terms, kind, per_limit, limit, capacity, out_keys, out_payload, out_values, out_hits, out_rank, out_n);
+}
+
+int sdqh_window_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
+    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_geometry: bad arguments");
+    *tile_rows = SORT_TILE;
+    return SDQH_OK;
 }
 
 int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_column** out_ranks, int64_t* out_distinct) {

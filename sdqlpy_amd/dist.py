@@ -57,6 +57,14 @@ from .result import ResultSet
 _COLL_ON_RECORDED_STREAM = os.environ.get("SDQLPY_AMD_DIST_COLL_ON_RECORDED_STREAM") == "1"
 
 
+def refuse_window(top):
+    """ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest) is a single-GPU operation: a partition's rows may lie on
+    several ranks, and ranking them takes an exchange by partition key that the runner does not have."""
+    from .result import WindowRequest
+    if isinstance(top, WindowRequest):
+        raise frontend.UnsupportedQuery("top_per / numbered run on one GPU: the multi-GPU runner has no exchange by partition key")
+
+
 class DistributedRunner:
     def __init__(self, eng, rank, world, group=None, device=None, partition="auto", prefilter=True, skip_trivial=None, device_sized=None):
         self.eng, self.ctx = eng, eng.ctx
@@ -545,6 +553,7 @@ class DistributedRunner:
         # that same stream only, behind the kernels queued there that still read it, and a tensor a collective used on RCCL's own
         # stream carries torch's record_stream mark (TORCH_NCCL_AVOID_RECORD_STREAMS=1 would void that: refused in _device_order)
         self._inflight.clear()
+        refuse_window(top)
         fn, plan, args = self._resolve(query, db)
         whole = self._whole_params(fn, plan, args, whole_tables)
         shape = self._shape(plan)

@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import DeferredResultSet, Pending, DictResult, ResultSet, TextRefs, decode_text
+from .result import WINDOW_KINDS, DeferredResultSet, Pending, DictResult, ResultSet, TextRefs, WindowRequest, decode_text
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
 TUPLE_SHAPES = {
@@ -160,6 +160,9 @@ class Engine:
         # order_routes: per result finalised with an ORDER BY where it was ordered — {"route": "topk" | "sorted" | "sorted_by" | "host",
         # "ranked": the order columns that went through a rank table} (the last 256)
         self.order_routes = collections.deque(maxlen=256)
+        # ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest) ranks on the device where the library has the window
+        # extension (abi.Context.table_window) — route "window", noted with the extra keys "per", "kind", "per_limit"
+        self.device_window = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1680,8 +1683,81 @@ def _derived(spec):
 
 
 def _note_order_route(eng, top, spec, route):
-    eng.order_routes.append({"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-                             "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route == "sorted_by" and len(t) > 4 and t[7] is not None]})
+    note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window") and len(t) > 4 and t[7] is not None]}
+    if isinstance(top, WindowRequest):                       # "order": the ORDER BY names alone; the PARTITION BY names are "per"
+        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+        note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
+    eng.order_routes.append(note)
+
+
+class _Ranked:
+    """What `ordered` is for rows that came back from the device's window call: true, and the rank of every row."""
+    __slots__ = ("rank",)
+
+    def __init__(self, rank):
+        self.rank = rank
+
+    def __bool__(self):
+        return True
+
+
+def _window_on(eng):
+    return eng is not None and bool(getattr(eng, "device_window", True)) and bool(getattr(eng.ctx.library, "has_window", False))
+
+
+def _windowed(eng, table, min_hits, hint_key, top, spec, want_hits):
+    """top_per / numbered on the device in one waited-for call (abi.Context.table_window): text terms through their resident ranks
+    column as in _sorted_by, the arrays sized from the previous run of the same plan step."""
+    terms = [t if len(t) == 4 or t[7] is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
+    hint = eng.compact_hints.get(("window", hint_key))
+    cap = 4096 if hint is None else hint + hint // 8 + 1024
+    keys, payload, values, hits, rank = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL),
+                                                             min(int(top[0]), abi.SORT_ALL), cap, want_hits=want_hits, want_rank=top.name is not None)
+    eng.compact_hints[("window", hint_key)] = len(keys)
+    return keys, payload, values, hits, rank
+
+
+def _host_top(rs, top):
+    """ORDER BY ... LIMIT (per group) of a result set on the host."""
+    return rs.windowed(top) if isinstance(top, WindowRequest) else rs.top(top[0], top[1])
+
+
+def _finish_top(rs, ordered, top):
+    """A result set whose rows the device may have ordered already (`ordered`) finished with `top`."""
+    if top is None:
+        return rs
+    if not ordered:
+        return _host_top(rs, top)
+    if isinstance(top, WindowRequest) and top.name is not None:
+        if top.name in rs.columns:
+            raise KeyError("window: the result already has a column %r" % top.name)
+        return ResultSet(rs.columns + [top.name], list(rs._cols) + [np.asarray(ordered.rank)])
+    return rs
+
+
+def result_columns(plan):
+    """The column names of the record set a plan ends in, read off its last loop — or None where they are only known once it ran."""
+    ops = {op.out: op for op in plan.ops}
+    op = ops.get(plan.result)
+
+    def sides(o):
+        o = _as_plain_op(o) if o is not None else None
+        key, val = getattr(o, "key", None), getattr(o, "val", None)
+        if not isinstance(key, RecordCons):
+            return None
+        if isinstance(val, RecordCons):
+            return [n for n, _ in key.fields] + [n for n, _ in val.fields]
+        return [n for n, _ in key.fields] if isinstance(val, Const) and val.value is True else None
+    if isinstance(op, WrapScalarOp):
+        return [n for n, _ in op.fields]
+    if isinstance(op, FinalizeOp):
+        if op.fields is not None:
+            return [spec[0] for spec in op.fields]
+        return sides(ops.get(op.source))
+    if isinstance(op, HostDictOp) and isinstance(op.val, Const) and op.val.value is True:
+        return sides(op)
+    return None
 
 
 def _device_sorts(eng, top, spec):
@@ -1719,6 +1795,10 @@ def _fetch_ordered(eng, bt_table, min_hits, hint_key, top, spec, want_hits):
     hits), or None — the caller compacts and the host orders.  Which way it went is noted in Engine.order_routes."""
     if top is None:
         return None
+    if isinstance(top, WindowRequest):                       # never topk / sorted / sorted_by: those know nothing of partitions
+        route = "window" if spec is not None and 1 <= len(spec) <= abi.SORT_MAX_KEYS and _window_on(eng) and (not _derived(spec) or _sort_terms_on(eng)) else "host"
+        _note_order_route(eng, top, spec, route)
+        return _windowed(eng, bt_table, min_hits, hint_key, top, spec, want_hits) if route == "window" else None
     route = "host"
     if _derived(spec):
         if top[0] >= 1 and len(spec) <= abi.SORT_MAX_KEYS and _sort_terms_on(eng):
@@ -1742,7 +1822,7 @@ def _fetch_entries(eng, bt_table, min_hits, hint_key, top, spec, **want):
     when the device can order them (spec) — otherwise all, ordered afterwards on the host."""
     got = _fetch_ordered(eng, bt_table, min_hits, hint_key, top, spec, want.get("want_hits", True))
     if got is not None:
-        return got[0], got[1], got[2], got[3], True
+        return got[0], got[1], got[2], got[3], (_Ranked(got[4]) if len(got) > 4 else True)
     keys, payload, values, hits = _compact(eng, bt_table, min_hits, hint_key, **want)
     return keys, payload, values, hits, False
 
@@ -1884,7 +1964,7 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             return d
         sel = None
         by_name = dict(numeric); by_name.update(dict(vf))
-        if top is not None and all(nm in by_name for nm, _ in top[1]):
+        if top is not None and not isinstance(top, WindowRequest) and all(nm in by_name for nm, _ in top[1]):
             sel = ResultSet([nm for nm, _ in top[1]], [by_name[nm] for nm, _ in top[1]]).top_index(top[0], top[1])
             vf = [(nm, a[sel]) for nm, a in vf]
         d = DictResult([(f, (numeric[f] if sel is None else numeric[f][sel]) if f in numeric else decode(f, src, sel)) for f, src in out_key_fields],
@@ -1897,7 +1977,7 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         got = _fetch_ordered(eng, value.table, 0, hint_key, top, spec, False)
         if got is not None:
             keys, payload = got[0], got[1]
-            ordered = True
+            ordered = _Ranked(got[4]) if len(got) > 4 else True
         else:
             keys, payload, _, _ = _compact(eng, value.table, 0, hint_key, want_values=False, want_hits=False)
             ordered = False
@@ -1935,13 +2015,16 @@ def _finalize(eng, op, env, top=None):
                 names[name] = spec[2]
             elif len(side) == 1:
                 names[name] = side[0]
-        inner_top = (top[0], [(names.get(n, n), d) for n, d in top[1]])
+        inner_order = [(names.get(n, n), d) for n, d in top[1]]
+        inner_top = top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order)
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
         route = eng.order_routes[-1]
         ranked = {i for i, (nm, _) in enumerate(inner_top[1]) if nm in route["ranked"]}
         route["order"], route["ranked"] = [nm for nm, _ in top[1]], [nm for i, (nm, _) in enumerate(top[1]) if i in ranked]
+        if isinstance(top, WindowRequest):
+            route["order"], route["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)
@@ -1966,9 +2049,7 @@ def _shape_result(op, d, top):
                 raise UnsupportedQuery("line %d: p[%d] is a record; name a field or use concat" % (op.lineno, which))
             fields.append((name, src[0][1]))
     rs = ResultSet([n for n, _ in fields], [a for _, a in fields], ready=getattr(d, "ready", None))
-    if top is not None and not getattr(d, "ordered", False):
-        rs = rs.top(top[0], top[1])
-    return rs
+    return _finish_top(rs, getattr(d, "ordered", False), top)
 
 
 def _as_plain_op(op):
@@ -2054,7 +2135,7 @@ def _host_dict(eng, op, env, is_result):
     top = env.get("__top__") if is_result else None
     if top is not None and isinstance(out, ResultSet):
         _note_order_route(eng, top, None, "host")          # (the loop ran on the host: so does its ORDER BY)
-        out = out.top(top[0], top[1])
+        out = _host_top(out, top)
     return out
 
 
@@ -2155,9 +2236,7 @@ def _record_set(eng, op, bt, env):
         d = _materialize(eng, bt, env, hint_key=(id(op), 1), top=top)
         cols = dict(d.key_fields); cols.update(dict(d.val_fields))
         out = ResultSet(list(bt.record_order), [cols[nm] for nm in bt.record_order])
-        if top is not None and not getattr(d, "ordered", False):
-            out = out.top(top[0], top[1])
-        return out
+        return _finish_top(out, getattr(d, "ordered", False), top)
     finally:
         bt.table.free()
 
@@ -2575,7 +2654,8 @@ class PreparedPlan:
         running the plan again here with every call waited for): the multi-GPU runner's collective re-run."""
         env = dict(env_extra) if env_extra else {}                  # (env_extra: hooks of the multi-GPU runner, "__group_fold__")
         if top is not None:
-            env["__top__"] = (int(top[0]), [(str(n), str(d)) for n, d in top[1]])
+            order = [(str(n), str(d)) for n, d in top[1]]
+            env["__top__"] = top.renamed(order) if isinstance(top, WindowRequest) else (int(top[0]), order)
             if any(d not in ("asc", "desc") for _, d in env["__top__"][1]):
                 raise ValueError("top: directions are 'asc' or 'desc'")
         if deferred and top is None and self.defer_names and getattr(self.eng, "deferred_results", False) and not self.eng.ctx._profiling:
@@ -2609,7 +2689,7 @@ class PreparedPlan:
                 if isinstance(res, DictResult) and not res.val_fields:      # {record: True}: a set of records, the reference's result container
                     res = ResultSet([n for n, _ in res.key_fields], [a for _, a in res.key_fields])
                     if top is not None:
-                        res = res.top(env["__top__"][0], env["__top__"][1])
+                        res = _host_top(res, env["__top__"])
             if top is not None and not isinstance(res, ResultSet):
                 raise UnsupportedQuery("top(k) applies to queries that end in a result set")
             return res

@@ -71,6 +71,78 @@ def decode_text(refs, decoder):
     return TextRefs(refs, decoder) if len(refs) >= LAZY_TEXT_ROWS else np.asarray(decoder)[refs]
 
 
+WINDOW_KINDS = ("row_number", "rank", "dense_rank")      # their positions are abi.WIN_ROW_NUMBER / WIN_RANK / WIN_DENSE_RANK
+WINDOW_ALL = 1 << 62                                      # abi.SORT_ALL: no limit
+
+
+class WindowRequest(tuple):
+    """ORDER BY ... LIMIT per group, travelling where a (k, order) of `top` travels: [0] = the limit on the whole result, [1] = the
+    PARTITION BY terms followed by the ORDER BY terms — code that only orders reads it as a plain `top` — and beside them how many of
+    the terms partition (npartition), the rank wanted (kind: a position in WINDOW_KINDS), the largest rank kept (per_limit) and the
+    name of the rank column the result gets (None: none)."""
+
+    def __new__(cls, k, terms, npartition, kind, per_limit, name=None):
+        self = tuple.__new__(cls, (int(k), [(str(n), str(d)) for n, d in terms]))
+        self.npartition, self.kind, self.per_limit, self.name = int(npartition), int(kind), int(per_limit), name
+        if not 0 <= self.npartition <= len(self[1]) or self.kind not in (0, 1, 2):
+            raise ValueError("window: bad partition count or kind")
+        return self
+
+    by = property(lambda self: self[1][:self.npartition])
+    order = property(lambda self: self[1][self.npartition:])
+
+    def renamed(self, terms):
+        """The same request over other column names (aliases of the same columns, term for term)."""
+        return WindowRequest(self[0], terms, self.npartition, self.kind, self.per_limit, self.name)
+
+
+def window_request(columns, by, order, kind, per_limit, k=WINDOW_ALL, name=None):
+    """The checked WindowRequest of top_per / numbered: by = names or (name, "asc" | "desc"), order = [(name, "asc" | "desc")], kind a
+    name of WINDOW_KINDS.  columns: the result's column names when they are known (None: checked when the result is).  KeyError for a
+    column the result lacks or a rank column it has already, ValueError for everything else."""
+    if kind not in WINDOW_KINDS:
+        raise ValueError("window: kind is one of %s, not %r" % (", ".join(WINDOW_KINDS), kind))
+    if int(per_limit) < 1 or int(k) < 1:
+        raise ValueError("window: k must be at least 1")
+    terms = [(b, "asc") if isinstance(b, str) else (b[0], b[1]) for b in by]
+    npartition = len(terms)
+    terms += [(o, "asc") if isinstance(o, str) else (o[0], o[1]) for o in order]
+    if any(d not in ("asc", "desc") for _, d in terms):
+        raise ValueError("window: directions are 'asc' or 'desc'")
+    if not terms:
+        raise ValueError("window: nothing to partition or order by")
+    if name is not None and not isinstance(name, str):
+        raise ValueError("window: the rank column's name is a string")
+    req = WindowRequest(k, terms, npartition, WINDOW_KINDS.index(kind), min(int(per_limit), WINDOW_ALL), name)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
+
+
+def check_window_columns(req, columns):
+    for nm, _ in req[1]:
+        if nm not in columns:
+            raise KeyError("window: the result has no column %r" % nm)
+    if req.name is not None and req.name in columns:
+        raise KeyError("window: the result already has a column %r" % req.name)
+
+
+def order_image(a, descending):
+    """The order-preserving unsigned 64-bit image of a column under the total order of the device's ORDER BY (sdqh_sort.h): integers
+    as signed values, doubles by sign and magnitude through their bits (-0.0 before +0.0, NaNs by their bits), text by its dense rank
+    (numpy's order of '<U' arrays); a descending column is the complement.  Equal images <=> equal values under that order."""
+    a = np.asarray(a)
+    top = np.uint64(1) << np.uint64(63)
+    if a.dtype.kind == "f":
+        u = np.ascontiguousarray(a, np.float64).view(np.uint64)
+        u = np.where(u >> np.uint64(63) != 0, ~u, u | top)
+    else:
+        if a.dtype.kind not in "iub":                        # text (or anything else numpy orders): its dense rank
+            a = np.unique(a, return_inverse=True)[1].reshape(-1)
+        u = np.ascontiguousarray(a, np.int64).view(np.uint64) ^ top
+    return ~u if descending else u
+
+
 class ResultSet:
     """Set of records: {record(field...): True}."""
 
@@ -154,6 +226,67 @@ class ResultSet:
             keys.append(a)
         idx = np.lexsort(keys) if keys else np.arange(self._n)         # lexsort is stable
         return idx[:max(0, int(k))]
+
+    def window_index(self, by, order, kind, per_limit, k=WINDOW_ALL):
+        """Ranks inside partitions on the host, what sdqh_table_window does on the device (include/sdqh_sort_window.h): rows ordered by
+        `by` then `order` (names or (name, "asc" | "desc")), ties in stored row order; a partition = rows equal in every `by` column,
+        a tie = rows equal in every column, both under the device's total order (order_image: -0.0 != +0.0, NaNs equal bit for
+        bit).  kind: a name of WINDOW_KINDS (or its position).  Returns (indices of the first k rows whose rank is <= per_limit, in
+        order; their ranks, int64).  Used for results that are not device tables."""
+        kind = WINDOW_KINDS.index(kind) if isinstance(kind, str) else int(kind)
+        if kind not in (0, 1, 2):
+            raise ValueError("window: unknown kind")
+        if int(per_limit) < 1 or int(k) < 1:
+            raise ValueError("window: k must be at least 1")
+        terms = [(b, "asc") if isinstance(b, str) else (b[0], b[1]) for b in by]
+        npartition = len(terms)
+        terms += [(o, "asc") if isinstance(o, str) else (o[0], o[1]) for o in order]
+        images = []
+        for name, direction in terms:
+            if name not in self.columns:
+                raise KeyError("window: the result has no column %r" % name)
+            if direction not in ("asc", "desc"):
+                raise ValueError("window: directions are 'asc' or 'desc'")
+            images.append(order_image(self.column(name), direction == "desc"))
+        n = self._n
+        idx = np.lexsort(images[::-1]) if images else np.arange(n)      # lexsort is stable: ties keep the stored order
+        if n == 0:
+            return idx[:0], np.zeros(0, np.int64)
+        part_head = np.zeros(n, bool)
+        tie_head = np.zeros(n, bool)
+        part_head[0] = tie_head[0] = True
+        for i, u in enumerate(images):
+            differ = u[idx][1:] != u[idx][:-1]
+            tie_head[1:] |= differ
+            if i < npartition:
+                part_head[1:] |= differ
+        pos = np.arange(n, dtype=np.int64)
+        part_start = np.maximum.accumulate(np.where(part_head, pos, 0))
+        if kind == 0:
+            rank = pos - part_start + 1
+        elif kind == 1:
+            rank = np.maximum.accumulate(np.where(tie_head, pos, 0)) - part_start + 1
+        else:
+            heads = np.cumsum(tie_head)
+            rank = heads - heads[part_start] + 1
+        keep = rank <= int(per_limit)
+        return idx[keep][:int(k)], rank[keep][:int(k)].astype(np.int64)
+
+    def windowed(self, req):
+        """The rows a WindowRequest keeps, in its order, with its rank column when it names one."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])
+        cols = [a[idx] for a in self._cols]                              # undecoded text stays undecoded
+        return ResultSet(self.columns + ([req.name] if req.name is not None else []), cols + ([rank] if req.name is not None else []))
+
+    def top_per(self, k, by, order, ties=False):
+        """The first k rows of every group of `by` in the order of `order`; ties=True keeps every row tied with the k-th (RANK)."""
+        return self.windowed(window_request(self.columns, by, order, "rank" if ties else "row_number", k))
+
+    def numbered(self, by, order, kind="row_number", name="rank"):
+        """Every row, ordered by `by` then `order`, plus an int64 column `name`: its row_number / rank / dense_rank inside its group."""
+        return self.windowed(window_request(self.columns, by, order, kind, WINDOW_ALL, name=name))
 
     def to_dict(self):
         out = {}

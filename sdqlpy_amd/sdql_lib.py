@@ -389,8 +389,32 @@ def sdql_compile(in_type):
             from . import abi
             return top(abi.SORT_ALL, order)
 
+        def _windowed(by, order, kind, per_limit, name):
+            from . import engine, frontend
+            from .result import window_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            # checked here, before anything is launched: the names against the columns the plan's last loop gives its result
+            req = window_request(engine.result_columns(cache["plan"]), by, order, kind, per_limit, name=name)
+            return lambda *args: run(args, req)
+
+        def top_per(k, by, order, ties=False):
+            """The same query finished with ORDER BY ... LIMIT k PER GROUP: the first k rows of every group of `by` (column names, or
+            (column, "asc" | "desc") to say in which order the groups come) in the order of `order`, e.g.
+            ``q3.top_per(3, ["o_orderdate"], [("revenue", "desc")])(li, cu, ord)``.  ties=True keeps every row tied with the k-th
+            (RANK() <= k instead of ROW_NUMBER() <= k); by=[] is one group: "top k with ties"."""
+            return _windowed(list(by), list(order), "rank" if ties else "row_number", k, None)
+
+        def numbered(by, order, kind="row_number", name="rank"):
+            """The same query finished with ORDER BY `by`, `order` and an int64 column `name`: every row's row_number / rank /
+            dense_rank (kind) inside its group of `by`."""
+            from . import abi
+            return _windowed(list(by), list(order), kind, abi.SORT_ALL, name)
+
         wrapper.top = top
         wrapper.order_by = order_by
+        wrapper.top_per = top_per
+        wrapper.numbered = numbered
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
