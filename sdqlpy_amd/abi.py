@@ -253,6 +253,25 @@ def _np_ptr(a):
     return C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(None)
 
 
+def _marshal_sort_keys(sort):
+    """[(kind, index, descending, is_f64)] as a SortKey array (at least one slot: an empty list is the callee's error to report)."""
+    arr = (SortKey * max(1, len(sort)))()
+    for a, (kind, index, desc, is_f64) in zip(arr, sort):
+        a.kind, a.index, a.descending, a.is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
+    return arr
+
+
+def _marshal_sort_terms(terms):
+    """Sort terms as a SortTerm array: a 4-tuple is an underived term, an 8-tuple adds (div, mod, add, ranks Column or None)."""
+    arr = (SortTerm * max(1, len(terms)))()
+    for a, term in zip(arr, terms):
+        kind, index, desc, is_f64 = term[:4]
+        div, mod, add, ranks = term[4:] if len(term) > 4 else (0, 0, 0, None)
+        a.kind, a.index, a.descending, a.is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
+        a.div, a.mod, a.add, a.ranks = int(div), int(mod), int(add), None if ranks is None else ranks.handle
+    return arr
+
+
 class Column:
     """Device (or, for the oracle, host) resident column handle."""
 
@@ -1122,9 +1141,7 @@ class Context:
         """ORDER BY ... LIMIT k over the entries.  sort: [(kind, index, descending, is_f64)] with kind
         in SORT_KEY / SORT_PAYLOAD / SORT_VALUE / SORT_HITS.  Returns (keys, payload, values, hits) of n <= k rows, in order."""
         k = int(k)
-        arr = (SortKey * len(sort))()
-        for i, (kind, index, desc, is_f64) in enumerate(sort):
-            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
+        arr = _marshal_sort_keys(sort)
         keys = np.empty(k, np.int64)
         payload = np.empty((max(1, table.npayload), k), np.int64) if table.npayload else None
         values = np.empty((TUPLE_MAX_VALUES, k), np.float64) if table.accumulate else None
@@ -1136,9 +1153,11 @@ class Context:
         n = n.value
         return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
 
-    def _sorted_call(self, name, table, min_hits, limit, ncols, arr, capacity_hint, want_hits):
-        """What sdqh_table_sorted and sdqh_table_sorted_by share: arrays sized from capacity_hint, one retry with the exact size after
-        SDQH_ERR_OVERFLOW, the rows sliced to what was written.  arr: the marshalled sort columns / terms."""
+    def _sorted_call(self, name, table, lead, limit, capacity_hint, want_hits, want_rank=None):
+        """What sdqh_table_sorted, sdqh_table_sorted_by and sdqh_table_window share: arrays sized from capacity_hint, one retry with
+        the exact size after SDQH_ERR_OVERFLOW, the rows sliced to what was written.  lead: the call's arguments between the table and
+        the capacity (the marshalled sort columns / terms among them).  want_rank None: the call has no rank array and a 4-tuple is
+        returned; else a 5-tuple whose last member is the ranks, or None without want_rank."""
         fn = getattr(self.lib, "sdqh_" + name)
         cap = max(1, min(int(capacity_hint), int(limit)))
         for attempt in (0, 1):
@@ -1146,9 +1165,10 @@ class Context:
             payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
             values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
             hits = np.empty(cap, np.int64) if want_hits else None
+            rank = np.empty(cap, np.int64) if want_rank else None
             n = C.c_int64()
-            rc = fn(self.handle, table.handle, C.c_int64(min_hits), C.c_int64(limit), C.c_int(ncols), arr, C.c_int64(cap),
-                    _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), C.byref(n))
+            outs = (_np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits)) + (() if want_rank is None else (_np_ptr(rank),))
+            rc = fn(self.handle, table.handle, *lead, C.c_int64(cap), *outs, C.byref(n))
             if rc == ERR_OVERFLOW and attempt == 0:
                 cap = max(1, n.value)
                 continue
@@ -1156,7 +1176,8 @@ class Context:
             break
         self._after_call(name)
         n = n.value
-        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
+        rows = (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
+        return rows if want_rank is None else rows + (None if rank is None else rank[:n],)
 
     def table_sorted(self, table, min_hits, limit, sort, capacity_hint, want_hits=True):
         """ORDER BY over the entries with at least min_hits rows, the first min(limit, n) of them (limit = SORT_ALL: all): sort as
@@ -1164,10 +1185,8 @@ class Context:
         that does not fit is fetched again with the exact size.  Returns (keys, payload, values, hits), in order."""
         if not self.library.has_sort:
             raise SdqhError(ERR_UNSUPPORTED, "table_sorted: %s has no ordering extension" % self.library.path)
-        arr = (SortKey * len(sort))()
-        for i, (kind, index, desc, is_f64) in enumerate(sort):
-            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
-        return self._sorted_call("table_sorted", table, min_hits, limit, len(sort), arr, capacity_hint, want_hits)
+        lead = (C.c_int64(min_hits), C.c_int64(limit), C.c_int(len(sort)), _marshal_sort_keys(sort))
+        return self._sorted_call("table_sorted", table, lead, limit, capacity_hint, want_hits)
 
     def text_ranks(self, column, nrows):
         """(resident I64 Column of nrows dense ranks, number of distinct texts) of a STR column, in numpy's order of '<U' arrays: rank[r] <
@@ -1185,13 +1204,8 @@ class Context:
         ordered is ranks[field].  A 4-tuple is an underived term.  Returns (keys, payload, values, hits), in order."""
         if not self.library.has_sort_terms:
             raise SdqhError(ERR_UNSUPPORTED, "table_sorted_by: %s has no sort-terms extension" % self.library.path)
-        arr = (SortTerm * len(terms))()
-        for i, term in enumerate(terms):
-            kind, index, desc, is_f64 = term[:4]
-            div, mod, add, ranks = term[4:] if len(term) > 4 else (0, 0, 0, None)
-            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind), int(index), int(bool(desc)), int(bool(is_f64))
-            arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = int(div), int(mod), int(add), None if ranks is None else ranks.handle
-        return self._sorted_call("table_sorted_by", table, min_hits, limit, len(terms), arr, capacity_hint, want_hits)
+        lead = (C.c_int64(min_hits), C.c_int64(limit), C.c_int(len(terms)), _marshal_sort_terms(terms))
+        return self._sorted_call("table_sorted_by", table, lead, limit, capacity_hint, want_hits)
 
     def sort_geometry(self):
         """(largest n of the single-workgroup path, rows per tile of the radix path, smallest n with a second scan level or 0)."""
@@ -1211,32 +1225,8 @@ class Context:
         the first min(limit, kept) of them.  The arrays are sized from `capacity`; a result that does not fit is fetched again with the
         exact size.  Returns (keys, payload, values, hits, ranks) — ranks None without want_rank."""
         self._need_window("table_window")
-        arr = (SortTerm * max(1, len(terms)))()
-        for i, term in enumerate(terms):
-            kind_i, index, desc, is_f64 = term[:4]
-            div, mod, add, ranks = term[4:] if len(term) > 4 else (0, 0, 0, None)
-            arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(kind_i), int(index), int(bool(desc)), int(bool(is_f64))
-            arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = int(div), int(mod), int(add), None if ranks is None else ranks.handle
-        cap = max(1, min(int(capacity), int(limit))) if limit >= 1 else 1
-        for attempt in (0, 1):
-            keys = np.empty(cap, np.int64)
-            payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
-            values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
-            hits = np.empty(cap, np.int64) if want_hits else None
-            rank = np.empty(cap, np.int64) if want_rank else None
-            n = C.c_int64()
-            rc = self.lib.sdqh_table_window(self.handle, table.handle, C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), arr, C.c_int(kind),
-                                            C.c_int64(per_limit), C.c_int64(limit), C.c_int64(cap),
-                                            _np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits), _np_ptr(rank), C.byref(n))
-            if rc == ERR_OVERFLOW and attempt == 0:
-                cap = max(1, n.value)
-                continue
-            self._check(rc)
-            break
-        self._after_call("table_window")
-        n = n.value
-        return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n],
-                None if rank is None else rank[:n])
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(kind), C.c_int64(per_limit), C.c_int64(limit))
+        return self._sorted_call("table_window", table, lead, limit, capacity, want_hits, bool(want_rank))
 
     def window_geometry(self):
         """Sorted positions one wave ranks per step of sdqh_table_window's tile scan (what the tests size their cases from)."""

@@ -22,11 +22,6 @@
 
 using namespace sdqh_host;
 
-#define HIP_TRYA(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 struct sdqh_graph {
     hipGraph_t graph = nullptr;
@@ -506,7 +501,7 @@ int sdqh_table_compact_deferred(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t
         if (!dev) return fail(ctx, SDQH_ERR_NOMEM, "table_compact_deferred: out of device memory");
     } else {
         if (ctx->rs_bytes[b] < need) {
-            if (ctx->rs_used[b]) HIP_TRYA(ctx, hipEventSynchronize(ctx->rs_copied[b]));
+            if (ctx->rs_used[b]) HIP_TRY(ctx, hipEventSynchronize(ctx->rs_copied[b]));
             if (ctx->rs_dev[b]) (void)hipFree(ctx->rs_dev[b]);
             ctx->rs_dev[b] = nullptr; ctx->rs_bytes[b] = 0;
             const size_t want = std::max<size_t>(need + need / 4, (size_t)4 << 20);
@@ -517,7 +512,7 @@ int sdqh_table_compact_deferred(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t
     }
     call_begin(ctx);
     if (int rc = index_ensure(ctx, table)) return rc;
-    if (!rec && ctx->rs_used[b]) HIP_TRYA(ctx, hipStreamWaitEvent(ctx->stream, ctx->rs_copied[b], 0));       // the buffer's last copy has left it
+    if (!rec && ctx->rs_used[b]) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->rs_copied[b], 0));       // the buffer's last copy has left it
     DevCompactOut o; std::memset(&o, 0, sizeof(o));
     size_t off = 0;
     o.keys = reinterpret_cast<int64_t*>(dev); off += cb;
@@ -534,19 +529,19 @@ int sdqh_table_compact_deferred(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t
     if (int rc = launch_compact_pair(ctx, table, o, mh)) return rc;
     call_end(ctx);
     // the copy waits for the kernels by an event, not the host: keys .. the last used value array in one piece, then the hit counts
-    HIP_TRYA(ctx, hipEventRecord(ctx->rs_ready, ctx->stream));
-    HIP_TRYA(ctx, hipStreamWaitEvent(side, ctx->rs_ready, 0));
+    HIP_TRY(ctx, hipEventRecord(ctx->rs_ready, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(side, ctx->rs_ready, 0));
     const int lead = 1 + (out_payload ? table->npay : 0) + nval;
-    HIP_TRYA(ctx, hipMemcpyAsync(base, dev, cb * (size_t)lead, hipMemcpyDeviceToHost, side));
-    if (out_hits) HIP_TRYA(ctx, hipMemcpyAsync(out_hits, o.hits, cb, hipMemcpyDeviceToHost, side));
+    HIP_TRY(ctx, hipMemcpyAsync(base, dev, cb * (size_t)lead, hipMemcpyDeviceToHost, side));
+    if (out_hits) HIP_TRY(ctx, hipMemcpyAsync(out_hits, o.hits, cb, hipMemcpyDeviceToHost, side));
     // out_n[1]: the DONE word of this result, written by the copy stream itself behind the copies (1; 2 = no marker: wait with sdqh_result_wait)
     if (stream_store32(ctx, side, reinterpret_cast<uint32_t*>(&out_n[1]), 1) != SDQH_OK) out_n[1] = 2;
     if (rec) {
         // join: a recording ends with every forked stream back on the origin (the next replay's kernels then start behind this replay's copy)
-        HIP_TRYA(ctx, hipEventRecord(ctx->rs_ready, side));
-        HIP_TRYA(ctx, hipStreamWaitEvent(ctx->stream, ctx->rs_ready, 0));
+        HIP_TRY(ctx, hipEventRecord(ctx->rs_ready, side));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->rs_ready, 0));
     } else {
-        HIP_TRYA(ctx, hipEventRecord(ctx->rs_copied[b], side));
+        HIP_TRY(ctx, hipEventRecord(ctx->rs_copied[b], side));
         ctx->rs_used[b] = true; ctx->rs_pending = true; ctx->rs_cur = b ^ 1;
     }
     // (value slots the tuple does not use are not written: the binding zeroes a block once, when it allocates it, and nothing on the
@@ -600,7 +595,7 @@ int sdqh_table_partition_pack(sdqh_ctx* ctx, const sdqh_table* table, int nparts
         return SDQH_OK;
     }
     // the headers double as the kernel's cursors: 16 bytes cleared at the head of every chunk (one strided memset)
-    HIP_TRYA(ctx, hipMemset2DAsync(packed, (size_t)cw * 8, 0, 16, (size_t)nparts, ctx->stream));
+    HIP_TRY(ctx, hipMemset2DAsync(packed, (size_t)cw * 8, 0, 16, (size_t)nparts, ctx->stream));
     const unsigned grid = (unsigned)std::max(1, (table->stage.nseg + PP_SEGS - 1) / PP_SEGS);
     { KernelScope ks(ctx, "k_stage_part_pack");
       hipLaunchKernelGGL(k_stage_part_pack, dim3(grid), dim3(TPB), 0, ctx->stream, table->stage, pt, ncols, chunk_rows, cw, static_cast<int64_t*>(packed)); }
@@ -719,7 +714,7 @@ int sdqh_graph_launch(sdqh_ctx* ctx, sdqh_graph* g) {
     for (const auto& h : g->inits) { if (h.bytes == 8) *static_cast<volatile uint64_t*>(h.p) = h.value; else *static_cast<volatile uint32_t*>(h.p) = (uint32_t)h.value; }
     ++ctx->launch_seq;
     rd_dirty(ctx);                                                      // the replayed kernels used the result block: no claim about it survives
-    HIP_TRYA(ctx, hipGraphLaunch(g->exec, ctx->stream));
+    HIP_TRY(ctx, hipGraphLaunch(g->exec, ctx->stream));
     return SDQH_OK;
 }
 

@@ -29,13 +29,6 @@
 
 using namespace sdqh_host;
 
-#define HIP_TRYE(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-#define LAUNCH(ctx, name, kernel, grid, ...)                                         \
-    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), 0, (ctx)->stream, __VA_ARGS__); } while (0)
 
 namespace {
 
@@ -303,7 +296,7 @@ int sdqh_table_extrema_end(sdqh_ctx* ctx, sdqh_table* table) {
     const unsigned grid = (unsigned)std::max(1, (table->stage.nseg + TPB / WAVE - 1) / (TPB / WAVE));
     LAUNCH(ctx, "k_ext_end", k_ext_slots<true>, grid, table->stage, es, table->ext_status);
     call_end(ctx);
-    HIP_TRYE(ctx, hipMemcpyAsync(ctx->result_host, table->ext_status, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, table->ext_status, 8, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     unsigned long long status = 0;
     std::memcpy(&status, ctx->result_host, 8);

@@ -31,11 +31,6 @@ int fail(sdqh_ctx* ctx, int code, const std::string& msg) {
     if (ctx) ctx->err = msg;
     return code;
 }
-#define HIP_TRY(ctx, expr)                                                                              \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 // ---- pool --------------------------------------------------------------------------------------
 void* pool_alloc(sdqh_ctx* ctx, size_t bytes) {
@@ -88,10 +83,6 @@ void call_end(sdqh_ctx* ctx) {
     (void)hipEventRecord(ctx->call_end, ctx->stream);
     ctx->call_timed = true;
 }
-#define LAUNCH(ctx, name, kernel, grid, ...)                                         \
-    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), 0, (ctx)->stream, __VA_ARGS__); } while (0)
-#define LAUNCH_LDS(ctx, name, kernel, grid, lds_bytes, ...)                           \
-    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), (lds_bytes), (ctx)->stream, __VA_ARGS__); } while (0)
 
 int sync_stream(sdqh_ctx* ctx) {
     if (ctx->capturing) return fail(ctx, SDQH_ERR_UNSUPPORTED, "a call that waits for the device cannot be recorded into a plan graph");

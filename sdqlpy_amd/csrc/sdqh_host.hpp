@@ -313,3 +313,16 @@ struct KernelScope {
 };
 
 }  // namespace sdqh_host
+
+// ---- macros of every host unit (used where sdqh_host's names are visible) ---------------------------
+// a HIP call inside an entry point: its error becomes the entry point's SDQH_ERR_DEVICE return
+#define HIP_TRY(ctx, expr)                                                                              \
+    do {                                                                                                \
+        hipError_t _e = (expr);                                                                         \
+        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+// a launch of TPB threads per workgroup on the context's stream, inside a KernelScope
+#define LAUNCH(ctx, name, kernel, grid, ...)                                         \
+    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), 0, (ctx)->stream, __VA_ARGS__); } while (0)
+#define LAUNCH_LDS(ctx, name, kernel, grid, lds_bytes, ...)                           \
+    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), (lds_bytes), (ctx)->stream, __VA_ARGS__); } while (0)

@@ -3299,13 +3299,15 @@ __device__ __forceinline__ uint64_t sort_bits(int64_t raw, int is_f64, int desc)
     if (is_f64) u = (u >> 63) ? ~u : (u | (1ull << 63)); else u ^= (1ull << 63);
     return desc ? ~u : u;
 }
+// the 64 bits of sort column sk in staged row idx, as stored
+__device__ __forceinline__ int64_t sort_raw(const DevSortKey& sk, const DevStage& st, int64_t idx, uint32_t hits) {
+    if (sk.kind == SDQH_SORT_KEY) return st.key[idx];
+    if (sk.kind == SDQH_SORT_PAYLOAD) { const int64_t* p = sk.index == 0 ? st.pay[0] : (sk.index == 1 ? st.pay[1] : (sk.index == 2 ? st.pay[2] : st.pay[3])); return p[idx]; }
+    if (sk.kind == SDQH_SORT_VALUE) return __double_as_longlong(st.sacc[(size_t)idx * st.acc_stride + sk.index]);
+    return (int64_t)hits;
+}
 __device__ __forceinline__ uint64_t top_sort_value(const DevSortKey& sk, const DevStage& st, int64_t idx, uint32_t hits) {
-    int64_t raw = 0;
-    if (sk.kind == SDQH_SORT_KEY) raw = st.key[idx];
-    else if (sk.kind == SDQH_SORT_PAYLOAD) { const int64_t* p = sk.index == 0 ? st.pay[0] : (sk.index == 1 ? st.pay[1] : (sk.index == 2 ? st.pay[2] : st.pay[3])); raw = p[idx]; }
-    else if (sk.kind == SDQH_SORT_VALUE) raw = __double_as_longlong(st.sacc[(size_t)idx * st.acc_stride + sk.index]);
-    else raw = (int64_t)hits;
-    return sort_bits(raw, sk.is_f64, sk.desc);
+    return sort_bits(sort_raw(sk, st, idx, hits), sk.is_f64, sk.desc);
 }
 
 struct TopLds {

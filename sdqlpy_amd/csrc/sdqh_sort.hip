@@ -22,14 +22,18 @@
 //                     One form for every n a stage can hold (references are 32 bits): no second scan level.
 //   k_sort_emit       the first min(limit, n) rows in order, columns as sdqh_table_compact lays them out
 //
-// include/sdqh_sort_terms.h on top of it: sdqh_table_sorted_by orders by DERIVED columns — k_sort_term_keys is k_sort_keys with
-// field = (uint64(source) / div) % mod + add and a bounds-checked gather through a ranks column in front of sort_bits; everything behind
-// the key kernel is shared — and sdqh_text_ranks makes such a ranks column of a text column (k_text_masks / k_text_pack, the passes
-// above, k_rank_count / k_rank_place: see there).
+// One path behind the three table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h) and
+// sdqh_table_window (include/sdqh_sort_window.h): select -> order -> rank -> emit (ordered_impl).  What differs between them is
+// data, not code:
 //
-// include/sdqh_sort_window.h on top of both: sdqh_table_window ranks the ordered entries inside PARTITIONS (maximal runs of sorted
-// positions whose first npartition keys are equal) and keeps the rows whose rank is <= per_limit — ROW_NUMBER / RANK / DENSE_RANK
-// OVER (PARTITION BY ... ORDER BY ...).  Selection, keys and passes are the ones above; between them and the emit:
+//   a TERM            every sort column is a DevSortTerm.  k_sort_keys reads the column (sort_raw) and, for a DERIVED term, takes
+//                     field = (uint64(source) / div) % mod + add and a bounds-checked gather through a ranks column in front of
+//                     sort_bits; sdqh_table_sorted's keys are terms with no derivation.  sdqh_text_ranks makes such a ranks column of
+//                     a text column (k_text_masks / k_text_pack, the passes above, k_rank_count / k_rank_place: see there).
+//   a WINDOW          optional (SortWindow).  sdqh_table_window ranks the ordered entries inside PARTITIONS (maximal runs of sorted
+//                     positions whose first npartition keys are equal) and keeps the rows whose rank is <= per_limit — ROW_NUMBER /
+//                     RANK / DENSE_RANK OVER (PARTITION BY ... ORDER BY ...).  Without one the rank step launches nothing, allocates
+//                     nothing, and the emit reads the permutation directly.  With one, between the passes and the emit:
 //
 //   k_win_heads       a wave owns a tile of SORT_TILE sorted positions: position i reads its keys and those of i - 1 through the
 //                     permutation and sets two flags (a byte per position) — part_head: a partition key differs, tie_head: any key
@@ -46,7 +50,7 @@
 //   k_sort_scan / k_win_place
 //                     those counts scanned over the tiles, then the kept positions placed in order (ballot + lanes below: no atomic
 //                     cursor, because order is the contract).  per_limit >= n keeps everything: both are skipped
-//   k_win_emit        k_sort_emit through the kept positions, with the rank column
+//   k_sort_emit       then goes through the kept positions and writes the rank column beside the others
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -63,13 +67,6 @@
 
 using namespace sdqh_host;
 
-#define HIP_TRYS(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-#define LAUNCH(ctx, name, kernel, grid, ...)                                         \
-    do { KernelScope _ks(ctx, name); hipLaunchKernelGGL(kernel, dim3((unsigned)(grid)), dim3(TPB), 0, (ctx)->stream, __VA_ARGS__); } while (0)
 
 namespace {
 
@@ -82,7 +79,7 @@ constexpr int TEXT_WORD_BYTES = 8;                   // varying bytes of a text 
 
 // a sort column with its derivation (include/sdqh_sort_terms.h); nranks = rows of `ranks`
 struct DevSortTerm { DevSortKey sk; uint64_t div, mod; int64_t add; const int64_t* ranks; int64_t nranks; };
-inline bool term_derived(const DevSortTerm& t) { return t.div > 1 || t.mod != 0 || t.add != 0 || t.ranks != nullptr; }
+__host__ __device__ inline bool term_derived(const DevSortTerm& t) { return t.div > 1 || t.mod != 0 || t.add != 0 || t.ranks != nullptr; }
 // the bytes of a text row that make up one 64-bit key, most significant first: byte (24 - 8 * part) of code unit `unit`
 struct DevTextWord { uint16_t unit[TEXT_WORD_BYTES]; uint8_t shift[TEXT_WORD_BYTES]; int32_t nbytes, _pad; };
 struct DevSortOut { int64_t* keys; int64_t* pay[SDQH_MAX_PAYLOAD]; double* val[SDQH_TUPLE_MAX_VALUES]; int64_t* hits; int32_t npay, nval; };
@@ -107,6 +104,21 @@ __device__ __forceinline__ uint32_t block_scan_incl(uint32_t v, uint32_t* s_part
         __syncthreads();
     }
     return s_part[threadIdx.x];
+}
+
+// the tile of SORT_TILE consecutive positions of [0, n) the calling wave owns: tile w = [r0, r1); false: there is no such tile
+__device__ __forceinline__ bool tile_range(uint32_t ntiles, uint32_t n, uint32_t& w, uint64_t& r0, uint64_t& r1) {
+    w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
+    if (w >= ntiles) return false;
+    r0 = (uint64_t)w * SORT_TILE; r1 = min((uint64_t)n, r0 + SORT_TILE);
+    return true;
+}
+
+// the AND / OR of a column's keys, one pair per lane, folded over the wave and into info — the order does not matter: atomics
+__device__ __forceinline__ void fold_masks(uint64_t all, uint64_t any, unsigned long long* __restrict__ info, int col) {
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) { all &= (uint64_t)__shfl_xor((long long)all, off, WAVE); any |= (uint64_t)__shfl_xor((long long)any, off, WAVE); }
+    if (lane_id() == 0 && (all != ~0ull || any != 0ull)) { atomicAnd(&info[1 + col], (unsigned long long)all); atomicOr(&info[1 + SDQH_SORT_MAX_KEYS + col], (unsigned long long)any); }
 }
 
 // 1. selected entries per segment
@@ -159,47 +171,32 @@ __global__ __launch_bounds__(TPB) void k_sort_gather(DevTable t, DevStage st, ui
         at0 += (size_t)__popcll(b);
     }
 }
-// 4. one sort column's transformed keys beside the references (a launch per column), and the AND / OR of them — the order of those
-// does not matter: atomics.  n is the device's (info[0]).
-__global__ __launch_bounds__(TPB) void k_sort_keys(DevStage st, DevSortKey sk, const uint32_t* __restrict__ refs, uint64_t* __restrict__ key, unsigned long long* __restrict__ info, int col) {
+// 4. one term's transformed keys beside the references (a launch per term), and the AND / OR of them.  n is the device's (info[0]).
+// A derived term (uniform over the launch): field = (uint64(source) / div) % mod + add, then — if the term has a ranks column —
+// ranks[field], read only after field was found inside [0, nranks): an entry whose field lies outside raises the term's bit in
+// info[SORT_INFO_BAD] (the host reads the block anyway and fails the call) and takes key 0.
+__global__ __launch_bounds__(TPB) void k_sort_keys(DevStage st, DevSortTerm tm, const uint32_t* __restrict__ refs, uint64_t* __restrict__ key, unsigned long long* __restrict__ info, int col) {
     const uint64_t n = info[0];
-    uint64_t all = ~0ull, any = 0ull;
-    for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
-        const int64_t idx = (int64_t)refs[i];
-        const uint64_t k = top_sort_value(sk, st, idx, st.shits ? st.shits[idx] : 0u);
-        key[i] = k; all &= k; any |= k;
-    }
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) { all &= (uint64_t)__shfl_xor((long long)all, off, WAVE); any |= (uint64_t)__shfl_xor((long long)any, off, WAVE); }
-    if (lane_id() == 0 && (all != ~0ull || any != 0ull)) { atomicAnd(&info[1 + col], (unsigned long long)all); atomicOr(&info[1 + SDQH_SORT_MAX_KEYS + col], (unsigned long long)any); }
-}
-
-// 4b. the same for a derived term: field = (uint64(source) / div) % mod + add, then — if the term has a ranks column — ranks[field],
-// read only after field was found inside [0, nranks): an entry whose field lies outside raises the term's bit in info[SORT_INFO_BAD]
-// (the host reads the block anyway and fails the call) and takes key 0.
-__global__ __launch_bounds__(TPB) void k_sort_term_keys(DevStage st, DevSortTerm tm, const uint32_t* __restrict__ refs, uint64_t* __restrict__ key, unsigned long long* __restrict__ info, int col) {
-    const uint64_t n = info[0];
+    const bool derived = term_derived(tm);
     uint64_t all = ~0ull, any = 0ull;
     bool bad = false;
     for (uint64_t i = (uint64_t)blockIdx.x * TPB + threadIdx.x; i < n; i += (uint64_t)gridDim.x * TPB) {
         const int64_t idx = (int64_t)refs[i];
-        int64_t raw;
-        if (tm.sk.kind == SDQH_SORT_KEY) raw = st.key[idx];
-        else if (tm.sk.kind == SDQH_SORT_PAYLOAD) { const int64_t* p = tm.sk.index == 0 ? st.pay[0] : (tm.sk.index == 1 ? st.pay[1] : (tm.sk.index == 2 ? st.pay[2] : st.pay[3])); raw = p[idx]; }
-        else raw = (int64_t)(st.shits ? st.shits[idx] : 0u);
-        uint64_t f = (uint64_t)raw;
-        if (tm.div > 1) f /= tm.div;
-        if (tm.mod) f %= tm.mod;
-        int64_t v = (int64_t)(f + (uint64_t)tm.add);
+        const uint32_t hits = st.shits ? st.shits[idx] : 0u;
         uint64_t k = 0ull;
-        if (tm.ranks) {
-            if (v >= 0 && v < tm.nranks) k = sort_bits(tm.ranks[v], 0, tm.sk.desc); else bad = true;
-        } else k = sort_bits(v, 0, tm.sk.desc);
+        if (!derived) k = top_sort_value(tm.sk, st, idx, hits);
+        else {
+            uint64_t f = (uint64_t)sort_raw(tm.sk, st, idx, hits);
+            if (tm.div > 1) f /= tm.div;
+            if (tm.mod) f %= tm.mod;
+            const int64_t v = (int64_t)(f + (uint64_t)tm.add);
+            if (!tm.ranks) k = sort_bits(v, 0, tm.sk.desc);
+            else if (v >= 0 && v < tm.nranks) k = sort_bits(tm.ranks[v], 0, tm.sk.desc);
+            else bad = true;
+        }
         key[i] = k; all &= k; any |= k;
     }
-#pragma unroll
-    for (int off = 1; off < WAVE; off <<= 1) { all &= (uint64_t)__shfl_xor((long long)all, off, WAVE); any |= (uint64_t)__shfl_xor((long long)any, off, WAVE); }
-    if (lane_id() == 0 && (all != ~0ull || any != 0ull)) { atomicAnd(&info[1 + col], (unsigned long long)all); atomicOr(&info[1 + SDQH_SORT_MAX_KEYS + col], (unsigned long long)any); }
+    fold_masks(all, any, info, col);
     if (__ballot(bad) && lane_id() == 0) atomicOr(&info[SORT_INFO_BAD], 1ull << col);
 }
 
@@ -266,9 +263,8 @@ __global__ __launch_bounds__(TPB) void k_sort_hist(const uint64_t* __restrict__ 
     __shared__ uint32_t s_cnt[TPB / WAVE][256];
     const int wv = (int)(threadIdx.x / WAVE), lane = lane_id();
     for (int d = lane; d < 256; d += WAVE) s_cnt[wv][d] = 0;
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + wv;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     for (uint64_t r = r0 + lane; r < r1; r += WAVE) { const uint32_t g = perm ? perm[r] : (uint32_t)r; atomicAdd(&s_cnt[wv][g < n ? (uint32_t)(key[g] >> shift) & 255u : 0u], 1u); }
     for (int d = lane; d < 256; d += WAVE) hist[(size_t)d * ntiles + w] = s_cnt[wv][d];
 }
@@ -296,11 +292,10 @@ __global__ __launch_bounds__(TPB) void k_sort_scatter(const uint64_t* __restrict
     __syncthreads();
     s_part[threadIdx.x] = first;
     __syncthreads();
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + wv;
-    if (w >= ntiles) return;
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     for (int d = lane; d < 256; d += WAVE) s_at[wv][d] = s_part[d] + hist[(size_t)d * ntiles + w];
     const uint64_t lt = lanemask_lt();
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
     for (uint64_t b = r0; b < r1; b += WAVE) {
         const uint64_t r = b + lane;
         const bool live = r < r1;
@@ -308,21 +303,6 @@ __global__ __launch_bounds__(TPB) void k_sort_scatter(const uint64_t* __restrict
         const uint32_t d = live && g < n ? (uint32_t)(key[g] >> shift) & 255u : 0u;
         const uint32_t place = wave_place(s_at[wv], live, d, lt);
         if (live && place < n) perm_out[place] = g;
-    }
-}
-
-// rows perm[0 .. m) of the gathered entries (perm == nullptr: the gathered order itself); o's arrays hold m rows each
-__global__ __launch_bounds__(TPB) void k_sort_emit(DevStage st, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, uint32_t n, uint32_t m, DevSortOut o) {
-    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
-        const uint32_t g = perm ? perm[j] : (uint32_t)j;
-        if (g >= n) continue;                                            // (a permutation of [0, n): never taken)
-        const int64_t idx = (int64_t)refs[g];
-        if (o.keys) o.keys[j] = st.key[idx];
-#pragma unroll
-        for (int p = 0; p < SDQH_MAX_PAYLOAD; ++p) if (p < o.npay && o.pay[p]) o.pay[p][j] = st.pay[p][idx];
-#pragma unroll
-        for (int v = 0; v < SDQH_TUPLE_MAX_VALUES; ++v) if (v < o.nval && o.val[v]) o.val[v][j] = st.sacc[(size_t)idx * st.acc_stride + v];
-        if (o.hits) o.hits[j] = st.shits ? (int64_t)st.shits[idx] : 0;
     }
 }
 
@@ -373,9 +353,8 @@ __device__ __forceinline__ bool text_head(const uint32_t* __restrict__ text, int
     return differ;
 }
 __global__ __launch_bounds__(TPB) void k_rank_count(const uint32_t* __restrict__ text, int width, const uint32_t* __restrict__ perm, uint32_t n, uint32_t* __restrict__ tile_heads, uint32_t ntiles) {
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     uint32_t heads = 0;
     for (uint64_t b = r0; b < r1; b += WAVE) {
         const uint64_t r = b + lane_id();
@@ -387,9 +366,8 @@ __global__ __launch_bounds__(TPB) void k_rank_count(const uint32_t* __restrict__
 }
 __global__ __launch_bounds__(TPB) void k_rank_place(const uint32_t* __restrict__ text, int width, const uint32_t* __restrict__ perm, uint32_t n, const uint32_t* __restrict__ tile_off, uint32_t ntiles,
                                                    int64_t* __restrict__ ranks) {
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     const uint64_t le = lanemask_lt() | (1ull << lane_id());
     uint32_t run = tile_off[w];                                       // ranks opened before this tile
     for (uint64_t b = r0; b < r1; b += WAVE) {
@@ -439,9 +417,8 @@ __device__ __forceinline__ void win_step(WinCarry& run, uint64_t mp, uint64_t mt
 // 1. heads + the carry of every tile.  keys[c * key_stride + g]: term c's key of gathered entry g.
 __global__ __launch_bounds__(TPB) void k_win_heads(const uint64_t* __restrict__ keys, size_t key_stride, int npart, int nterms, const uint32_t* __restrict__ perm, uint32_t n,
                                                   uint8_t* __restrict__ heads, WinCarry* __restrict__ carry, uint32_t ntiles) {
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     WinCarry run = {0u, 0u, 0u, 0u};
     for (uint64_t b = r0; b < r1; b += WAVE) {
         const uint64_t r = b + lane_id();
@@ -488,9 +465,8 @@ __global__ __launch_bounds__(TPB) void k_win_scan(WinCarry* __restrict__ carry, 
 // 3. the rank of `kind` of every position, and per tile the positions with rank <= per_limit
 __global__ __launch_bounds__(TPB) void k_win_rank(const uint8_t* __restrict__ heads, const WinCarry* __restrict__ carry, uint32_t n, int kind, uint64_t per_limit,
                                                  uint32_t* __restrict__ rank, uint32_t* __restrict__ tile_kept, uint32_t ntiles) {
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     const uint32_t lane = (uint32_t)lane_id();
     const uint64_t le = lanemask_lt() | (1ull << lane);
     WinCarry run = carry[w];
@@ -521,9 +497,8 @@ __global__ __launch_bounds__(TPB) void k_win_rank(const uint8_t* __restrict__ he
 // 4. the kept positions, in order: sel[0 .. kept) (tile_off: k_sort_scan of tile_kept); only the first m are asked for
 __global__ __launch_bounds__(TPB) void k_win_place(const uint32_t* __restrict__ rank, uint32_t n, uint64_t per_limit, const uint32_t* __restrict__ tile_off, uint32_t ntiles,
                                                   uint32_t* __restrict__ sel, uint32_t m) {
-    const uint32_t w = blockIdx.x * (TPB / WAVE) + threadIdx.x / WAVE;
-    if (w >= ntiles) return;
-    const uint64_t r0 = (uint64_t)w * SORT_TILE, r1 = min((uint64_t)n, r0 + SORT_TILE);
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
     const uint64_t lt = lanemask_lt();
     uint64_t at0 = tile_off[w];
     for (uint64_t b = r0; b < r1 && at0 < m; b += WAVE) {
@@ -535,14 +510,16 @@ __global__ __launch_bounds__(TPB) void k_win_place(const uint32_t* __restrict__ 
         at0 += (uint64_t)__popcll(k);
     }
 }
-// 5. k_sort_emit through the kept positions (sel == nullptr: every position is kept), with the rank column
-__global__ __launch_bounds__(TPB) void k_win_emit(DevStage st, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ sel,
-                                                 const uint32_t* __restrict__ rank, uint32_t n, uint32_t m, DevSortOut o, int64_t* __restrict__ out_rank) {
+// The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
+// kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
+// hold m rows each; a null array is not written, and rank is read only for out_rank.
+__global__ __launch_bounds__(TPB) void k_sort_emit(DevStage st, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ sel,
+                                                  const uint32_t* __restrict__ rank, uint32_t n, uint32_t m, DevSortOut o, int64_t* __restrict__ out_rank) {
     for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
         const uint32_t i = sel ? sel[j] : (uint32_t)j;
         if (i >= n) continue;                                            // (kept positions are positions: never taken)
         const uint32_t g = perm ? perm[i] : i;
-        if (g >= n) continue;
+        if (g >= n) continue;                                            // (a permutation of [0, n): never taken)
         const int64_t idx = (int64_t)refs[g];
         if (o.keys) o.keys[j] = st.key[idx];
 #pragma unroll
@@ -560,6 +537,26 @@ struct Scratch {                                     // pool blocks of one call,
     ~Scratch() { for (void* q : p) if (q) pool_free(ctx, q); }
 };
 inline size_t round_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+
+// A scratch block carved into typed arrays, each starting on a 256-byte boundary.  A block's layout is ONE sequence of take() calls
+// (a lambda), run twice: over Carver(nullptr) it sums the sizes — bytes() is what to allocate — and over Carver(block) it hands out the
+// arrays, so no array can be left out of the sum.  The sums are byte for byte those the hand-written offsets gave (the slack a
+// block carried is taken as an array of its own): the pool hands a freed block to the next request of its size.
+struct Carver {
+    uintptr_t base; size_t at = 0;
+    explicit Carver(void* block) : base(reinterpret_cast<uintptr_t>(block)) {}
+    template <class T> T* take(size_t count) { T* p = reinterpret_cast<T*>(base + at); at += round_up(count * sizeof(T)); return p; }
+    size_t bytes() const { return at; }
+};
+// the block of `layout` from the pool into `slot` and carved; false: out of device memory
+template <class Layout> bool carve(sdqh_ctx* ctx, void*& slot, Layout layout) {
+    Carver sum(nullptr);
+    layout(sum);
+    if (!(slot = pool_alloc(ctx, sum.bytes()))) return false;
+    Carver c(slot);
+    layout(c);
+    return true;
+}
 
 }  // namespace
 
@@ -598,25 +595,22 @@ static int sort_select(sdqh_ctx* ctx, sdqh_table* table, const std::string& me, 
     // block 0: [segment offsets | info | references | keys per column], sized for every staged row (the count is the device's)
     const size_t rows = (size_t)std::max<int64_t>(table->nrows_build, 1) + 1;
     const int nseg = table->stage.nseg;
-    const size_t seg_bytes = round_up((size_t)std::max(nseg, 1) * 4), info_bytes = round_up(SORT_INFO * 8), ref_bytes = round_up(rows * 4), key_bytes = round_up(rows * 8);
-    char* blob = static_cast<char*>(scratch.p[0] = pool_alloc(ctx, seg_bytes + info_bytes + ref_bytes + key_bytes * (size_t)nsort));
-    if (!blob) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-    uint32_t* seg_off = reinterpret_cast<uint32_t*>(blob);
-    unsigned long long* info = s.info = reinterpret_cast<unsigned long long*>(blob + seg_bytes);
-    uint32_t* refs = s.refs = reinterpret_cast<uint32_t*>(blob + seg_bytes + info_bytes);
-    uint64_t* keys = s.keys = reinterpret_cast<uint64_t*>(blob + seg_bytes + info_bytes + ref_bytes);
-    const size_t key_stride = s.key_stride = key_bytes / 8;
+    const size_t key_stride = s.key_stride = round_up(rows * 8) / 8;
+    uint32_t* seg_off = nullptr;
+    if (!carve(ctx, scratch.p[0], [&](Carver& c) {
+            seg_off = c.take<uint32_t>((size_t)std::max(nseg, 1));
+            s.info = c.take<unsigned long long>(SORT_INFO);
+            s.refs = c.take<uint32_t>(rows);
+            s.keys = c.take<uint64_t>(key_stride * (size_t)nsort);
+        })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
     const uint32_t mh = (uint32_t)std::min<int64_t>(std::max<int64_t>(min_hits, 0), 0xFFFFFFFFll);
     const unsigned seg_grid = (unsigned)std::max(1, (nseg + TPB / WAVE - 1) / (TPB / WAVE));
     LAUNCH(ctx, "k_sort_count", k_sort_count, seg_grid, table->dev, table->stage, mh, seg_off);
-    LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, seg_off, nseg, info);
-    LAUNCH(ctx, "k_sort_gather", k_sort_gather, seg_grid, table->dev, table->stage, mh, seg_off, refs);
+    LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, seg_off, nseg, s.info);
+    LAUNCH(ctx, "k_sort_gather", k_sort_gather, seg_grid, table->dev, table->stage, mh, seg_off, s.refs);
     const unsigned key_grid = (unsigned)std::max<size_t>(1, std::min<size_t>((rows + TPB - 1) / TPB, (size_t)ctx->num_cu * 8));
-    for (int c = 0; c < nsort; ++c) {
-        if (term_derived(terms[c])) LAUNCH(ctx, "k_sort_term_keys", k_sort_term_keys, key_grid, table->stage, terms[c], refs, keys + (size_t)c * key_stride, info, c);
-        else LAUNCH(ctx, "k_sort_keys", k_sort_keys, key_grid, table->stage, terms[c].sk, refs, keys + (size_t)c * key_stride, info, c);
-    }
-    HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, info, SORT_INFO * 8, hipMemcpyDeviceToHost, ctx->stream));
+    for (int c = 0; c < nsort; ++c) LAUNCH(ctx, "k_sort_keys", k_sort_keys, key_grid, table->stage, terms[c], s.refs, s.keys + (size_t)c * key_stride, s.info, c);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, SORT_INFO * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     std::memcpy(s.h, ctx->result_host, sizeof(s.h));
     if (s.h[SORT_INFO_BAD]) {                                         // before anything is written, *out_n included
@@ -643,17 +637,17 @@ static int sort_passes(sdqh_ctx* ctx, const std::string& me, int nsort, Scratch&
     const bool small = n <= SORT_SMALL;
     s.perm = nullptr;
     if (npass) {
-        const size_t perm_bytes = round_up((size_t)n * 4), hist_bytes = small ? 0 : round_up((size_t)ntiles * 256 * 4);
-        char* b1 = static_cast<char*>(scratch.p[1] = pool_alloc(ctx, perm_bytes * (small ? 1 : 2) + hist_bytes + 1024));
-        if (!b1) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        uint32_t* pa = reinterpret_cast<uint32_t*>(b1);
+        uint32_t *pa = nullptr, *pb = nullptr, *hist = nullptr, *bin_total = nullptr;       // (the single-workgroup kernel uses pa alone)
+        if (!carve(ctx, scratch.p[1], [&](Carver& c) {
+                pa = c.take<uint32_t>((size_t)n);
+                pb = c.take<uint32_t>(small ? 0 : (size_t)n);
+                hist = c.take<uint32_t>(small ? 0 : (size_t)ntiles * 256);
+                bin_total = c.take<uint32_t>(256);
+            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         if (small) {
             LAUNCH(ctx, "k_sort_small", k_sort_small, 1, s.keys, s.key_stride, nsort, un, s.info, pa);
             s.perm = pa;
         } else {
-            uint32_t* pb = reinterpret_cast<uint32_t*>(b1 + perm_bytes);
-            uint32_t* hist = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes);
-            uint32_t* bin_total = reinterpret_cast<uint32_t*>(b1 + 2 * perm_bytes + hist_bytes);
             for (int p = 0; p < npass; ++p) {
                 radix_pass(ctx, s.keys + (size_t)pass_col[p] * s.key_stride, s.perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
                 s.perm = pa; std::swap(pa, pb);
@@ -701,163 +695,152 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
     for (int v = 0; v < r.nval; ++v) dst[nd++] = reinterpret_cast<int64_t*>(out_values + (size_t)v * (size_t)capacity);
     if (out_hits) dst[nd++] = out_hits;
     if (out_extra) dst[nd++] = out_extra;
-    if (pinned) HIP_TRYS(ctx, hipMemcpyAsync(ctx->bulk_host, r.dev, need, hipMemcpyDeviceToHost, ctx->stream));
-    else for (int a = 0; a < nd; ++a) HIP_TRYS(ctx, hipMemcpyAsync(dst[a], r.dev + (size_t)a * nb, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (pinned) HIP_TRY(ctx, hipMemcpyAsync(ctx->bulk_host, r.dev, need, hipMemcpyDeviceToHost, ctx->stream));
+    else for (int a = 0; a < nd; ++a) HIP_TRY(ctx, hipMemcpyAsync(dst[a], r.dev + (size_t)a * nb, nb, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     if (pinned) for (int a = 0; a < nd; ++a) std::memcpy(dst[a], static_cast<const char*>(ctx->bulk_host) + (size_t)a * nb, nb);
     return SDQH_OK;
 }
 
-// sdqh_table_sorted / sdqh_table_sorted_by behind their argument checks; who: the entry point's name in messages
-static int sorted_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms,
-                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
-    const std::string me(who);
-    Scratch scratch(ctx);
-    SortState s;
-    if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;
-    const int64_t n = s.n, m = std::min<int64_t>(limit, n);
-    *out_n = m;
-    if (!out_keys && !out_payload && !out_values && !out_hits) { call_end(ctx); return SDQH_OK; }      // count-only call
-    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
-    if (m == 0) { call_end(ctx); return SDQH_OK; }
-    if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
-    SortRows r;
-    if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, false, scratch, r)) return rc;
-    if (r.narr) {
-        const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-        LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, (uint32_t)n, (uint32_t)m, r.o);
-        call_end(ctx);
-        if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, nullptr)) return rc;
-    }
-    if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
-    return SDQH_OK;
-}
+// the optional third step of ordered_impl: ranks of `kind` inside partitions by the first npart terms, rows with rank <= per_limit kept
+struct SortWindow { int npart, kind; int64_t per_limit; int64_t* out_rank; };
 
-// sdqh_table_window behind its argument checks
-static int window_impl(sdqh_ctx* ctx, sdqh_table* table, int64_t min_hits, int npart, int nsort, const DevSortTerm* terms, int kind, int64_t per_limit, int64_t limit,
-                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_rank, int64_t* out_n) {
-    const std::string me("table_window");
+// The three table entry points behind their argument checks: select -> order -> rank (win != nullptr) -> emit.  who: the entry
+// point's name in messages.
+static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
+                        int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    const std::string me(who);
+    int64_t* out_rank = win ? win->out_rank : nullptr;
     Scratch scratch(ctx);
     SortState s;
-    if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;
+    if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
     const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank;
-    const bool all_kept = per_limit >= n;                            // a rank is at most n: nothing to filter
-    if (n == 0 || (count_only && all_kept)) { *out_n = std::min<int64_t>(limit, n); call_end(ctx); return SDQH_OK; }
-    if (all_kept && std::min<int64_t>(limit, n) > capacity) { *out_n = std::min<int64_t>(limit, n); call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
+    const bool all_kept = !win || win->per_limit >= n;               // a rank is at most n: nothing to filter, the count is known
+    const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
+    const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
+    // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering window knows its count
+    // only after the ranks, so of these it takes the first alone (and leaves *out_n untouched if a later step fails).
+    int64_t m = std::min<int64_t>(limit, n);
+    if (n == 0) return done(0);                                       // nothing selected (limit >= 1: m = 0 means n = 0)
+    if (all_kept && count_only) return done(m);                       // count-only call
+    if (all_kept && m > capacity) return overflow(m);                 // the needed count, nothing written
+    if (!win) *out_n = m;
     if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
-    // block 3: [heads | tile carries | ranks | kept per tile | kept positions]
     const uint32_t un = (uint32_t)n;
-    const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-    const size_t head_bytes = round_up((size_t)n), carry_bytes = round_up((size_t)ntiles * sizeof(WinCarry)), rank_bytes = round_up((size_t)n * 4), kept_bytes = round_up((size_t)ntiles * 4);
-    char* b3 = static_cast<char*>(scratch.p[3] = pool_alloc(ctx, head_bytes + carry_bytes + rank_bytes + kept_bytes + (all_kept ? 0 : rank_bytes) + 256));
-    if (!b3) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-    uint8_t* heads = reinterpret_cast<uint8_t*>(b3);
-    WinCarry* carry = reinterpret_cast<WinCarry*>(b3 + head_bytes);
-    uint32_t* rank = reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes);
-    uint32_t* tile_kept = reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes + rank_bytes);
-    uint32_t* sel = all_kept ? nullptr : reinterpret_cast<uint32_t*>(b3 + head_bytes + carry_bytes + rank_bytes + kept_bytes);
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-    const uint64_t pl = (uint64_t)per_limit;
-    LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, npart, nsort, s.perm, un, heads, carry, ntiles);
-    LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-    LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, kind, pl, rank, tile_kept, ntiles);
-    int64_t kept = n;
-    if (!all_kept) {
-        LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
-        HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (int rc = sync_stream(ctx)) return rc;
-        unsigned long long k0;
-        std::memcpy(&k0, ctx->result_host, 8);
-        kept = (int64_t)k0;
+    uint32_t *rank = nullptr, *sel = nullptr;
+    if (win) {
+        // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack]
+        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t* tile_kept = nullptr;
+        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
+                heads = c.take<uint8_t>((size_t)n);
+                carry = c.take<WinCarry>(ntiles);
+                rank = c.take<uint32_t>((size_t)n);
+                tile_kept = c.take<uint32_t>(ntiles);
+                sel = all_kept ? nullptr : c.take<uint32_t>((size_t)n);
+                (void)c.take<char>(256);
+            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        const uint64_t pl = (uint64_t)win->per_limit;
+        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, win->npart, nsort, s.perm, un, heads, carry, ntiles);
+        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+        LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, win->kind, pl, rank, tile_kept, ntiles);
+        if (!all_kept) {                                              // the kept positions counted, the ways out again, then placed
+            LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (int rc = sync_stream(ctx)) return rc;
+            unsigned long long kept;
+            std::memcpy(&kept, ctx->result_host, 8);
+            m = std::min<int64_t>(limit, (int64_t)kept);
+            if (count_only || m == 0) return done(m);
+            if (m > capacity) return overflow(m);
+            LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
+        }
     }
-    const int64_t m = std::min<int64_t>(limit, kept);
     *out_n = m;
-    if (count_only) { call_end(ctx); return SDQH_OK; }
-    if (m > capacity) { call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
-    if (m == 0) { call_end(ctx); return SDQH_OK; }
-    const uint32_t um = (uint32_t)m;
-    if (!all_kept) LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, um);
+    // emit: m rows (>= 1) of the arrays asked for; none if only columns the table does not have were
     SortRows r;
     if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, out_rank != nullptr, scratch, r)) return rc;
-    if (!r.narr) { call_end(ctx); return SDQH_OK; }                  // (only columns the table does not have were asked for)
-    const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-    LAUNCH(ctx, "k_win_emit", k_win_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, um, r.o, r.extra);
-    call_end(ctx);
-    if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
+    if (r.narr) {
+        const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+        LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, (uint32_t)m, r.o, r.extra);
+    }
+    call_end(ctx);                                                    // the call's device time ends here: the fetch is the host's
+    if (r.narr) if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
     if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
     return SDQH_OK;
 }
 
-// the checks both entry points make of a sort column; the term's derivation is left as it is
+// the checks every entry point makes of a sort column; the term's derivation is left as it is
 static bool sort_column_ok(const sdqh_table* table, int kind, int index) {
     const int nv = table->accumulate ? table->nv : 0;
     return (kind == SDQH_SORT_KEY) || (kind == SDQH_SORT_PAYLOAD && index >= 0 && index < table->npay) ||
            (kind == SDQH_SORT_VALUE && index >= 0 && index < nv) || (kind == SDQH_SORT_HITS && table->accumulate);
 }
-static void sort_column_set(DevSortKey& k, int kind, int index, int descending, int is_f64) {
-    k.kind = kind; k.index = index; k.desc = descending ? 1 : 0;
-    k.is_f64 = kind == SDQH_SORT_VALUE ? 1 : (kind == SDQH_SORT_PAYLOAD ? (is_f64 ? 1 : 0) : 0);
-}
 
-int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
-                      int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
-    sdqh_table* table = const_cast<sdqh_table*>(ctable);
-    if (!ctx || !table || !out_n || !sort || nsort < 1 || nsort > SDQH_SORT_MAX_KEYS || limit < 1 || capacity < 0)
-        return fail(ctx, SDQH_ERR_INVALID, "table_sorted: bad arguments");
-    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: compile-only context");
-    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted: bitmap-only table");
-    (void)hipSetDevice(ctx->device);
-    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
-    for (int i = 0; i < nsort; ++i) {
-        if (!sort_column_ok(table, sort[i].kind, sort[i].index)) return fail(ctx, SDQH_ERR_INVALID, "table_sorted: sort key names a field the table does not have");
-        sort_column_set(terms[i].sk, sort[i].kind, sort[i].index, sort[i].descending, sort[i].is_f64);
-    }
-    return sorted_impl(ctx, table, "table_sorted", min_hits, limit, nsort, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
-}
-
-// the terms of sdqh_table_sorted_by / sdqh_table_window checked and marshalled; SDQH_OK or the failed call's code
-static int sort_terms_set(sdqh_ctx* ctx, const sdqh_table* table, const std::string& me, int nterms, const sdqh_sort_term* in, DevSortTerm* terms) {
+// the terms of an entry point checked and marshalled; SDQH_OK or the failed call's code.  plain: sdqh_table_sorted's keys (terms
+// with no derivation), named "sort key" in its one message
+static int sort_terms_set(sdqh_ctx* ctx, const sdqh_table* table, const std::string& me, int nterms, const sdqh_sort_term* in, bool plain, DevSortTerm* terms) {
+    std::memset(terms, 0, sizeof(DevSortTerm) * SDQH_SORT_MAX_KEYS);
     for (int i = 0; i < nterms; ++i) {
         const sdqh_sort_term& t = in[i];
-        if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " names a field the table does not have");
-        sort_column_set(terms[i].sk, t.kind, t.index, t.descending, t.is_f64);
-        if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " has a negative divisor or modulus");
-        if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + ": ranks must be an I64 column");
+        const std::string term = me + ": term " + std::to_string(i);
+        if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, (plain ? me + ": sort key" : term) + " names a field the table does not have");
+        DevSortKey& k = terms[i].sk;
+        k.kind = t.kind; k.index = t.index; k.desc = t.descending ? 1 : 0;
+        k.is_f64 = t.kind == SDQH_SORT_VALUE ? 1 : (t.kind == SDQH_SORT_PAYLOAD ? (t.is_f64 ? 1 : 0) : 0);
+        if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, term + " has a negative divisor or modulus");
+        if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, term + ": ranks must be an I64 column");
         terms[i].div = (uint64_t)t.div; terms[i].mod = (uint64_t)t.mod; terms[i].add = t.add;
         terms[i].ranks = t.ranks ? static_cast<const int64_t*>(t.ranks->data) : nullptr;
         terms[i].nranks = t.ranks ? t.ranks->nrows : 0;
-        if (term_derived(terms[i]) && terms[i].sk.is_f64) return fail(ctx, SDQH_ERR_INVALID, me + ": term " + std::to_string(i) + " derives from a double");
+        if (term_derived(terms[i]) && k.is_f64) return fail(ctx, SDQH_ERR_INVALID, term + " derives from a double");
     }
     return SDQH_OK;
 }
 
-int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
-                         int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
-    sdqh_table* table = const_cast<sdqh_table*>(ctable);
-    if (!ctx || !table || !out_n || !in || nterms < 1 || nterms > SDQH_SORT_MAX_KEYS || limit < 1 || capacity < 0)
-        return fail(ctx, SDQH_ERR_INVALID, "table_sorted_by: bad arguments");
-    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted_by: compile-only context");
-    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_sorted_by: bitmap-only table");
+// what the three entry points check before they look at their terms; ok: the entry point's own conditions on its arguments
+static int sort_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, bool ok) {
+    const std::string me(who);
+    if (!ctx || !table || !ok) return fail(ctx, SDQH_ERR_INVALID, me + ": bad arguments");
+    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, me + ": compile-only context");
+    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, me + ": bitmap-only table");
     (void)hipSetDevice(ctx->device);
-    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
-    if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, terms)) return rc;
-    return sorted_impl(ctx, table, "table_sorted_by", min_hits, limit, nterms, terms, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return SDQH_OK;
+}
+static bool sort_args_ok(const void* terms, int nterms, int64_t limit, int64_t capacity, const int64_t* out_n) {
+    return out_n && terms && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && limit >= 1 && capacity >= 0;
 }
 
-int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* ctable, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
+                      int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    if (int rc = sort_enter(ctx, table, "table_sorted", sort_args_ok(sort, nsort, limit, capacity, out_n))) return rc;
+    sdqh_sort_term in[SDQH_SORT_MAX_KEYS]; std::memset(in, 0, sizeof(in));
+    for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
+                         int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+    if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                       int kind, int64_t per_limit, int64_t limit, int64_t capacity,
                       int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_rank, int64_t* out_n) {
-    sdqh_table* table = const_cast<sdqh_table*>(ctable);
-    if (!ctx || !table || !out_n || !in || nterms < 1 || nterms > SDQH_SORT_MAX_KEYS || npartition < 0 || npartition > nterms || per_limit < 1 || limit < 1 || capacity < 0 ||
-        (kind != SDQH_WIN_ROW_NUMBER && kind != SDQH_WIN_RANK && kind != SDQH_WIN_DENSE_RANK))
-        return fail(ctx, SDQH_ERR_INVALID, "table_window: bad arguments");
-    if (ctx->compile_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_window: compile-only context");
-    if (table->bitmap_only) return fail(ctx, SDQH_ERR_UNSUPPORTED, "table_window: bitmap-only table");
-    (void)hipSetDevice(ctx->device);
-    DevSortTerm terms[SDQH_SORT_MAX_KEYS]; std::memset(terms, 0, sizeof(terms));
-    if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, terms)) return rc;
-    return window_impl(ctx, table, min_hits, npartition, nterms, terms, kind, per_limit, limit, capacity, out_keys, out_payload, out_values, out_hits, out_rank, out_n);
+    const bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && per_limit >= 1 &&
+                    (kind == SDQH_WIN_ROW_NUMBER || kind == SDQH_WIN_RANK || kind == SDQH_WIN_DENSE_RANK);
+    if (int rc = sort_enter(ctx, table, "table_window", ok)) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
+    const SortWindow win = {npartition, kind, per_limit, out_rank};
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_window_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
@@ -885,25 +868,26 @@ int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_
     const uint32_t un = (uint32_t)nrows;
     const uint32_t ntiles = (uint32_t)((nrows + SORT_TILE - 1) / SORT_TILE);
     // one block: [masks | info | tile heads | keys | permutation x 2 | digit counts per tile | digit totals]
-    const size_t mask_bytes = round_up(2 * TEXT_MAX_WIDTH * 4), info_bytes = round_up(SORT_INFO * 8), tile_bytes = round_up((size_t)ntiles * 4), key_bytes = round_up((size_t)nrows * 8),
-                 perm_bytes = round_up((size_t)nrows * 4), hist_bytes = round_up((size_t)ntiles * 256 * 4);
-    char* blob = static_cast<char*>(scratch.p[0] = pool_alloc(ctx, mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes + hist_bytes + 1024));
-    if (!blob) return fail(ctx, SDQH_ERR_NOMEM, "text_ranks: out of device memory");
-    uint32_t* masks = reinterpret_cast<uint32_t*>(blob);
-    unsigned long long* info = reinterpret_cast<unsigned long long*>(blob + mask_bytes);
-    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes);
-    uint64_t* key = reinterpret_cast<uint64_t*>(blob + mask_bytes + info_bytes + tile_bytes);
-    uint32_t* pa = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes);
-    uint32_t* pb = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + perm_bytes);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes);
-    uint32_t* bin_total = reinterpret_cast<uint32_t*>(blob + mask_bytes + info_bytes + tile_bytes + key_bytes + 2 * perm_bytes + hist_bytes);
+    uint32_t *masks = nullptr, *tile_heads = nullptr, *pa = nullptr, *pb = nullptr, *hist = nullptr, *bin_total = nullptr;
+    unsigned long long* info = nullptr;
+    uint64_t* key = nullptr;
+    if (!carve(ctx, scratch.p[0], [&](Carver& c) {
+            masks = c.take<uint32_t>(2 * TEXT_MAX_WIDTH);
+            info = c.take<unsigned long long>(SORT_INFO);
+            tile_heads = c.take<uint32_t>(ntiles);
+            key = c.take<uint64_t>((size_t)nrows);
+            pa = c.take<uint32_t>((size_t)nrows);
+            pb = c.take<uint32_t>((size_t)nrows);
+            hist = c.take<uint32_t>((size_t)ntiles * 256);
+            bin_total = c.take<uint32_t>(256);
+        })) return fail(ctx, SDQH_ERR_NOMEM, "text_ranks: out of device memory");
     // (a) which bytes vary at all
-    HIP_TRYS(ctx, hipMemsetAsync(masks, 0xFF, TEXT_MAX_WIDTH * 4, ctx->stream));
-    HIP_TRYS(ctx, hipMemsetAsync(masks + TEXT_MAX_WIDTH, 0, TEXT_MAX_WIDTH * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(masks, 0xFF, TEXT_MAX_WIDTH * 4, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(masks + TEXT_MAX_WIDTH, 0, TEXT_MAX_WIDTH * 4, ctx->stream));
     const int rows_per = TPB / width;
     const unsigned mgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((nrows + rows_per - 1) / rows_per, (int64_t)ctx->num_cu * 8));
     LAUNCH(ctx, "k_text_masks", k_text_masks, mgrid, units, (uint64_t)nrows, width, masks);
-    HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, masks, 2 * TEXT_MAX_WIDTH * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, masks, 2 * TEXT_MAX_WIDTH * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     uint32_t hm[2 * TEXT_MAX_WIDTH];
     std::memcpy(hm, ctx->result_host, sizeof(hm));
@@ -931,7 +915,7 @@ int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_
     LAUNCH(ctx, "k_rank_count", k_rank_count, tgrid, units, width, perm, un, tile_heads, ntiles);
     LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_heads, (int)ntiles, info);
     LAUNCH(ctx, "k_rank_place", k_rank_place, tgrid, units, width, perm, un, tile_heads, ntiles, static_cast<int64_t*>(rk->data));
-    HIP_TRYS(ctx, hipMemcpyAsync(ctx->result_host, info, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, info, 8, hipMemcpyDeviceToHost, ctx->stream));
     call_end(ctx);
     if (int rc = sync_stream(ctx)) return rc;
     unsigned long long heads;

@@ -35,11 +35,6 @@ using namespace sdqh_host;
 
 namespace {
 
-#define HIP_TRYX(ctx, expr)                                                                             \
-    do {                                                                                                \
-        hipError_t _e = (expr);                                                                         \
-        if (_e != hipSuccess) return fail(ctx, SDQH_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
 
 enum Sink { SINK_SUM, SINK_GROUP, SINK_STAGE, SINK_KEYSET, SINK_ENTRY, SINK_GROUP_LANE };
 const char* sink_name(Sink s) { return s == SINK_SUM ? "XSum" : s == SINK_GROUP ? "XGroup" : s == SINK_STAGE ? "XStage" : s == SINK_KEYSET ? "XKeySet" : s == SINK_ENTRY ? "XEntry" : "XGroupLane"; }
@@ -1465,7 +1460,7 @@ int launch(sdqh_ctx* ctx, hipFunction_t fn, const char* name, const XArgs& a, co
     size_t size = sizeof(pk);
     void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &pk, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
     KernelScope ks(ctx, name);
-    HIP_TRYX(ctx, hipModuleLaunchKernel(fn, g.grid, 1, 1, TPB, 1, 1, lds_bytes, ctx->stream, nullptr, config));
+    HIP_TRY(ctx, hipModuleLaunchKernel(fn, g.grid, 1, 1, TPB, 1, 1, lds_bytes, ctx->stream, nullptr, config));
     return SDQH_OK;
 }
 
@@ -1491,7 +1486,7 @@ int64_t model_stream_bytes(const XInfo& x, int64_t nrows, bool regs_all) {
 }
 
 int read_flags(sdqh_ctx* ctx, const int32_t* d_flags, int* out) {
-    HIP_TRYX(ctx, hipMemcpyAsync(ctx->result_host, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
     *out = *static_cast<const int*>(ctx->result_host);
     return SDQH_OK;

@@ -1678,13 +1678,19 @@ def _device_sort_spec(bt, key_fields, vnames, count_idx, order, eng=None, fields
     return spec
 
 
-def _derived(spec):
-    return spec is not None and any(len(t) > 4 for t in spec)
+def _term_derived(t):
+    """Is sort term t the 8-tuple (..., div, mod, add, text) of abi.Context.table_sorted_by, not a plain 4-tuple column?"""
+    return len(t) > 4
+
+
+def _term_text(t):
+    """The text whose ranks term t orders by (its field indexes it), or None: the field orders itself."""
+    return t[7] if _term_derived(t) else None
 
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window") and len(t) > 4 and t[7] is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window") and _term_text(t) is not None]}
     if isinstance(top, WindowRequest):                       # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
@@ -1700,22 +1706,6 @@ class _Ranked:
 
     def __bool__(self):
         return True
-
-
-def _window_on(eng):
-    return eng is not None and bool(getattr(eng, "device_window", True)) and bool(getattr(eng.ctx.library, "has_window", False))
-
-
-def _windowed(eng, table, min_hits, hint_key, top, spec, want_hits):
-    """top_per / numbered on the device in one waited-for call (abi.Context.table_window): text terms through their resident ranks
-    column as in _sorted_by, the arrays sized from the previous run of the same plan step."""
-    terms = [t if len(t) == 4 or t[7] is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
-    hint = eng.compact_hints.get(("window", hint_key))
-    cap = 4096 if hint is None else hint + hint // 8 + 1024
-    keys, payload, values, hits, rank = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL),
-                                                             min(int(top[0]), abi.SORT_ALL), cap, want_hits=want_hits, want_rank=top.name is not None)
-    eng.compact_hints[("window", hint_key)] = len(keys)
-    return keys, payload, values, hits, rank
 
 
 def _host_top(rs, top):
@@ -1760,61 +1750,63 @@ def result_columns(plan):
     return None
 
 
-def _device_sorts(eng, top, spec):
-    """Is `top` = (k, order) beyond sdqh_table_topk (more than MAX_TOPK rows or MAX_SORT_KEYS columns) and within the device's
-    ORDER BY (abi.Context.table_sorted: a library with the ordering extension, Engine.device_sort on)?"""
-    if top is None or spec is None or top[0] < 1 or len(spec) > abi.SORT_MAX_KEYS:
-        return False
-    if not (top[0] > abi.MAX_TOPK or len(spec) > abi.MAX_SORT_KEYS):
-        return False
-    return bool(getattr(eng, "device_sort", True)) and bool(getattr(eng.ctx.library, "has_sort", False))
+def _order_route(eng, top, spec):
+    """Who orders `top` = (k, order) or a WindowRequest over the sort columns `spec` (None: no column list the device can take):
+    "topk"       sdqh_table_topk: at most MAX_TOPK rows by at most MAX_SORT_KEYS plain columns
+    "sorted"     abi.Context.table_sorted: plain columns beyond that (the ordering extension, Engine.device_sort on)
+    "sorted_by"  abi.Context.table_sorted_by: some term is derived, whatever k is (the sort-terms extension, Engine.device_sort on)
+    "window"     abi.Context.table_window: every WindowRequest the device takes — never the three above, which know nothing of
+                 partitions (the window extension and Engine.device_window on; derived terms need what "sorted_by" needs)
+    "host"       everything else: the caller compacts and result.py orders."""
+    if spec is None:
+        return "host"
+
+    def on(switch, extension):
+        return bool(getattr(eng, switch, True)) and bool(getattr(eng.ctx.library, extension, False))
+    k, n = top[0], len(spec)
+    derived = any(_term_derived(t) for t in spec)
+    terms_ok = not derived or on("device_sort", "has_sort_terms")
+    if isinstance(top, WindowRequest):
+        return "window" if 1 <= n <= abi.SORT_MAX_KEYS and on("device_window", "has_window") and terms_ok else "host"
+    if derived:
+        return "sorted_by" if k >= 1 and n <= abi.SORT_MAX_KEYS and terms_ok else "host"
+    if 1 <= k <= abi.MAX_TOPK and n <= abi.MAX_SORT_KEYS:
+        return "topk"
+    return "sorted" if k >= 1 and n <= abi.SORT_MAX_KEYS and on("device_sort", "has_sort") else "host"
 
 
-def _sorted(eng, table, min_hits, hint_key, top, spec, want_hits):
-    """ORDER BY (... LIMIT k) on the device in one waited-for call; the arrays are sized from the previous run of the same plan step."""
-    hint = eng.compact_hints.get(("sorted", hint_key))
+def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
+    """The routes "sorted", "sorted_by" and "window" of _order_route: one waited-for call whose arrays are sized from the previous run
+    of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
+    hint_key = ("window" if route == "window" else "sorted", hint_key)
+    hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
-    keys, payload, values, hits = eng.ctx.table_sorted(table, min_hits, min(int(top[0]), abi.SORT_ALL), spec, cap, want_hits=want_hits)
-    eng.compact_hints[("sorted", hint_key)] = len(keys)
-    return keys, payload, values, hits
-
-
-def _sorted_by(eng, table, min_hits, hint_key, top, spec, want_hits):
-    """_sorted for a spec with derived terms (abi.Context.table_sorted_by, whatever k is: sdqh_table_topk cannot take them); the text a
-    term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    terms = [t if len(t) == 4 or t[7] is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
-    hint = eng.compact_hints.get(("sorted", hint_key))
-    cap = 4096 if hint is None else hint + hint // 8 + 1024
-    keys, payload, values, hits = eng.ctx.table_sorted_by(table, min_hits, min(int(top[0]), abi.SORT_ALL), terms, cap, want_hits=want_hits)
-    eng.compact_hints[("sorted", hint_key)] = len(keys)
-    return keys, payload, values, hits
+    k = min(int(top[0]), abi.SORT_ALL)
+    terms = [t if _term_text(t) is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
+    if route == "sorted":
+        got = eng.ctx.table_sorted(table, min_hits, k, spec, cap, want_hits=want_hits)
+    elif route == "sorted_by":
+        got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
+    else:
+        got = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap,
+                                   want_hits=want_hits, want_rank=top.name is not None)
+    eng.compact_hints[hint_key] = len(got[0])
+    return got
 
 
 def _fetch_ordered(eng, bt_table, min_hits, hint_key, top, spec, want_hits):
     """The first k rows of a table in the order of `top` = (k, order) where the device can order them (spec): (keys, payload, values,
-    hits), or None — the caller compacts and the host orders.  Which way it went is noted in Engine.order_routes."""
+    hits) — and the ranks, from the window call — or None: the caller compacts and the host orders.  Which way it went is noted in
+    Engine.order_routes."""
     if top is None:
         return None
-    if isinstance(top, WindowRequest):                       # never topk / sorted / sorted_by: those know nothing of partitions
-        route = "window" if spec is not None and 1 <= len(spec) <= abi.SORT_MAX_KEYS and _window_on(eng) and (not _derived(spec) or _sort_terms_on(eng)) else "host"
-        _note_order_route(eng, top, spec, route)
-        return _windowed(eng, bt_table, min_hits, hint_key, top, spec, want_hits) if route == "window" else None
-    route = "host"
-    if _derived(spec):
-        if top[0] >= 1 and len(spec) <= abi.SORT_MAX_KEYS and _sort_terms_on(eng):
-            route = "sorted_by"
-    elif spec is not None and 1 <= top[0] <= abi.MAX_TOPK and len(spec) <= abi.MAX_SORT_KEYS:
-        route = "topk"
-    elif _device_sorts(eng, top, spec):
-        route = "sorted"
+    route = _order_route(eng, top, spec)
     _note_order_route(eng, top, spec, route)
+    if route == "host":
+        return None
     if route == "topk":
         return eng.ctx.table_topk(bt_table, min_hits, top[0], spec, want_hits=want_hits)
-    if route == "sorted":
-        return _sorted(eng, bt_table, min_hits, hint_key, top, spec, want_hits)
-    if route == "sorted_by":
-        return _sorted_by(eng, bt_table, min_hits, hint_key, top, spec, want_hits)
-    return None
+    return _ordered_call(eng, route, bt_table, min_hits, hint_key, top, spec, want_hits)
 
 
 def _fetch_entries(eng, bt_table, min_hits, hint_key, top, spec, **want):

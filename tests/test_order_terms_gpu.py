@@ -349,12 +349,7 @@ def test_underived_terms_give_what_table_sorted_gives(hip_engine):
 
 
 # 5. the contract --------------------------------------------------------------------------------------------------------------------------
-def _raw_terms(terms):
-    arr = (abi.SortTerm * len(terms))()
-    for i, (kind, index, desc, is_f64, div, mod, add, ranks) in enumerate(terms):
-        arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = kind, index, int(desc), int(is_f64)
-        arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = div, mod, add, None if ranks is None else ranks.handle
-    return arr
+_raw_terms = abi._marshal_sort_terms
 
 
 def test_contract_of_sorted_by(hip_engine, rank_columns):

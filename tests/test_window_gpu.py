@@ -149,13 +149,7 @@ def _check(ctx, t, terms, npart, what, min_hits=1, rank_tables=None, per_limits=
     return done, ref
 
 
-def _raw_terms(terms):
-    arr = (abi.SortTerm * max(1, len(terms)))()
-    for i, t in enumerate(terms):
-        arr[i].kind, arr[i].index, arr[i].descending, arr[i].is_f64 = int(t[0]), int(t[1]), int(bool(t[2])), int(bool(t[3]))
-        if len(t) > 4:
-            arr[i].div, arr[i].mod, arr[i].add, arr[i].ranks = int(t[4]), int(t[5]), int(t[6]), None if t[7] is None else t[7].handle
-    return arr
+_raw_terms = abi._marshal_sort_terms
 
 
 def _raw(ctx, t, min_hits, npart, terms, kind, per_limit, limit, capacity, keys=None, rank=None, got=None, nterms=None):
@@ -382,7 +376,8 @@ def _probed_table(ctx, n, seed=9):
     pk = keys[rng.integers(0, rows, 3 * rows)]
     pv = rng.integers(1, 1000, 3 * rows).astype(np.float64)
     t = ctx.hash_build_unique(rows, abi.make_filter(), [], ctx.upload(keys), [ctx.upload(pay_i), ctx.upload(pay_f.view(np.int64))], accumulate=True)
-    ctx.hash_probe_aggregate(3 * rows, abi.make_filter(), t, ctx.upload(pk), abi.make_tuple(abi.TUPLE_A, [ctx.upload(pv)]))
+    if rows:
+        ctx.hash_probe_aggregate(3 * rows, abi.make_filter(), t, ctx.upload(pk), abi.make_tuple(abi.TUPLE_A, [ctx.upload(pv)]))
     return t
 
 
@@ -413,6 +408,92 @@ def test_agreement_with_sorted_by(hip_engine):
         finally:
             t.free()
     assert done >= 2 * 5 * 2 * 2
+
+
+ENTRY_POINTS = ("table_sorted", "table_sorted_by", "table_window")
+OUTPUTS = ("keys", "payload", "values", "hits")
+
+
+def _entry_point_calls(ctx, t, min_hits, spec, limit, cap, want):
+    """sdqh_table_sorted(spec), sdqh_table_sorted_by(spec as underived terms) and sdqh_table_window(no partition, ROW_NUMBER, every row
+    kept, no rank column) through the raw C calls, each over its own arrays of `cap` rows filled with -7, of which those named in `want`
+    are passed: [(return code, *out_n, {name: array}, kernel names of the call's profile)].  Doubles are held as their int64 bits."""
+    lead = {"table_sorted": (C.c_int64(limit), C.c_int(len(spec)), abi._marshal_sort_keys(spec)),
+            "table_sorted_by": (C.c_int64(limit), C.c_int(len(spec)), abi._marshal_sort_terms(spec)),
+            "table_window": (C.c_int(0), C.c_int(len(spec)), abi._marshal_sort_terms(spec), C.c_int(abi.WIN_ROW_NUMBER), C.c_int64(ALL), C.c_int64(limit))}
+    calls = []
+    for name in ENTRY_POINTS:
+        arrs = {"keys": np.full(cap, -7, np.int64), "payload": np.full((2, cap), -7, np.int64),
+                "values": np.full((abi.TUPLE_MAX_VALUES, cap), -7, np.int64), "hits": np.full(cap, -7, np.int64)}
+        outs = [arrs[o].ctypes.data_as(C.c_void_p) if o in want else None for o in OUTPUTS] + ([None] if name == "table_window" else [])
+        got = C.c_int64(-7)
+        rc = getattr(ctx.lib, "sdqh_" + name)(ctx.handle, t.handle, C.c_int64(min_hits), *lead[name], C.c_int64(cap), *outs, C.byref(got))
+        calls.append((rc, got.value, arrs, [nm for nm, _ in ctx.profile()]))
+    return calls
+
+
+def test_the_three_entry_points_agree(hip_engine):
+    """One path behind three entry points: for the same underived columns sdqh_table_sorted, sdqh_table_sorted_by and the window call
+    that keeps every row and wants no rank return the same *out_n and bit-identical arrays — the rows numpy's stable lexsort gives —
+    whichever of the output arrays are passed (the emit kernel's null pointers); arrays not passed and rows beyond *out_n keep their
+    fill; a capacity below the count is SDQH_ERR_OVERFLOW with the needed count and nothing written.  The two plain calls launch no
+    window kernel and exactly the kernels recorded from the commit before the paths were merged (tests/golden/order_path_kernels.json:
+    the launches of a call depend on which digits of its keys vary, so they are listed per case)."""
+    import json
+    from test_order_by_gpu import SPECS
+    ctx = hip_engine.ctx
+    S, tile, _ = ctx.sort_geometry()
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "order_path_kernels.json")) as fh:
+        golden = json.load(fh)
+    assert golden["geometry"] == [S, tile]
+    wants = (OUTPUTS, ("keys",), ("values", "hits"))
+    done = 0
+    ctx.set_profiling(1)
+    try:
+        for n in (0, 1, S, S + 1, tile + 1, 3 * tile + 5):
+            t = _probed_table(ctx, n)
+            try:
+                for min_hits in (0, 2):
+                    rows = _stage_rows(ctx, t, min_hits)
+                    m = len(rows[0])
+                    assert m <= n and (n < S or m >= 7), (n, min_hits, m)
+                    tied = False
+                    for si, spec in enumerate(SPECS):
+                        imgs = _images(rows, spec)
+                        order = np.lexsort(imgs[::-1]) if m else np.zeros(0, np.int64)
+                        tied |= m > 1 and bool(np.all([u[order][1:] == u[order][:-1] for u in imgs], axis=0).any())
+                        for want in wants:
+                            cap = m + 3
+                            exp = {"keys": np.full(cap, -7, np.int64), "payload": np.full((2, cap), -7, np.int64),
+                                   "values": np.full((abi.TUPLE_MAX_VALUES, cap), -7, np.int64), "hits": np.full(cap, -7, np.int64)}
+                            if "keys" in want:
+                                exp["keys"][:m] = rows[0][order]
+                            if "payload" in want:
+                                exp["payload"][:, :m] = np.asarray(rows[1])[:2, order]
+                            if "values" in want:                               # (the value rows the table does not have are zeroed)
+                                exp["values"][:, :m] = 0
+                                exp["values"][0, :m] = np.ascontiguousarray(rows[2][0][order]).view(np.int64)
+                            if "hits" in want:
+                                exp["hits"][:m] = rows[3][order]
+                            calls = _entry_point_calls(ctx, t, min_hits, spec, ALL, cap, want)
+                            for name, (rc, got, arrs, kernels) in zip(ENTRY_POINTS, calls):
+                                what = (n, min_hits, si, want, name)
+                                assert (rc, got) == (abi.OK, m), what
+                                for o in OUTPUTS:
+                                    assert (arrs[o] == exp[o]).all(), what + (o,)
+                                if name != "table_window" and want is OUTPUTS:
+                                    assert not [k for k in kernels if k.startswith("k_win")], what
+                                    assert kernels == golden["calls"]["n=%d min_hits=%d spec=%d" % (n, min_hits, si)].split(), what
+                            done += 1
+                        for name, (rc, got, arrs, _) in zip(ENTRY_POINTS, _entry_point_calls(ctx, t, min_hits, spec, 7, 6, OUTPUTS)):
+                            assert (rc, got) == ((abi.ERR_OVERFLOW if m >= 7 else abi.OK), min(7, m)), (n, min_hits, si, name, "limit 7, capacity 6")
+                            assert m < 7 or all((arrs[o] == -7).all() for o in OUTPUTS), (n, min_hits, si, name, "written on overflow")
+                    assert tied or n < S, (n, min_hits, "no tie in any spec: stability is not exercised")
+            finally:
+                t.free()
+    finally:
+        ctx.set_profiling(0)
+    assert done == 6 * 2 * len(SPECS) * 3
 
 
 # 6. argument errors -----------------------------------------------------------------------------------------------------------------------
