@@ -31,6 +31,12 @@ TEXT_RANK_MAX_WIDTH = 128
 # DENSE_RANK OVER (PARTITION BY ... ORDER BY ...) — and the first k rows of every partition
 WINDOW_EXPORTS = ["sdqh_table_window", "sdqh_window_geometry"]
 WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK = 0, 1, 2
+# ... and its fourth (include/sdqh_sort_frames.h, Library.has_window_agg): aggregates over frames of the same partitions — SUM / COUNT /
+# MIN / MAX (measure) OVER (PARTITION BY ... ORDER BY ... <frame>)
+WINDOW_AGG_EXPORTS = ["sdqh_table_window_agg", "sdqh_window_agg_geometry"]
+WAGG_SUM, WAGG_COUNT, WAGG_MIN, WAGG_MAX = 0, 1, 2, 3
+FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
+WAGG_MAX_AGGS = 4
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -93,6 +99,11 @@ class SortTerm(C.Structure):
     """sdqh_sort_term: a sort column and the derivation of what is ordered — field = (uint64(source) / div) % mod + add, then ranks[field]."""
     _fields_ = [("kind", C.c_int32), ("index", C.c_int32), ("descending", C.c_int32), ("is_f64", C.c_int32),
                 ("div", C.c_int64), ("mod", C.c_int64), ("add", C.c_int64), ("ranks", C.c_void_p)]
+
+
+class WindowAgg(C.Structure):
+    """sdqh_window_agg: an aggregate (op, frame) and its measure, named as a SortKey names a column."""
+    _fields_ = [("op", C.c_int32), ("frame", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("_pad", C.c_int32)]
 
 
 SRC_COLUMN, SRC_LOOKUP, SRC_LOOKUP_YEAR = 0, 1, 2
@@ -1153,11 +1164,12 @@ class Context:
         n = n.value
         return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
 
-    def _sorted_call(self, name, table, lead, limit, capacity_hint, want_hits, want_rank=None):
-        """What sdqh_table_sorted, sdqh_table_sorted_by and sdqh_table_window share: arrays sized from capacity_hint, one retry with
-        the exact size after SDQH_ERR_OVERFLOW, the rows sliced to what was written.  lead: the call's arguments between the table and
-        the capacity (the marshalled sort columns / terms among them).  want_rank None: the call has no rank array and a 4-tuple is
-        returned; else a 5-tuple whose last member is the ranks, or None without want_rank."""
+    def _sorted_call(self, name, table, lead, limit, capacity_hint, want_hits, want_rank=None, naggs=0):
+        """What sdqh_table_sorted, sdqh_table_sorted_by, sdqh_table_window and sdqh_table_window_agg share: arrays sized from
+        capacity_hint, one retry with the exact size after SDQH_ERR_OVERFLOW, the rows sliced to what was written.  lead: the call's
+        arguments between the table and the capacity (the marshalled sort columns / terms among them).  want_rank None: the call has
+        no rank array and a 4-tuple is returned; else a 5-tuple whose last member is the ranks, or None without want_rank.  naggs:
+        the last array is naggs x capacity (the aggregates of sdqh_table_window_agg) and the last member its rows, (naggs, n)."""
         fn = getattr(self.lib, "sdqh_" + name)
         cap = max(1, min(int(capacity_hint), int(limit)))
         for attempt in (0, 1):
@@ -1165,7 +1177,7 @@ class Context:
             payload = np.empty((max(1, table.npayload), cap), np.int64) if table.npayload else None
             values = np.empty((TUPLE_MAX_VALUES, cap), np.float64) if table.accumulate else None
             hits = np.empty(cap, np.int64) if want_hits else None
-            rank = np.empty(cap, np.int64) if want_rank else None
+            rank = np.empty((naggs, cap) if naggs else cap, np.int64) if want_rank else None
             n = C.c_int64()
             outs = (_np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits)) + (() if want_rank is None else (_np_ptr(rank),))
             rc = fn(self.handle, table.handle, *lead, C.c_int64(cap), *outs, C.byref(n))
@@ -1177,7 +1189,7 @@ class Context:
         self._after_call(name)
         n = n.value
         rows = (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
-        return rows if want_rank is None else rows + (None if rank is None else rank[:n],)
+        return rows if want_rank is None else rows + (None if rank is None else rank[..., :n],)
 
     def table_sorted(self, table, min_hits, limit, sort, capacity_hint, want_hits=True):
         """ORDER BY over the entries with at least min_hits rows, the first min(limit, n) of them (limit = SORT_ALL: all): sort as
@@ -1233,6 +1245,32 @@ class Context:
         self._need_window("window_geometry")
         a = C.c_int64()
         self._check(self.lib.sdqh_window_geometry(self.handle, C.byref(a)))
+        return a.value
+
+    def _need_window_agg(self, what):
+        if not self.library.has_window_agg:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window aggregate extension (include/sdqh_sort_frames.h)" % (what, self.library.path))
+
+    def table_window_agg(self, table, min_hits, npartition, terms, aggs, limit, capacity_hint, want_hits=True):
+        """Aggregates over window frames of the ordered entries: terms and npartition as table_window takes them; aggs: [(op, frame,
+        kind, index, is_f64)] — op in WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX, frame in FRAME_ROWS / FRAME_RANGE / FRAME_PARTITION,
+        the measure as a sort column is named (COUNT ignores it).  Every selected row is kept; the first min(limit, n) in sorted order.
+        Returns (keys, payload, values, hits, aggs) — aggs one array per aggregate, float64 for a double measure under SUM / MIN / MAX,
+        else int64."""
+        self._need_window_agg("table_window_agg")
+        arr = (WindowAgg * max(1, len(aggs)))()
+        for i, (op, frame, kind, index, is_f64) in enumerate(aggs):
+            arr[i].op, arr[i].frame, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(frame), int(kind), int(index), 1 if is_f64 else 0
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(aggs)), arr, C.c_int64(limit))
+        got = self._sorted_call("table_window_agg", table, lead, limit, capacity_hint, want_hits, True, naggs=max(1, len(aggs)))
+        as_f64 = [op != WAGG_COUNT and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))) for op, _, kind, _, is_f64 in aggs]
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def window_agg_geometry(self):
+        """Sorted positions one wave aggregates per step of sdqh_table_window_agg's tile scan (what the tests size their cases from)."""
+        self._need_window_agg("window_agg_geometry")
+        a = C.c_int64()
+        self._check(self.lib.sdqh_window_agg_geometry(self.handle, C.byref(a)))
         return a.value
 
     def _need_extrema(self, what):
@@ -1494,6 +1532,11 @@ class Library:
             L.sdqh_table_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        self.has_window_agg = self.has_window and all(hasattr(L, s) for s in WINDOW_AGG_EXPORTS)      # ... and aggregates over frames (include/sdqh_sort_frames.h)
+        if self.has_window_agg:
+            L.sdqh_table_window_agg.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_agg_geometry.argtypes = [C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -22,8 +22,9 @@
 //                     One form for every n a stage can hold (references are 32 bits): no second scan level.
 //   k_sort_emit       the first min(limit, n) rows in order, columns as sdqh_table_compact lays them out
 //
-// One path behind the three table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h) and
-// sdqh_table_window (include/sdqh_sort_window.h): select -> order -> rank -> emit (ordered_impl).  What differs between them is
+// One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
+// (include/sdqh_sort_window.h) and sdqh_table_window_agg (include/sdqh_sort_frames.h): select -> order -> rank or aggregate -> emit
+// (ordered_impl).  What differs between them is
 // data, not code:
 //
 //   a TERM            every sort column is a DevSortTerm.  k_sort_keys reads the column (sort_raw) and, for a DERIVED term, takes
@@ -51,6 +52,20 @@
 //                     those counts scanned over the tiles, then the kept positions placed in order (ballot + lanes below: no atomic
 //                     cursor, because order is the contract).  per_limit >= n keeps everything: both are skipped
 //   k_sort_emit       then goes through the kept positions and writes the rank column beside the others
+//   FRAMES            in a window's place (SortFrames).  sdqh_table_window_agg (include/sdqh_sort_frames.h) folds a measure column over
+//                     frames of the same partitions — SUM / COUNT / MIN / MAX OVER (PARTITION BY ... ORDER BY ... ROWS | RANGE | the
+//                     whole partition) — and keeps every row.  Behind k_win_heads, in place of the rank step:
+//
+//   k_wagg_tiles      a wave per tile: every aggregate's 64-bit element of every position (the measure read through perm -> refs ->
+//                     stage once), the tile's carry {the elements folded since its last partition head, or over the whole tile} per
+//                     aggregate, and the tile's first partition head and tie head
+//   k_wagg_scan       a workgroup per aggregate: exclusive segmented scan of the carries over the tiles (win_join's rule)
+//   k_wagg_run        the tile again with its carry-in: a segmented inclusive scan across the lanes (a lane never reaches below its
+//                     partition head's lane), the running carry folded in — the ROWS value of every position, 8 bytes
+//   k_wagg_next / k_wagg_ends
+//                     only for RANGE / PARTITION frames, backwards: the first heads of the later tiles (suffix minimum), then per
+//                     position the last row of its tie run / partition, whose ROWS value is copied: the frames agree bit for bit.
+//                     Row j is sorted position j: the first m values are the output, k_sort_emit writes the rows as for a plain sort
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -63,7 +78,7 @@
 
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
-#include "sdqh_sort_window.h"
+#include "sdqh_sort_frames.h"
 
 using namespace sdqh_host;
 
@@ -510,6 +525,205 @@ __global__ __launch_bounds__(TPB) void k_win_place(const uint32_t* __restrict__ 
         at0 += (uint64_t)__popcll(k);
     }
 }
+// ---- aggregates over window frames (sdqh_table_window_agg) -----------------------------------------------------------------------
+// Every aggregate is a 64-bit ELEMENT per position folded by one of three associative operators (its class): SUM of an integer
+// measure and COUNT add uint64 (two's complement: exact in any association), SUM of a double measure adds doubles, MIN / MAX take the
+// unsigned maximum of the order-preserving image (reversed for MIN; a NaN is 0, which no other double encodes to — the rule of
+// sdqh_extrema.hip).  Each class has a left and right identity: 0, -0.0 (x + -0.0 = x for every x, -0.0 included), 0.
+constexpr int WAGG_ADD_I = 0, WAGG_ADD_F = 1, WAGG_UMAX = 2;
+constexpr unsigned long long WAGG_QNAN = 0x7FF8000000000000ull;
+struct DevWagg { DevSortKey sk; int32_t op, frame, cls, _pad; };      // sk: the measure (desc unused)
+struct DevWaggs { DevWagg a[SDQH_WAGG_MAX_AGGS]; int32_t n, _pad; };
+struct WaggHeads { uint32_t part, tie; };            // positions of a partition head and of a tie head (n: none)
+
+__device__ __forceinline__ uint64_t wagg_identity(int cls) { return cls == WAGG_ADD_F ? (1ull << 63) : 0ull; }
+// left (lower positions) joined with right
+__device__ __forceinline__ uint64_t wagg_join(int cls, uint64_t l, uint64_t r) {
+    if (cls == WAGG_ADD_I) return l + r;
+    if (cls == WAGG_UMAX) return l > r ? l : r;
+    return (uint64_t)__double_as_longlong(__longlong_as_double((long long)l) + __longlong_as_double((long long)r));
+}
+// the element of staged row idx
+__device__ __forceinline__ uint64_t wagg_element(const DevWagg& g, const DevStage& st, int64_t idx, uint32_t hits) {
+    if (g.op == SDQH_WAGG_COUNT) return 1ull;
+    const int64_t raw = sort_raw(g.sk, st, idx, hits);
+    if (g.op == SDQH_WAGG_SUM) return (uint64_t)raw;
+    if (g.sk.is_f64) { const double d = __longlong_as_double(raw); if (d != d) return 0ull; }
+    return sort_bits(raw, g.sk.is_f64, g.op == SDQH_WAGG_MIN);
+}
+// a folded element as the caller reads it: sums and counts as they are, an image decoded (a double frame nothing reached: the quiet NaN)
+__device__ __forceinline__ uint64_t wagg_result(const DevWagg& g, uint64_t e) {
+    if (g.cls != WAGG_UMAX) return e;
+    if (g.sk.is_f64 && e == 0ull) return WAGG_QNAN;
+    const uint64_t u = g.op == SDQH_WAGG_MIN ? ~e : e;
+    if (!g.sk.is_f64) return u ^ (1ull << 63);
+    return (u >> 63) ? (u ^ (1ull << 63)) : ~u;
+}
+// Inclusive scan of one element per lane, restarted at partition heads (Hillis-Steele over the wave): `first` = the lane of the
+// last partition head at or below this lane (none: 0).  A lane takes from lane - d only when that lane is not below `first`; by
+// then it holds everything from max(first, lane - d + 1) on, so nothing is taken twice and nothing of another partition at all.
+__device__ __forceinline__ uint64_t wagg_wave_scan(int cls, uint64_t v, uint32_t lane, uint32_t first) {
+#pragma unroll
+    for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((long long)v, d, WAVE);
+        if (lane >= first + d) v = wagg_join(cls, o, v);
+    }
+    return v;
+}
+// what a wave's batch at [b, ..) knows of lane's partition: the two head ballots, and `first` for wagg_wave_scan
+struct WaggBatch { uint64_t mp, mt, pl; uint32_t first; };
+__device__ __forceinline__ WaggBatch wagg_batch(const uint8_t* __restrict__ heads, uint64_t r, bool live, uint64_t le) {
+    const uint32_t f = live ? heads[r] : 0u;
+    WaggBatch h;
+    h.mp = __ballot(f & WIN_PART); h.mt = __ballot(f & WIN_TIE);
+    h.pl = h.mp & le;
+    h.first = h.pl ? 63u - (uint32_t)__clzll((long long)h.pl) : 0u;
+    return h;
+}
+
+// 1. the element of every position and aggregate (elem[a * stride + r], read through perm -> refs -> stage once: the later passes
+// stay on these arrays), per tile and aggregate the carry — the elements folded since the tile's last partition head, or over the
+// whole tile — and per tile the position of its first partition head and first tie head.  heads: k_win_heads'.
+__global__ __launch_bounds__(TPB) void k_wagg_tiles(DevStage st, DevWaggs ag, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ heads,
+                                                   uint32_t n, size_t stride, uint64_t* __restrict__ elem, uint64_t* __restrict__ tval, WaggHeads* __restrict__ tfirst, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint64_t run[SDQH_WAGG_MAX_AGGS];
+#pragma unroll
+    for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) run[a] = wagg_identity(ag.a[a].cls);
+    WaggHeads fh = {n, n};
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        if (h.mp && fh.part == n) fh.part = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (h.mt && fh.tie == n) fh.tie = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mt);
+        const uint32_t g = live ? (perm ? perm[r] : (uint32_t)r) : n;
+        const bool ok = g < n;                                           // (a permutation of [0, n): every live lane)
+        const int64_t idx = ok ? (int64_t)refs[g] : 0;
+        const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u;
+        const int last = (int)min((uint64_t)WAVE, r1 - b) - 1;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) {
+            const int cls = ag.a[a].cls;
+            const uint64_t e = ok ? wagg_element(ag.a[a], st, idx, hits) : wagg_identity(cls);
+            if (live) elem[(size_t)a * stride + r] = e;
+            const uint64_t s = wagg_wave_scan(cls, e, lane, h.first);
+            const uint64_t tail = (uint64_t)__shfl((long long)s, last, WAVE);          // since the batch's last head, or the whole batch
+            run[a] = h.mp ? tail : wagg_join(cls, run[a], tail);
+        }
+    }
+    if (lane == 0) {
+        tfirst[w] = fh;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) tval[(size_t)a * ntiles + w] = run[a];
+    }
+}
+// 2. workgroup a: exclusive segmented scan of aggregate a's tile carries, in place — k_win_scan's shape and win_join's rule (a right
+// side with a partition head wins); the operator is not commutative where it matters (doubles): left operand = lower tiles
+__global__ __launch_bounds__(TPB) void k_wagg_scan(DevWaggs ag, const WaggHeads* __restrict__ tfirst, uint32_t n, uint64_t* __restrict__ tval, uint32_t ntiles) {
+    __shared__ uint64_t s_v[TPB];
+    __shared__ uint32_t s_f[TPB];
+    const int cls = ag.a[blockIdx.x].cls;
+    const uint64_t id = wagg_identity(cls);
+    uint64_t* __restrict__ v = tval + (size_t)blockIdx.x * ntiles;
+    const uint32_t per = (ntiles + TPB - 1) / TPB;
+    const uint64_t b0 = (uint64_t)threadIdx.x * per, b1 = min((uint64_t)ntiles, b0 + per);
+    uint64_t sum = id; uint32_t f = 0u;
+    for (uint64_t b = b0; b < b1; ++b) { const bool hf = tfirst[b].part < n; sum = hf ? v[b] : wagg_join(cls, sum, v[b]); f |= hf ? 1u : 0u; }
+    s_v[threadIdx.x] = sum; s_f[threadIdx.x] = f;
+    __syncthreads();
+    for (int off = 1; off < TPB; off <<= 1) {
+        uint64_t av = id; uint32_t af = 0u;
+        if ((int)threadIdx.x >= off) { av = s_v[threadIdx.x - off]; af = s_f[threadIdx.x - off]; }
+        __syncthreads();
+        if (!s_f[threadIdx.x]) { s_v[threadIdx.x] = wagg_join(cls, av, s_v[threadIdx.x]); s_f[threadIdx.x] = af; }
+        __syncthreads();
+    }
+    uint64_t run = threadIdx.x > 0 ? s_v[threadIdx.x - 1] : id;
+    for (uint64_t b = b0; b < b1; ++b) { const uint64_t x = v[b]; v[b] = run; run = tfirst[b].part < n ? x : wagg_join(cls, run, x); }
+}
+// 3. the tile again with its carry-in, 64 positions at a time: the segmented scan across the lanes, the running carry folded into
+// the lanes whose partition started before the batch; elem[a * stride + r] becomes aggregate a's ROWS value of position r, decoded
+__global__ __launch_bounds__(TPB) void k_wagg_run(DevWaggs ag, const uint8_t* __restrict__ heads, uint32_t n, size_t stride, uint64_t* __restrict__ elem,
+                                                 const uint64_t* __restrict__ tval, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint64_t run[SDQH_WAGG_MAX_AGGS];
+#pragma unroll
+    for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) run[a] = a < ag.n ? tval[(size_t)a * ntiles + w] : 0ull;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const int last = (int)min((uint64_t)WAVE, r1 - b) - 1;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) {
+            const int cls = ag.a[a].cls;
+            const uint64_t e = live ? elem[(size_t)a * stride + r] : wagg_identity(cls);
+            const uint64_t s = wagg_wave_scan(cls, e, lane, h.first);
+            const uint64_t v = h.pl ? s : wagg_join(cls, run[a], s);
+            if (live) elem[(size_t)a * stride + r] = wagg_result(ag.a[a], v);
+            run[a] = (uint64_t)__shfl((long long)v, last, WAVE);        // (the last live lane has seen every head of the batch)
+        }
+    }
+}
+// 4. one workgroup: for every tile the first partition head and the first tie head of the tiles AFTER it (n: none) — an exclusive
+// suffix minimum of tfirst over the tiles (positions grow with the tile, "none" is n, the largest)
+__device__ __forceinline__ WaggHeads wagg_min(const WaggHeads& a, const WaggHeads& b) { return WaggHeads{min(a.part, b.part), min(a.tie, b.tie)}; }
+__global__ __launch_bounds__(TPB) void k_wagg_next(const WaggHeads* __restrict__ tfirst, uint32_t n, WaggHeads* __restrict__ tnext, uint32_t ntiles) {
+    __shared__ WaggHeads s_h[TPB];
+    const uint32_t per = (ntiles + TPB - 1) / TPB;
+    const uint64_t b0 = min((uint64_t)ntiles, (uint64_t)threadIdx.x * per), b1 = min((uint64_t)ntiles, b0 + per);
+    WaggHeads mine = {n, n};
+    for (uint64_t b = b0; b < b1; ++b) mine = wagg_min(mine, tfirst[b]);
+    s_h[threadIdx.x] = mine;
+    __syncthreads();
+    for (int off = 1; off < TPB; off <<= 1) {
+        WaggHeads o = {n, n};
+        if ((int)threadIdx.x + off < TPB) o = s_h[threadIdx.x + off];
+        __syncthreads();
+        s_h[threadIdx.x] = wagg_min(s_h[threadIdx.x], o);
+        __syncthreads();
+    }
+    WaggHeads run = {n, n};
+    if (threadIdx.x + 1 < TPB) run = s_h[threadIdx.x + 1];
+    for (uint64_t b = b1; b > b0; --b) { const WaggHeads x = tfirst[b - 1]; tnext[b - 1] = run; run = wagg_min(run, x); }
+}
+// 5. the RANGE and PARTITION values of the first m positions (only launched when some aggregate asks for one): a tile walked
+// backwards, the next tie head / partition head after a position read off the ballots above its lane, else off the batches and
+// tiles behind; the value is the ROWS value of the position before that head — a copy, so the frames agree bit for bit
+__global__ __launch_bounds__(TPB) void k_wagg_ends(DevWaggs ag, const uint8_t* __restrict__ heads, const WaggHeads* __restrict__ tnext, uint32_t n, uint32_t m, size_t stride,
+                                                  const uint64_t* __restrict__ rows, uint64_t* __restrict__ fin, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;                       // ntiles: the tiles that hold a position below m
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    WaggHeads next = tnext[w];
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const uint64_t pg = h.mp & ~le, tg = h.mt & ~le;
+        const uint32_t pe = (pg ? (uint32_t)b + (uint32_t)__builtin_ctzll(pg) : next.part) - 1u;
+        const uint32_t te = (tg ? (uint32_t)b + (uint32_t)__builtin_ctzll(tg) : next.tie) - 1u;
+        if (live && r < m) {
+#pragma unroll
+            for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n && ag.a[a].frame != SDQH_FRAME_ROWS) {
+                const uint32_t e = ag.a[a].frame == SDQH_FRAME_RANGE ? te : pe;
+                if (e < n) fin[(size_t)a * stride + r] = rows[(size_t)a * stride + e];     // (r <= e < n: always)
+            }
+        }
+        if (h.mp) next.part = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (h.mt) next.tie = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mt);
+        if (b == r0) break;
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -704,18 +918,21 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 
 // the optional third step of ordered_impl: ranks of `kind` inside partitions by the first npart terms, rows with rank <= per_limit kept
 struct SortWindow { int npart, kind; int64_t per_limit; int64_t* out_rank; };
+// ... or, in its place, aggregates over frames of the same partitions (sdqh_table_window_agg): every row kept, out[a * capacity + j]
+struct SortFrames { int npart; DevWaggs aggs; int64_t* out; };
 
-// The three table entry points behind their argument checks: select -> order -> rank (win != nullptr) -> emit.  who: the entry
-// point's name in messages.
+// The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr; never
+// both) -> emit.  who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
-                        int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+                        const SortFrames* frames, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     const std::string me(who);
     int64_t* out_rank = win ? win->out_rank : nullptr;
+    const SortFrames* fr = frames && frames->out ? frames : nullptr;     // (no array for them: rows only, no aggregate pass)
     Scratch scratch(ctx);
     SortState s;
     if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
-    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank;
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr;
     const bool all_kept = !win || win->per_limit >= n;               // a rank is at most n: nothing to filter, the count is known
     const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
     const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
@@ -729,33 +946,62 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
     const uint32_t un = (uint32_t)n;
     uint32_t *rank = nullptr, *sel = nullptr;
-    if (win) {
-        // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack]
+    const size_t agg_stride = round_up((size_t)n * 8) / 8;           // aggregate a's values start at a * agg_stride
+    const uint64_t* agg_rows = nullptr; const uint64_t* agg_fin = nullptr;
+    if (win || fr) {
+        // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack] for a window, [heads | tile carries |
+        // ROWS values | RANGE / PARTITION values | value carries | first heads per tile | next heads per tile] for frames
         const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+        const size_t na = fr ? (size_t)fr->aggs.n : 0;
+        bool ends = false;                                            // does some aggregate ask for RANGE or PARTITION?
+        for (size_t a = 0; a < na; ++a) ends |= fr->aggs.a[a].frame != SDQH_FRAME_ROWS;
         uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t* tile_kept = nullptr;
+        uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
         if (!carve(ctx, scratch.p[3], [&](Carver& c) {
                 heads = c.take<uint8_t>((size_t)n);
                 carry = c.take<WinCarry>(ntiles);
-                rank = c.take<uint32_t>((size_t)n);
-                tile_kept = c.take<uint32_t>(ntiles);
-                sel = all_kept ? nullptr : c.take<uint32_t>((size_t)n);
-                (void)c.take<char>(256);
+                if (win) {
+                    rank = c.take<uint32_t>((size_t)n);
+                    tile_kept = c.take<uint32_t>(ntiles);
+                    sel = all_kept ? nullptr : c.take<uint32_t>((size_t)n);
+                    (void)c.take<char>(256);
+                }
+                if (fr) {
+                    elem = c.take<uint64_t>(agg_stride * na);
+                    fin = c.take<uint64_t>(ends ? agg_stride * na : 0);
+                    tval = c.take<uint64_t>((size_t)ntiles * na);
+                    tfirst = c.take<WaggHeads>(ntiles);
+                    tnext = c.take<WaggHeads>(ends ? ntiles : 0);
+                }
             })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-        const uint64_t pl = (uint64_t)win->per_limit;
-        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, win->npart, nsort, s.perm, un, heads, carry, ntiles);
-        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-        LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, win->kind, pl, rank, tile_kept, ntiles);
-        if (!all_kept) {                                              // the kept positions counted, the ways out again, then placed
-            LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (int rc = sync_stream(ctx)) return rc;
-            unsigned long long kept;
-            std::memcpy(&kept, ctx->result_host, 8);
-            m = std::min<int64_t>(limit, (int64_t)kept);
-            if (count_only || m == 0) return done(m);
-            if (m > capacity) return overflow(m);
-            LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
+        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, win ? win->npart : fr->npart, nsort, s.perm, un, heads, carry, ntiles);
+        if (fr) {                                                     // every position is kept: row j is sorted position j, the first m values are the output
+            LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, table->stage, fr->aggs, s.refs, s.perm, heads, un, agg_stride, elem, tval, tfirst, ntiles);
+            LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, fr->aggs, tfirst, un, tval, ntiles);
+            LAUNCH(ctx, "k_wagg_run", k_wagg_run, tgrid, fr->aggs, heads, un, agg_stride, elem, tval, ntiles);
+            if (ends) {
+                const uint32_t mtiles = (uint32_t)((m + SORT_TILE - 1) / SORT_TILE);
+                LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
+                LAUNCH(ctx, "k_wagg_ends", k_wagg_ends, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), fr->aggs, heads, tnext, un, (uint32_t)m, agg_stride, elem, fin, mtiles);
+            }
+            agg_rows = elem; agg_fin = fin;
+        }
+        if (win) {
+            const uint64_t pl = (uint64_t)win->per_limit;
+            LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+            LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, win->kind, pl, rank, tile_kept, ntiles);
+            if (!all_kept) {                                          // the kept positions counted, the ways out again, then placed
+                LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+                if (int rc = sync_stream(ctx)) return rc;
+                unsigned long long kept;
+                std::memcpy(&kept, ctx->result_host, 8);
+                m = std::min<int64_t>(limit, (int64_t)kept);
+                if (count_only || m == 0) return done(m);
+                if (m > capacity) return overflow(m);
+                LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
+            }
         }
     }
     *out_n = m;
@@ -767,6 +1013,13 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, (uint32_t)m, r.o, r.extra);
     }
     call_end(ctx);                                                    // the call's device time ends here: the fetch is the host's
+    if (fr) {                                                         // the aggregates' first m values, each from the array its frame left them in
+        for (int a = 0; a < fr->aggs.n; ++a) {
+            const uint64_t* from = (fr->aggs.a[a].frame == SDQH_FRAME_ROWS ? agg_rows : agg_fin) + (size_t)a * agg_stride;
+            HIP_TRY(ctx, hipMemcpyAsync(fr->out + (size_t)a * (size_t)capacity, from, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        if (!r.narr) if (int rc = sync_stream(ctx)) return rc;
+    }
     if (r.narr) if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
     if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
     return SDQH_OK;
@@ -820,7 +1073,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
@@ -828,7 +1081,7 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hit
     if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -840,7 +1093,40 @@ int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
     const SortWindow win = {npartition, kind, per_limit, out_rank};
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                          int naggs, const sdqh_window_agg* aggs, int64_t limit, int64_t capacity,
+                          int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
+    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && aggs && naggs >= 1 && naggs <= SDQH_WAGG_MAX_AGGS;
+    for (int a = 0; ok && a < naggs; ++a)
+        ok = aggs[a].op >= SDQH_WAGG_SUM && aggs[a].op <= SDQH_WAGG_MAX && aggs[a].frame >= SDQH_FRAME_ROWS && aggs[a].frame <= SDQH_FRAME_PARTITION;
+    if (int rc = sort_enter(ctx, table, "table_window_agg", ok)) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_window_agg", nterms, in, false, terms)) return rc;
+    SortFrames fr; std::memset(&fr, 0, sizeof(fr));
+    fr.npart = npartition; fr.out = out_aggs; fr.aggs.n = naggs;
+    for (int a = 0; a < naggs; ++a) {
+        const sdqh_window_agg& g = aggs[a];
+        DevWagg& d = fr.aggs.a[a];
+        d.op = g.op; d.frame = g.frame;
+        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
+            const std::string agg = "table_window_agg: aggregate " + std::to_string(a);
+            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
+            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
+            d.sk.kind = g.kind; d.sk.index = g.index;
+            d.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
+        }
+        d.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op == SDQH_WAGG_SUM && d.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I);
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_window_agg_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
+    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_agg_geometry: bad arguments");
+    *tile_rows = SORT_TILE;
+    return SDQH_OK;
 }
 
 int sdqh_window_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {

@@ -125,6 +125,64 @@ def check_window_columns(req, columns):
             raise KeyError("window: the result has no column %r" % nm)
     if req.name is not None and req.name in columns:
         raise KeyError("window: the result already has a column %r" % req.name)
+    for name, _, col, _ in getattr(req, "aggs", ()):
+        if col is not None and col not in columns:
+            raise KeyError("over: the result has no column %r" % col)
+        if name in columns:
+            raise KeyError("over: the result already has a column %r" % name)
+
+
+WAGG_OPS = ("sum", "count", "min", "max")                 # their positions are abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX
+FRAMES = ("rows", "range", "partition")                   # ... abi.FRAME_ROWS / FRAME_RANGE / FRAME_PARTITION
+
+
+class FrameRequest(WindowRequest):
+    """Aggregates over window frames, travelling where a WindowRequest travels (every row is kept: it reads as ROW_NUMBER with no
+    per-group limit and no rank column): [0] = the limit on the whole result, [1] = the PARTITION BY terms followed by the ORDER BY
+    terms, npartition, and aggs = [(name of the new column, op: a name of WAGG_OPS, measure column or None for a count, frame: a
+    name of FRAMES)] in the order the columns are appended."""
+
+    def __new__(cls, k, terms, npartition, aggs):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.aggs = [(str(n), str(op), None if col is None else str(col), str(fr)) for n, op, col, fr in aggs]
+        if not self.aggs or any(op not in WAGG_OPS or fr not in FRAMES or (col is None and op != "count") for _, op, col, fr in self.aggs):
+            raise ValueError("over: bad aggregate")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
+        names = names or {}
+        return FrameRequest(self[0], terms, self.npartition, [(n, op, names.get(col, col), fr) for n, op, col, fr in self.aggs])
+
+
+def frame_request(columns, by, order, aggs, frame="range", k=WINDOW_ALL):
+    """The checked FrameRequest of `over`: by / order as window_request takes them; aggs = {new column: (op, measure column or None)
+    or (op, measure, frame)} with op a name of WAGG_OPS and frame a name of FRAMES (default: `frame`).  columns: the result's column
+    names when they are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has
+    already, ValueError for everything else."""
+    req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("over: aggs is a non-empty dict {new column: (op, measure[, frame])}")
+    if frame not in FRAMES:
+        raise ValueError("over: frame is one of %s, not %r" % (", ".join(FRAMES), frame))
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (2, 3):
+            raise ValueError("over: an aggregate is name: (op, measure[, frame])")
+        op, col, fr = spec[0], spec[1], (spec[2] if len(spec) == 3 else frame)
+        if op not in WAGG_OPS:
+            raise ValueError("over: op is one of %s, not %r" % (", ".join(WAGG_OPS), op))
+        if fr not in FRAMES:
+            raise ValueError("over: frame is one of %s, not %r" % (", ".join(FRAMES), fr))
+        if col is None and op != "count":
+            raise ValueError("over: %s needs a measure column" % op)
+        if col is not None and not isinstance(col, str):
+            raise ValueError("over: a measure is a column name")
+        out.append((name, op, col, fr))
+    req = FrameRequest(req[0], req[1], req.npartition, out)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
 
 
 def order_image(a, descending):
@@ -238,28 +296,10 @@ class ResultSet:
             raise ValueError("window: unknown kind")
         if int(per_limit) < 1 or int(k) < 1:
             raise ValueError("window: k must be at least 1")
-        terms = [(b, "asc") if isinstance(b, str) else (b[0], b[1]) for b in by]
-        npartition = len(terms)
-        terms += [(o, "asc") if isinstance(o, str) else (o[0], o[1]) for o in order]
-        images = []
-        for name, direction in terms:
-            if name not in self.columns:
-                raise KeyError("window: the result has no column %r" % name)
-            if direction not in ("asc", "desc"):
-                raise ValueError("window: directions are 'asc' or 'desc'")
-            images.append(order_image(self.column(name), direction == "desc"))
+        idx, part_head, tie_head = self._window_heads(by, order)
         n = self._n
-        idx = np.lexsort(images[::-1]) if images else np.arange(n)      # lexsort is stable: ties keep the stored order
         if n == 0:
             return idx[:0], np.zeros(0, np.int64)
-        part_head = np.zeros(n, bool)
-        tie_head = np.zeros(n, bool)
-        part_head[0] = tie_head[0] = True
-        for i, u in enumerate(images):
-            differ = u[idx][1:] != u[idx][:-1]
-            tie_head[1:] |= differ
-            if i < npartition:
-                part_head[1:] |= differ
         pos = np.arange(n, dtype=np.int64)
         part_start = np.maximum.accumulate(np.where(part_head, pos, 0))
         if kind == 0:
@@ -272,8 +312,89 @@ class ResultSet:
         keep = rank <= int(per_limit)
         return idx[keep][:int(k)], rank[keep][:int(k)].astype(np.int64)
 
+    def _window_heads(self, by, order):
+        """(the stored rows' indices in the order of `by` then `order`, ties in stored order; per sorted position: does a partition
+        start here, does a tie run start here) — the order, partitions and ties of sdqh_table_window."""
+        terms = [(b, "asc") if isinstance(b, str) else (b[0], b[1]) for b in by]
+        npartition = len(terms)
+        terms += [(o, "asc") if isinstance(o, str) else (o[0], o[1]) for o in order]
+        images = []
+        for name, direction in terms:
+            if name not in self.columns:
+                raise KeyError("window: the result has no column %r" % name)
+            if direction not in ("asc", "desc"):
+                raise ValueError("window: directions are 'asc' or 'desc'")
+            images.append(order_image(self.column(name), direction == "desc"))
+        n = self._n
+        idx = np.lexsort(images[::-1]) if images else np.arange(n)      # lexsort is stable: ties keep the stored order
+        part_head = np.zeros(n, bool)
+        tie_head = np.zeros(n, bool)
+        if n:
+            part_head[0] = tie_head[0] = True
+        for i, u in enumerate(images):
+            differ = u[idx][1:] != u[idx][:-1]
+            tie_head[1:] |= differ
+            if i < npartition:
+                part_head[1:] |= differ
+        return idx, part_head, tie_head
+
+    def framed(self, req):
+        """Every row in a FrameRequest's order (the first req[0] of them) with its aggregate columns appended: what
+        sdqh_table_window_agg does on the device (include/sdqh_sort_frames.h), on the host.  Per partition a running fold in row
+        order — np.cumsum for SUM (int64 wraps), a running maximum of the order-preserving images for MIN / MAX (NaNs skipped, -0.0
+        below +0.0, nothing but NaNs: NaN) — which is the ROWS value; RANGE / PARTITION rows take the ROWS value of the last row of
+        their tie run / partition.  int64 for COUNT and integer measures, float64 otherwise."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, part_head, tie_head = self._window_heads(req.by, req.order)
+        n = self._n
+        starts = np.nonzero(part_head)[0]
+        stops = np.append(starts[1:], n)
+
+        def last_of(head):                                           # per position: the last position of its run of `head`
+            at = np.nonzero(head)[0]
+            return (np.append(at[1:], n) - 1)[np.cumsum(head) - 1] if n else np.zeros(0, np.int64)
+        ends = {"range": last_of(tie_head), "partition": last_of(part_head)}
+        top = np.uint64(1) << np.uint64(63)
+        new = []
+        for name, op, col, frame in req.aggs:
+            x = None if op == "count" else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("over: %s of column %r: the measure is not numeric" % (op, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            if op in ("count", "sum"):
+                v = np.ones(n, np.int64) if op == "count" else np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+                fold = np.add
+            else:                                                    # the images of sdqh_extrema.h: unsigned maximum, reversed for MIN, NaN = 0
+                v = order_image(x, op == "min")
+                if is_f:
+                    v = np.where(np.isnan(x), np.uint64(0), v)
+                fold = np.maximum
+            rows = np.empty_like(v)
+            for a, b in zip(starts, stops):
+                fold.accumulate(v[a:b], out=rows[a:b])
+            if op in ("min", "max"):
+                u = ~rows if op == "min" else rows
+                if is_f:
+                    bits = np.where(u >> np.uint64(63) != 0, u ^ top, ~u)
+                    rows = np.where(rows == 0, np.uint64(0x7FF8000000000000), bits).view(np.float64)
+                else:
+                    rows = (u ^ top).view(np.int64)
+            new.append((name, rows if frame == "rows" else rows[ends[frame]]))
+        k = max(0, min(int(req[0]), n))
+        cols = [a[idx[:k]] for a in self._cols]                          # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [a[:k] for _, a in new])
+
+    def over(self, by, order, aggs, frame="range"):
+        """Every row, ordered by `by` then `order`, plus one column per aggregate over the row's frame inside its group of `by`:
+        aggs = {new column: (op, measure column or None[, frame])}, op in WAGG_OPS, frame in FRAMES ("rows": group start .. this
+        row; "range": .. the last row tied with this one, SQL's default; "partition": the whole group)."""
+        return self.framed(frame_request(self.columns, by, order, aggs, frame))
+
     def windowed(self, req):
-        """The rows a WindowRequest keeps, in its order, with its rank column when it names one."""
+        """The rows a WindowRequest keeps, in its order, with its rank column when it names one (a FrameRequest: framed)."""
+        if isinstance(req, FrameRequest):
+            return self.framed(req)
         self._wait()
         check_window_columns(req, self.columns)
         idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])

@@ -411,10 +411,24 @@ def sdql_compile(in_type):
             from . import abi
             return _windowed(list(by), list(order), kind, abi.SORT_ALL, name)
 
+        def over(by, order, aggs, frame="range"):
+            """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a window frame inside the row's
+            group of `by`: aggs = {new column: (op, measure column or None[, frame])}, op in "sum" / "count" / "min" / "max", frame
+            in "rows" (group start .. this row) / "range" (.. the last row tied with this one: SQL's default) / "partition" (the
+            whole group), e.g. ``q3.over(["o_orderdate"], [("revenue", "desc")], {"running": ("sum", "revenue"), "n": ("count",
+            None, "partition")})(li, cu, ord)``.  int64 for counts and integer measures, float64 otherwise."""
+            from . import engine, frontend
+            from .result import frame_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = frame_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, frame)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
         wrapper.numbered = numbered
+        wrapper.over = over
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
