@@ -1358,10 +1358,8 @@ __device__ __forceinline__ void pass_pairs(const DevFilter& f, const DevProbes& 
 // payload column count known at compile time (NPAY >= 0) or read from the arguments (-1)
 template <int NPAY> __device__ __forceinline__ int cfg_npay(const int32_t n) { if constexpr (NPAY >= 0) return NPAY; else return n; }
 
-// (Round 3 tried setting the bitmap bits of a drain's 64 rows by the wave together — equal words of adjacent lanes ORed first by a
-// segmented scan, one atomic per run, and plain stores for the runs strictly inside a wave's range of a strictly increasing key
-// column.  Merged atomics alone: Q3's orders build 0.128 -> 0.144 ms, the scan costs more than the atomics it saves.  With the
-// plain stores: wrong results at SF=1 — plain stores and memory-side atomics do not mix on one cache line.  One atomic per row stays.)
+// (Tried in round 3 and lost: a wave's bitmap bits merged by a segmented scan into one atomic per word, with plain stores inside its range —
+//  slower, and wrong with the plain stores.  One atomic per row stays.  Record: profiles/HISTORY.md, §3c "Did not work".)
 template <int NPAY>
 __device__ __forceinline__ void stage_store(const DevStage& st, int64_t pos, int64_t key, const int64_t (&pay)[MAX_STAGE_COLS], bool opens_run = true) {
     st.key[pos] = key;
@@ -1372,9 +1370,6 @@ __device__ __forceinline__ void stage_store(const DevStage& st, int64_t pos, int
     if (st.bm) {
         uint64_t off;
         if (bm_locate(st, key, off)) {
-#if defined(XS_EXP) && (XS_EXP & 1)
-            if (key == -12345)                                // (timing experiment of the specialised builds: no bitmap atomics)
-#endif
             atomicOr(&st.bm[off >> 5], 1u << (off & 31));     // fire and forget; duplicates show up as distinct < staged (k_rank_words)
             // grouped layout: off = the high part's offset (bm_shift 32, no rectangle).  opens_run false: the caller knows the entry stored just
             // before this one (the wave's previous kept lane) has the same high part — the run's first stage row is not this one

@@ -966,7 +966,6 @@ std::string generate_vstage(const XInfo& x) {
     const std::string row = g.os.str();
     const std::vector<std::pair<int, int>> tabs = g.tabs;
     std::ostringstream out;
-    if (const char* e = std::getenv("SDQLPY_AMD_XV_EXP")) out << "#define XV_EXP " << std::atoi(e) << "\n";      // (timing experiments: x_vstage8)
     out << "#include \"sdqh_xkernels.hpp\"\nusing namespace sdqh;\n";
     bool q32 = x.irange[p->key] >= 1;                                     // key and payload fit 32 bits: a queue of 4-byte words
     for (int v = 0; v < p->nvals; ++v) q32 = q32 && p->ops[p->vals[v]].type == SDQH_T_I64 && x.irange[p->vals[v]] >= 1;
@@ -1325,7 +1324,7 @@ int kernel_for(sdqh_ctx* ctx, const XInfo& x, Sink sink, bool direct, hipFunctio
 
 int specialise(sdqh_ctx* ctx, const std::string& source_in, const std::string& entry, hipFunction_t* fn) {
     // SDQLPY_AMD_X_DEFINES="NAME=VALUE NAME=VALUE": macros put in front of every specialised source (A/B switches of the skeletons,
-    // e.g. X8_PIPE=1; part of the source, so of the cache key)
+    // e.g. X8_U_STEPS=3; part of the source, so of the cache key)
     std::string source = source_in;
     if (const char* defs = std::getenv("SDQLPY_AMD_X_DEFINES")) {
         std::istringstream in(defs); std::string tok, head;

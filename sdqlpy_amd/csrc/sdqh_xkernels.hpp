@@ -16,39 +16,10 @@
 #pragma once
 #include "sdqh_kernels.hpp"
 
-// A/B switches of the skeletons (SDQLPY_AMD_X_DEFINES puts macros in front of a specialised source; defaults here)
+// Macros of the skeletons (the generator, or SDQLPY_AMD_X_DEFINES, puts them in front of a specialised source; defaults here and at
+// X_PIN / X8_U_STEPS).  A switch for an A/B measurement leaves with the change that measured it: tests/test_abi_cpu.py holds the list.
 #ifndef XGL_IVAL
 #define XGL_IVAL -1                                                   // the per-lane group sink: index of the summed value that arrives as a small integer (see XGroupLane), or -1
-#endif
-#ifndef XE_EXP
-#define XE_EXP 0                                                      // timing experiments of the entry sink (wrong results): 1 no atomics, 2 no count atomic
-#endif
-#ifndef X8_DRAIN_AT
-#define X8_DRAIN_AT WAVE                                              // x_queue8 drains the front of its queue once this many rows wait (64: only whole waves)
-#endif
-#ifndef X8_EXP
-#define X8_EXP 0                                                      // timing experiments of x_queue8 (wrong results): 1 no bitmap requests, 2 nothing queued, 3 queued but never drained, 4 drained rows evaluated twice, 5 nothing reaches the sink (final loops only; 6.. : XGroup's own, see there)
-#endif
-#ifndef X8_EXP_MINROWS
-#define X8_EXP_MINROWS 0                                              // experiments 3 and 14 leave loops over fewer rows alone (a build that feeds the build under test)
-#endif
-#ifndef X8_EXP_BUILD
-#define X8_EXP_BUILD 0                                                // 1: the timing experiments touch the BUILD loops (stage / key-set sinks) instead of the final ones
-#endif
-#ifndef X8_PIPE
-#define X8_PIPE 0                                                     // x_queue8: the next double step's streamed loads requested behind this step's bitmap words (see there)
-#endif
-#ifndef XV_MASKED
-#define XV_MASKED 0                                                   // x_vstage8: bitmap words requested by the lanes whose row passed the conditions so far only
-#endif
-#ifndef XV_OFFALL
-#define XV_OFFALL 0
-#endif
-#ifndef XV_BITS
-#define XV_BITS 0                                                     // x_vstage8: the key bitmap's words assembled per wave in LDS and stored, where the build key increases (see there: slower)
-#endif
-#ifndef XV_PIPE
-#define XV_PIPE 1                                                     // x_vstage8: the next step's streamed loads requested behind this step's bitmap words (see there)
 #endif
 
 namespace sdqh {
@@ -335,7 +306,6 @@ __device__ __forceinline__ int64_t x_hits(const DevTable& t, uint32_t ent) {
 
 // ---- K-A: sums of NV doubles + a row count; one partial per workgroup, folded by k_sum_partials ----
 template <int NV> struct XSum {
-    static constexpr bool FINAL = true;                               // (the timing experiments of the queue skeleton touch final loops only: a build they emptied would change the loop under test)
     static constexpr bool PIPELINED = false;                          // x_tight: two tiles in flight per step (many waves per SIMD cover the latency)
     struct Args { double* partial; };
     double acc[NV > 0 ? NV : 1];
@@ -367,7 +337,6 @@ template <int NV> struct XSum {
 
 // ---- K-C over a small group domain: LDS hash table per workgroup, f64 LDS atomics, slot-major partials ----
 template <int NV> struct XGroup {
-    static constexpr bool FINAL = true;
     static constexpr bool PIPELINED = false;
     struct Args { unsigned long long* gkeys; double* pacc; int64_t* pcnt; int* flags; };
     static constexpr int NVS = NV > 0 ? NV : 1;
@@ -390,31 +359,14 @@ template <int NV> struct XGroup {
     }
     __device__ __forceinline__ void consume(const XArgs&, const Args&, bool pass, int64_t, const XOut<NV>& o) {
         if (!pass) return;
-#if X8_EXP == 11
-        { asm volatile("s_nop 0"); return; }                                 // (timing experiment: rows reach the sink, which does nothing; no epilogue)
-#endif
-#if X8_EXP == 12
-        { asm volatile("s_nop 0" :: "v"(o.key), "v"(o.val[0])); return; }    // (timing experiment: ... but needs the row's key and value)
-#endif
         if (o.bad || o.key < 0) { atomicOr(&s_flags[0], 2); return; }
-#if X8_EXP == 8 || X8_EXP == 9
-        const int slot = (int)((unsigned long long)o.key & (LG_SLOTS - 1));      // (timing experiment: no hashing, no probing; 9: and no epilogue)
-        s_keys[slot] = (unsigned long long)o.key;
-#else
         const int slot = group_slot(s_keys, (unsigned long long)o.key, false);
-#endif
         if (slot < 0) { atomicOr(&s_flags[0], 1); return; }
-#if X8_EXP == 7
-        if (slot != 100000) return;                                         // (timing experiment: the slot found, nothing added)
-#endif
 #pragma unroll
         for (int k = 0; k < NV; ++k) atomicAdd(&s_acc[slot][k], x_f(o.val[k]));
         atomicAdd(&s_cnt[slot], 1ull);
     }
     __device__ __forceinline__ void finish(const XArgs&, const Args& s) {
-#if X8_EXP == 6 || X8_EXP == 9 || X8_EXP == 10 || X8_EXP == 11 || X8_EXP == 12 || X8_EXP == 14
-        if (s.gkeys != nullptr) return;                                     // (timing experiment: no epilogue)
-#endif
         __syncthreads();
         for (int i = threadIdx.x; i < LG_SLOTS; i += TPB) {
             if (s_keys[i] != EMPTY_GROUP && s_cnt[i] > 0) {
@@ -436,91 +388,19 @@ template <int NV> struct XGroup {
 };
 
 // ---- K-B: survivors compacted in row order into the wave segment's slice of the stage ----
-// Round 6, measured and left OFF (XS_LINES=1 turns it on): the survivors through a ring of XS_RING rows per wave in LDS, reaching the stage
-// arrays XS_FLUSH rows at a time — whole 128-byte lines of every array — instead of what each consume() call's 64 lanes kept (1.5 rows
-// per call in Q5's orders build, where 2.3 % of the rows survive).  The suspicion was that the L2 fills every line it is handed a part
-// of: that build reads 243 MB (2 x FETCH_SIZE) for a 92 MB stream.  tools/build_bytes.sh took it apart (profiles/r06_build_bytes_*.txt):
-// 92 MB with the survivors queued and never drained; 93 MB drained and EVALUATED with nothing reaching the sink — the looked-up customer
-// entries are L2 hits, not the 217 MB the round-5 review asked about —; 243 MB with the sink.  With whole-line stores: 242 MB and the same
-// 0.062 ms.  So it is not the stage arrays: it is the sink's INDEX part — one memory-side atomicOr per entry into a 7.5 MB bitmap and one
-// 4-byte row-index note into a 7.5 MB array, 340 K entries scattered over 60 M key values, each a 64-byte read-modify-write at the memory
-// side (and FETCH_SIZE's doubling, right for wide coalesced reads, counts those scattered requests twice: the true figure lies between
-// 75 and 150 MB).  Positions, order and the index part of a store are what they were either way.
-#ifndef XS_LINES
-#define XS_LINES 0
-#endif
-// the INDEX part of a staged entry alone (stage_store's: the key's bit, the grouped layout's first row of a run)
-__device__ __forceinline__ void stage_index_part(const DevStage& st, int64_t pos, int64_t key) {
-    if (st.bm) {
-        uint64_t off;
-        if (bm_locate(st, key, off)) {
-#if defined(XS_EXP) && (XS_EXP & 1)
-            if (key == -12345)                                // (byte-accounting experiment, tools/build_bytes.sh: no bitmap atomics — results ARE wrong)
-#endif
-            atomicOr(&st.bm[off >> 5], 1u << (off & 31));
-            if (st.grp_first) atomicMin(&st.grp_first[off], (uint32_t)pos);
-        }
-    }
-}
+// (Tried in round 6 and lost: survivors through a per-wave LDS ring, stored as whole 128-byte lines — same bytes, same 0.062 ms; the cost is
+//  the sink's index part.  Record: profiles/HISTORY.md, "Round 6"; profiles/r06_build_bytes_*.txt.)
 template <int NV> struct XStage {
-    static constexpr bool FINAL = false;
-    static constexpr int XS_RING = 128, XS_FLUSH = 32;                    // (a flush leaves < 32 rows behind, a consume adds <= 64)
     struct Args { DevStage st; };
-    int64_t out, seg_begin, flushed;
+    int64_t out, seg_begin;
     uint32_t carry;                                                       // row index: the bitmap word of the wave's previous entry
-    __device__ __forceinline__ void init(const Args&) { out = 0; seg_begin = 0; flushed = 0; carry = ROW_INDEX_NONE; }
-    __device__ __forceinline__ void begin_segment(int64_t begin) { out = seg_begin = flushed = begin; carry = ROW_INDEX_NONE; }
-    __device__ __forceinline__ static long long (*ring())[XS_RING] {
-        __shared__ long long s_ring[TPB / WAVE][NV + 1][XS_RING];
-        return s_ring[threadIdx.x / WAVE];
-    }
-    // rows [flushed, flushed + n) of the ring to the stage arrays: lane i the row flushed + i
-    __device__ __forceinline__ void flush(const DevStage& st, int n) {
-        long long (*buf)[XS_RING] = ring();
-        const int lane = lane_id();
-        if (lane < n) {
-            const int64_t pos = flushed + lane;
-            const int slot = (int)((pos - seg_begin) & (XS_RING - 1));
-            const long long key = buf[0][slot];
-            st.key[pos] = key;
-#pragma unroll
-            for (int q = 0; q < MAX_STAGE_COLS; ++q) if (q < st.npay) st.pay[q][pos] = q < NV ? buf[1 + (q < NV ? q : 0)][slot] : 0ll;
-            if (st.shits) st.shits[pos] = 0;
-            if (st.sacc) zero_acc(st, pos);
-            if (st.grp_kp) { using V2 = long long __attribute__((ext_vector_type(2))); const V2 kp = {key, NV > 0 ? buf[1][slot] : 0ll}; reinterpret_cast<V2*>(st.grp_kp)[pos] = kp; }
-        }
-        flushed += n;
-    }
+    __device__ __forceinline__ void init(const Args&) { out = 0; seg_begin = 0; carry = ROW_INDEX_NONE; }
+    __device__ __forceinline__ void begin_segment(int64_t begin) { out = seg_begin = begin; carry = ROW_INDEX_NONE; }
     __device__ __forceinline__ void consume(const XArgs& a, const Args& s, bool pass, int64_t, const XOut<NV>& o) {
         bool keep = pass;
         if (pass && (o.bad || (a.key_lo <= a.key_hi && (o.key < a.key_lo || o.key > a.key_hi)))) { atomicOr(a.flags, 2); keep = false; }
         const uint64_t b = __ballot(keep);
         const int64_t pos = out + __popcll(b & lanemask_lt());
-#if XS_LINES
-        if (!b) return;                                                   // (wave-uniform; nothing kept: nothing noted — row_index_note returns at once for an empty mask)
-        if (keep) {
-            long long (*buf)[XS_RING] = ring();
-            const int slot = (int)((pos - seg_begin) & (XS_RING - 1));
-            buf[0][slot] = o.key;
-#pragma unroll
-            for (int k = 0; k < NV; ++k) buf[1 + k][slot] = o.val[k];
-            stage_index_part(s.st, pos, o.key);
-        }
-#if defined(XS_EXP) && (XS_EXP & 2)
-        if (o.key == -12345)                                              // (experiment: no row-index notes)
-#endif
-        row_index_note(s.st, (int)(seg_begin / s.st.seg_rows), keep, o.key, pos, b, carry);
-        out += __popcll(b);
-        __builtin_amdgcn_wave_barrier();
-#if defined(XS_EXP) && (XS_EXP & 4)
-        if (o.key == -12345)                                              // (experiment: nothing stored to the stage arrays)
-#endif
-        while (out - flushed >= XS_FLUSH) flush(s.st, XS_FLUSH);
-#if defined(XS_EXP) && (XS_EXP & 4)
-        if (out - flushed >= XS_FLUSH) flushed = out - (out - flushed) % XS_FLUSH;
-#endif
-        __builtin_amdgcn_wave_barrier();
-#else
         if (keep) {
             int64_t pay[MAX_STAGE_COLS] = {0, 0, 0, 0, 0};
 #pragma unroll
@@ -529,13 +409,8 @@ template <int NV> struct XStage {
         }
         row_index_note(s.st, (int)(seg_begin / s.st.seg_rows), keep, o.key, pos, b, carry);
         out += __popcll(b);
-#endif
     }
     __device__ __forceinline__ void end_segment(const Args& s, int seg, int64_t begin) {
-#if XS_LINES
-        __builtin_amdgcn_wave_barrier();
-        while (out > flushed) flush(s.st, out - flushed >= WAVE ? WAVE : (int)(out - flushed));
-#endif
         if (lane_id() == 0) s.st.seg_count[seg] = (uint32_t)(out - begin);
     }
     __device__ __forceinline__ void finish(const XArgs&, const Args&) {}
@@ -543,7 +418,6 @@ template <int NV> struct XStage {
 
 // ---- membership-only K-B: OR the bits of the passing keys ----
 template <int NV> struct XKeySet {
-    static constexpr bool FINAL = false;
     struct Args { uint32_t* bm; };
     __device__ __forceinline__ void init(const Args&) {}
     __device__ __forceinline__ void consume(const XArgs& a, const Args& s, bool pass, int64_t, const XOut<NV>& o) {
@@ -559,7 +433,6 @@ template <int NV> struct XKeySet {
 //      one native f64 atomic per run and value (rows of one group sit in adjacent lanes when the probe side is
 //      clustered on the key) ----
 template <int NV> struct XEntry {
-    static constexpr bool FINAL = true;
     struct Args { DevTable tb; };
     __device__ __forceinline__ void init(const Args&) {}
     __device__ __forceinline__ void consume(const XArgs&, const Args& s, bool pass, int64_t, const XOut<NV>& o) {
@@ -592,20 +465,11 @@ template <int NV> struct XEntry {
                 head |= oh;
             }
         }
-#if XE_EXP == 1
-        if (tail && v[0] == 1.2345e300) atomicAdd(&s.tb.shits[idx], cnt);                   // (timing experiment: no atomics)
-#elif XE_EXP == 2
-        if (tail) {                                                                            // (timing experiment: sums only)
-#pragma unroll
-            for (int k = 0; k < NV; ++k) atomicAdd(&s.tb.sacc[(size_t)idx * s.tb.acc_stride + k], v[k]);
-        }
-#else
         if (tail) {
 #pragma unroll
             for (int k = 0; k < NV; ++k) atomicAdd(&s.tb.sacc[(size_t)idx * s.tb.acc_stride + k], v[k]);
             atomicAdd(&s.tb.shits[idx], cnt);
         }
-#endif
     }
     __device__ __forceinline__ void finish(const XArgs&, const Args&) {}
 };
@@ -891,7 +755,6 @@ __device__ __forceinline__ int64_t xt_i64(const uint32_t (&w)[16], int i) { retu
 // Deterministic: a lane adds its rows in row order, lanes are folded in a fixed order, workgroups by
 // k_groupby_merge in workgroup order.  The slots are the key's offsets, so no key table and no claiming.
 template <int NV> struct XGroupLane {
-    static constexpr bool FINAL = true;
     static constexpr bool PIPELINED = true;                           // x_tight: its LDS cells leave two or three waves per SIMD: a wave hides its own latency
     struct Args { unsigned long long* gkeys; double* pacc; int64_t* pcnt; int* flags; int32_t nslots, _pad; };
     // XGL_IVAL = v: summed value v is a small non-negative INTEGER on every row (a byte-coded column whose dictionary is consecutive
@@ -1071,7 +934,6 @@ __device__ __forceinline__ int wave_excl_prefix4(uint32_t v, int& total) {
     return below;
 }
 
-template <class Sink> __device__ __forceinline__ constexpr bool x_exp_on() { return X8_EXP_BUILD ? !Sink::FINAL : Sink::FINAL; }
 template <class P, template <int> class SinkT, bool SEGMENTED>
 __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P::NV>::Args& sa, int64_t nrows, int64_t seg_rows, int nseg) {
     using Sink = SinkT<P::NV>;
@@ -1111,11 +973,6 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
         if constexpr (P::NSC > 1) x_stage_text<P, 1>(a, q_row, begin, first, count, s_str, sres);
         bool pass = false; int64_t r = 0;
         if (lane < count) { r = begin + (int64_t)q_row[first + lane]; pass = P::eval_row(a, r, sres, o); }
-        if constexpr (X8_EXP == 4 && x_exp_on<Sink>()) {                                                                                                        // (timing experiment: every drained row evaluated twice)
-            if (lane < count) { XOut<P::NV> o2; const bool p2 = P::eval_row(a, r ^ 1, sres, o2); pass = pass && (p2 || (uint32_t)a.key_hi != 0x12345678u); }
-        }
-        if constexpr (X8_EXP == 14 && x_exp_on<Sink>()) pass = pass && (o.key == -12345 || nrows < (int64_t)X8_EXP_MINROWS);                                                                         // (no row reaches the sink, by its data)
-        if constexpr ((X8_EXP == 5 || X8_EXP == 10) && x_exp_on<Sink>()) { int pi = pass ? 1 : 0; asm volatile("" : "+v"(pi)); pass = pi != 0 && (uint32_t)a.key_hi == 0x12345678u; }   // (evaluated, nothing reaches the sink; 10: and no epilogue)
         sink.consume(a, sa, pass, r, o);
     };
     auto enqueue8 = [&](int64_t r0, uint32_t m) {                      // m: bit i = row r0 + i of this lane survives
@@ -1163,16 +1020,6 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
         }
     }
     if (live) {
-#if X8_PIPE
-        typename P::Regs pre[X8_U];
-        {
-            const int64_t b0 = tiled ? (int64_t)seg * STEP2 : begin;
-            if (b0 + STEP2 <= end) {
-#pragma unroll
-                for (int u = 0; u < X8_U; ++u) P::template sload<false>(a, b0 + (int64_t)u * X8_STEP + (int64_t)lane * XT_R, nrows, pre[u]);
-            }
-        }
-#endif
         for (int64_t b = tiled ? (int64_t)seg * STEP2 : begin;;) {
             bool last = false, produced = false;
             if constexpr (x_is_driven<P>::value) {
@@ -1215,19 +1062,11 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
             last = b >= end;
             if (last) {
             } else if (b + (int64_t)X8_STEP * X8_U <= end) {
-                // The NEXT double step's streamed loads are requested behind this step's bitmap words and before anything waits
-                // (X8_PIPE): `s_waitcnt vmcnt` counts in issue order, so requested BEFORE the words (round 3's attempt: Q3's probe
-                // 0.103 -> 0.110 ms) they have to land before the words can be tested and nothing overlaps; behind them they stay in
-                // flight through the tests, the queueing and the drains of this step.  Unconditional (behind the segment's last double
-                // step: that step again), so no wait piles up in front of a branch.
+                // (Tried and lost here: the NEXT double step's streamed loads requested ahead — in front of the bitmap words in round 3, behind
+                //  them, the form x_vstage8 keeps, in rounds 4 and 5.  Record: profiles/HISTORY.md, §3c and "Round 6".)
                 typename P::Regs s[X8_U];
-#if X8_PIPE
-#pragma unroll
-                for (int u = 0; u < X8_U; ++u) s[u] = pre[u];
-#else
 #pragma unroll
                 for (int u = 0; u < X8_U; ++u) P::template sload<false>(a, b + (int64_t)u * X8_STEP + (int64_t)lane * XT_R, nrows, s[u]);
-#endif
                 uint32_t m[X8_U], off[X8_U][XT_R], w[X8_U][XT_R];
                 uint32_t wb[X8_U]; XWindow win[X8_U];                           // (P::PWIN: the lane's window of the bitmap)
                 if constexpr (P::PREF32) {
@@ -1240,9 +1079,7 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
 #pragma unroll
                         for (int i = 0; i < XT_R; ++i) { const bool p = P::spre32(a, s[u], s_tab, i, off[u][i]); m[u] |= p ? (1u << i) : 0u; }
                     }
-                    if constexpr (X8_EXP == 1 && x_exp_on<Sink>()) {
-                        // (timing experiment: no bitmap requests at all)
-                    } else if constexpr (x_is_phash<P>::value) {
+                    if constexpr (x_is_phash<P>::value) {
                         // HASHED filter of a hash-layout table: spre32 gave 32 hash bits of the key; the key's word is one request, its two
                         // bits one test — the keys that pass (the table's, and a few per cent of the others) are queued for the slots
 #pragma unroll
@@ -1291,21 +1128,8 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
                         for (int i = 0; i < XT_R; ++i) m[u] |= P::stest(a, s[u], s_tab, i) ? (1u << i) : 0u;
                     }
                 }
-#if X8_PIPE
-                {
-                    __builtin_amdgcn_sched_barrier(0);
-                    const int64_t adv = phase == 1 ? stride : STEP2;                    // (tiled: this wave's next double step is a stride away)
-                    const int64_t bn = b + adv + STEP2 <= end ? b + adv : b;
-#pragma unroll
-                    for (int u = 0; u < X8_U; ++u) P::template sload<false>(a, bn + (int64_t)u * X8_STEP + (int64_t)lane * XT_R, nrows, pre[u]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-#endif
                 if constexpr (P::PREF32) {
-                    if constexpr (X8_EXP == 1 && x_exp_on<Sink>()) {
-#pragma unroll
-                        for (int u = 0; u < X8_U; ++u) m[u] = ((uint32_t)a.key_hi == 0x12345678u) ? m[u] : 0u;
-                    } else if constexpr (x_is_phash<P>::value) {
+                    if constexpr (x_is_phash<P>::value) {
 #pragma unroll
                         for (int u = 0; u < X8_U; ++u) {
                             uint32_t hit = 0;
@@ -1350,10 +1174,6 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
 #pragma unroll
                         for (int i = 0; i < XT_R; ++i) m[u] &= ~(((~w[u][i] >> (off[u][i] >> 27)) & 1u) << i);
                 }
-                if constexpr (X8_EXP == 2 && x_exp_on<Sink>()) {
-#pragma unroll
-                    for (int u = 0; u < X8_U; ++u) m[u] = ((uint32_t)a.key_hi == 0x12345678u) ? m[u] : 0u;      // (timing experiment: tests done, nothing queued)
-                }
 #pragma unroll
                 for (int u = 0; u < X8_U; ++u) enqueue8(b + (int64_t)u * X8_STEP + (int64_t)lane * XT_R, m[u]);
                 b += phase == 1 ? stride : (int64_t)X8_STEP * X8_U;
@@ -1378,8 +1198,7 @@ __device__ __forceinline__ void x_queue8(const XArgs& a, const typename SinkT<P:
             }
             }   // !produced
             int head = 0;
-            if constexpr (X8_EXP == 3 && x_exp_on<Sink>()) { if ((uint32_t)a.key_hi != 0x12345678u && nrows >= (int64_t)X8_EXP_MINROWS) qn = 0; }      // (timing experiment: survivors queued, never drained)
-            while (qn - head >= X8_DRAIN_AT || (last && qn > head)) {
+            while (qn - head >= WAVE || (last && qn > head)) {
                 const int n = qn - head >= WAVE ? WAVE : qn - head;
                 drain(head, n);
                 head += n;
@@ -1439,65 +1258,17 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
 #pragma unroll
     for (int l = 0; l < NL; ++l) bm[l] = P::NL > l ? P::lkbm(a, l) : nullptr;
     uint32_t carry = ROW_INDEX_NONE;                                          // row index: the bitmap word of the wave's previous entry
-    // XV_BITS: a build keyed by a strictly increasing column (st.wrow: the row-index layout exists for nothing else) meets its survivors in
-    // increasing key order, and the keys of another wave's rows lie outside [the wave's first row's key, its last row's key]: every bitmap
-    // word strictly between the first and the last word the wave touches is the wave's alone.  The wave ORs its bits into a window of
-    // XB_WORDS words in LDS and stores the words the window leaves behind — plainly, but for the first word it ever touched and, at the
-    // end, the last: those two may be shared with a neighbour and are ORed in (one atomic each instead of one per entry; zero words are
-    // not stored: the fill left them zero).  Right (the suite passes with it) and SLOWER: Q3's orders build 0.078 -> 0.091 ms — the ballots,
-    // the LDS atomics and the window's stores cost more than 1.5 M fire-and-forget atomics do (round 3 found the same for atomics merged by
-    // a segmented scan).  Off; kept as the measurement it is (SDQLPY_AMD_X_DEFINES="XV_BITS=1").
-    constexpr int XB_WORDS = 128;
-    __shared__ uint32_t s_bw[XV_BITS ? TPB / WAVE : 1][XV_BITS ? XB_WORDS : 1];
-    uint32_t* bw = s_bw[XV_BITS ? threadIdx.x / WAVE : 0];
-    const bool xb_on = XV_BITS && st.wrow && st.bm && st.bm_shift == 0 && st.lin_rb == 0 && !st.grp_first;
-    uint32_t xb_base = 0xFFFFFFFFu, xb_first = 0xFFFFFFFFu, xb_last = 0;
-    DevStage st_nobits = st;
-    if (xb_on) { st_nobits.bm = nullptr; for (int i = lane; i < XB_WORDS; i += WAVE) bw[i] = 0u; }
-    auto xb_flush = [&](uint32_t upto, bool final) {                         // the window's words below `upto` go to memory, the window is cleared
-        for (int i = lane; i < XB_WORDS; i += WAVE) {
-            const uint32_t wi = xb_base + (uint32_t)i, v = bw[i];
-            if (v && wi < upto) { if (wi == xb_first || (final && wi == xb_last)) atomicOr(&st.bm[wi], v); else st.bm[wi] = v; }
-            bw[i] = 0u;
-        }
-    };
-    auto xb_add = [&](bool keep, int64_t key) {
-        uint64_t off = 0;
-        const bool in = keep && bm_locate(st, key, off);
-        const uint32_t w = (uint32_t)(off >> 5);
-        const uint64_t all = __ballot(in);
-        uint64_t todo = all;
-        while (todo) {
-            const uint32_t wmin = (uint32_t)__shfl((int)w, __builtin_ctzll(todo), WAVE);
-            if (xb_base == 0xFFFFFFFFu) { xb_base = wmin; xb_first = wmin; }
-            if (wmin - xb_base >= (uint32_t)XB_WORDS) { xb_flush(0xFFFFFFFFu, false); xb_base = wmin; }
-            const bool mine = in && ((todo >> lane) & 1ull) && w - xb_base < (uint32_t)XB_WORDS;
-            if (mine) atomicOr(&bw[w - xb_base], 1u << (off & 31));
-            todo &= ~__ballot(mine);
-        }
-        if (all) xb_last = (uint32_t)__shfl((int)w, 63 - __builtin_clzll(all), WAVE);
-    };
+    // (Tried in round 6 and lost: the key bitmap's words assembled per wave in an LDS window and stored, one atomic per shared word instead of
+    //  one per entry — right, and slower.  Record: profiles/HISTORY.md, "Round 6".)
     auto flush = [&](int first, int count) {                                 // queued entries [first, first + count), count <= 64, one per lane
         if (st.wrow) row_index_note(st, seg, lane < count, lane < count ? (int64_t)q[0][first + lane] : 0, out + lane, count >= 64 ? ~0ull : ((1ull << count) - 1ull), carry);
-        if (xb_on) xb_add(lane < count, lane < count ? (int64_t)q[0][first + lane] : 0);
         if (lane < count) {
             const int64_t key = (int64_t)q[0][first + lane];
             int64_t pay[MAX_STAGE_COLS] = {0, 0, 0, 0, 0};
 #pragma unroll
             for (int k = 0; k < P::NV; ++k) pay[k] = (int64_t)q[1 + k][first + lane];
             if (a.key_lo <= a.key_hi && (key < a.key_lo || key > a.key_hi)) atomicOr(a.flags, 2);      // (the call fails; what is stored is never read)
-#ifdef XV_EXP
-            {   // timing experiments only (SDQLPY_AMD_XV_EXP): bit 0 no bitmap atomics, bit 1 no accumulator zeroing, bit 2 no payload stores
-                const int64_t pos = out + lane;
-                st.key[pos] = key;
-                if (!(XV_EXP & 4)) { for (int qq = 0; qq < P::NV; ++qq) st.pay[qq][pos] = pay[qq]; }
-                if (st.shits) st.shits[pos] = 0;
-                if (st.sacc && !(XV_EXP & 2)) zero_acc(st, pos);
-                if (st.bm && !(XV_EXP & 1)) { uint64_t off; if (bm_locate(st, key, off)) atomicOr(&st.bm[off >> 5], 1u << (off & 31)); }
-            }
-#else
-            stage_store<-1>(xb_on ? st_nobits : st, out + lane, key, pay);
-#endif
+            stage_store<-1>(st, out + lane, key, pay);
         }
         out += count;
     };
@@ -1553,13 +1324,7 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
                 for (int l = 0; l < NL; ++l) {
                     off[l][u][i] = 0;
                     if (P::NL > l) {
-#if XV_OFFALL
-                        bool in = true;                                            // (A/B: the key's own offset whatever the earlier conditions say)
-                        const uint32_t o32 = P::lkoff(a, s[u], s_tab, i, r0 + i, l, in);
-                        p = p & in; off[l][u][i] = in ? o32 : 0u;
-#else
                         const uint32_t o32 = P::lkoff(a, s[u], s_tab, i, r0 + i, l, p); off[l][u][i] = p ? o32 : 0u;
-#endif
                     }
                 }
                 m[u] |= p ? (1u << i) : 0u;
@@ -1573,16 +1338,7 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
 #pragma unroll
             for (int u = 0; u < U; ++u)
 #pragma unroll
-                for (int i = 0; i < XT_R; ++i) {
-#if defined(XV_EXP) && (XV_EXP & 8)
-                    w[l][u][i] = 0xFFFFFFFFu;                                      // (timing experiment: no bitmap requests, every key "found")
-#elif XV_MASKED
-                    w[l][u][i] = 0u;
-                    if ((m[u] >> i) & 1u) w[l][u][i] = bm[l][off[l][u][i] >> 5];    // only the lanes whose row is still alive take part in the request
-#else
-                    w[l][u][i] = bm[l][off[l][u][i] >> 5];
-#endif
-                }
+                for (int i = 0; i < XT_R; ++i) w[l][u][i] = bm[l][off[l][u][i] >> 5];
     };
     auto finish = [&](const auto& s, int64_t b, auto u_tag, auto& m, const auto& off, const auto& w) {   // bit tests, survivors queued, full groups stored
         constexpr int U = decltype(u_tag)::value ? X8_U : 1;
@@ -1595,9 +1351,6 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
                 for (int i = 0; i < XT_R; ++i) hit |= __builtin_amdgcn_ubfe(w[l][u][i], off[l][u][i] & 31u, 1u) << i;
                 m[u] &= hit;
             }
-#if defined(XV_EXP) && (XV_EXP & 16)
-            m[u] = ((uint32_t)a.key_hi == 0x12345678u) ? m[u] : 0u;                 // (timing experiment: nothing queued)
-#endif
             enqueue(s[u], b + (int64_t)u * X8_STEP + (int64_t)lane * XT_R, m[u]);
         }
     };
@@ -1613,7 +1366,6 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
         finish(s, b, u_tag, m, off, w);
     };
     int64_t b = begin;
-#if XV_PIPE
     {
         constexpr int64_t STEP2 = (int64_t)X8_STEP * X8_U;
         const int64_t nfull = (end - begin) / STEP2;
@@ -1641,12 +1393,10 @@ __device__ __forceinline__ void x_vstage8(const XArgs& a, const typename XStage<
             if (k < nfull) { piped(cur, nxt, b, b); b += STEP2; }
         }
     }
-#endif
     for (; b + (int64_t)X8_STEP * X8_U <= end; b += (int64_t)X8_STEP * X8_U) step(b, XBool<true>{}, XBool<false>{});
     for (; b + X8_STEP <= end; b += X8_STEP) step(b, XBool<false>{}, XBool<false>{});
     if (b < end) step(b, XBool<false>{}, XBool<true>{});
     if (qn) flush(0, qn);
-    if (xb_on && xb_base != 0xFFFFFFFFu) xb_flush(xb_last + 1u, true);
     if (lane == 0) st.seg_count[seg] = (uint32_t)(out - begin);
 }
 

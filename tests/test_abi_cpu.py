@@ -348,3 +348,27 @@ def test_plan_recording_is_refused_by_the_cpu_implementation_and_the_calls_go_on
     finally:
         plain.close()
         recording.close()
+
+
+def test_kernel_headers_carry_no_leftover_ab_switches():
+    """The compile-time switches of the two kernel headers are a closed list, and none of them is a timing experiment.
+    A new A/B switch is welcome while it is being measured, and leaves with the pull request that measured it: the winner becomes
+    the code, the loser a line in profiles/HISTORY.md."""
+    allowed = {
+        "XGL_IVAL",                                         # emitted by the generator (sdqh_x.hip) per kernel: which summed value arrives as an integer
+        "SDQH_UNROLL", "SDQH_NT_LOADS", "SDQH_TILE_CHUNK",  # set by tools/microbench_q1.hip, which compiles sdqh_kernels.hpp under other values
+        # two more #ifndef / #define pairs are functional and stay: neither yields a wrong result nor a second code path, each is ONE
+        # constant of the live code that profiles/r05_exp_* swept through SDQLPY_AMD_X_DEFINES and that tools/x_exp.sh still names
+        "X_PIN",                                            # whether the layout-specialised lookups pin same-depth loads together (x_pin)
+        "X8_U_STEPS",                                       # 512-row steps whose loads x_queue8 / x_vstage8 keep in flight (sizes their LDS queues)
+    }
+    found, offenders = set(), []
+    for name in ("sdqh_xkernels.hpp", "sdqh_kernels.hpp"):
+        text = open(os.path.join(ROOT, "sdqlpy_amd", "csrc", name)).read()
+        found |= {m.group(1) for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)[^\n]*\n[ \t]*#[ \t]*define[ \t]+(\w+)", text, flags=re.M) if m.group(1) == m.group(2)}
+        for no, line in enumerate(text.splitlines(), 1):
+            code = line.split("//")[0]
+            if (re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", code) or re.search(r"\bif\s+constexpr\b", code)) and re.search(r"\w_EXP\b", code):
+                offenders.append("%s:%d: %s" % (name, no, line.strip()))
+    assert found == allowed, sorted(found ^ allowed)        # (both headers use `#pragma once`: no include guard to allow for)
+    assert not offenders, offenders

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the run-time skeletons on one query: every variant in a process of its own (macros are part of the specialised source).
-#   bash tools/x_exp.sh q3 gpurun_out/r04/exp_q3.txt "X8_PIPE=1 XV_PIPE=1" "x_waves=12" ...
+#   bash tools/x_exp.sh q3 out/exp_q3.txt "X8_U_STEPS=3 x_waves=12" "NOLAYOUT" ...
 # each further argument is one variant: NAME=value in UPPER case are macros (SDQLPY_AMD_X_DEFINES), a bare UPPER-case word W sets
 # SDQLPY_AMD_X_W=1 in the environment, lower case name=value are options (sdqh_set_option)
 Q=$1; OUT=$2; shift 2
