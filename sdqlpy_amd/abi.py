@@ -37,6 +37,12 @@ WINDOW_AGG_EXPORTS = ["sdqh_table_window_agg", "sdqh_window_agg_geometry"]
 WAGG_SUM, WAGG_COUNT, WAGG_MIN, WAGG_MAX = 0, 1, 2, 3
 FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
 WAGG_MAX_AGGS = 4
+# ... and its fifth (include/sdqh_sort_slide.h, Library.has_window_slide): the same ops and FIRST / LAST over sliding frames — ROWS BETWEEN
+# lo AND hi, signed offsets from the row — LAG and LEAD among them
+WINDOW_SLIDE_EXPORTS = ["sdqh_table_window_slide", "sdqh_window_slide_geometry"]
+WSLIDE_FIRST, WSLIDE_LAST = 4, 5
+SLIDE_UNBOUNDED_PRECEDING, SLIDE_UNBOUNDED_FOLLOWING = -(1 << 63), (1 << 63) - 1
+WSLIDE_MAX_AGGS = 4
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -104,6 +110,11 @@ class SortTerm(C.Structure):
 class WindowAgg(C.Structure):
     """sdqh_window_agg: an aggregate (op, frame) and its measure, named as a SortKey names a column."""
     _fields_ = [("op", C.c_int32), ("frame", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("_pad", C.c_int32)]
+
+
+class WindowSlide(C.Structure):
+    """sdqh_window_slide: an op, its measure (as a SortKey names a column), the frame's signed offsets and the 64 bits of an empty frame."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
 
 
 SRC_COLUMN, SRC_LOOKUP, SRC_LOOKUP_YEAR = 0, 1, 2
@@ -1273,6 +1284,35 @@ class Context:
         self._check(self.lib.sdqh_window_agg_geometry(self.handle, C.byref(a)))
         return a.value
 
+    def _need_window_slide(self, what):
+        if not self.library.has_window_slide:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window slide extension (include/sdqh_sort_slide.h)" % (what, self.library.path))
+
+    def table_window_slide(self, table, min_hits, npartition, terms, slides, limit, capacity, want_hits=True):
+        """Values over sliding frames of the ordered entries: terms and npartition as table_window takes them; slides: [(op, kind,
+        index, is_f64, lo, hi, empty)] — op in WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX / WSLIDE_FIRST / WSLIDE_LAST, the measure as a
+        sort column is named (COUNT ignores it), the frame rows [j + lo, j + hi] of row j's partition (SLIDE_UNBOUNDED_PRECEDING /
+        SLIDE_UNBOUNDED_FOLLOWING: no bound), empty: the 64 bits an empty frame gives, as an int64.  Every selected row is kept; the
+        first min(limit, n) in sorted order.  Returns (keys, payload, values, hits, slides) — slides one array per slide, float64 for a
+        double measure under any op but COUNT, else int64."""
+        self._need_window_slide("table_window_slide")
+        arr = (WindowSlide * max(1, len(slides)))()
+        for i, (op, kind, index, is_f64, lo, hi, empty) in enumerate(slides):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
+            arr[i].lo, arr[i].hi, arr[i].empty = int(lo), int(hi), int(empty)
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(slides)), arr, C.c_int64(limit))
+        got = self._sorted_call("table_window_slide", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(slides)))
+        as_f64 = [op != WAGG_COUNT and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))) for op, kind, _, is_f64, _, _, _ in slides]
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def window_slide_geometry(self):
+        """(sorted positions per tile of sdqh_table_window_slide's scans, the largest frame width a kernel walks row by row or 0): what
+        the tests size their cases from."""
+        self._need_window_slide("window_slide_geometry")
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.sdqh_window_slide_geometry(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1537,6 +1577,11 @@ class Library:
             L.sdqh_table_window_agg.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_agg_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        self.has_window_slide = self.has_window_agg and all(hasattr(L, s) for s in WINDOW_SLIDE_EXPORTS)      # ... and sliding frames (include/sdqh_sort_slide.h)
+        if self.has_window_slide:
+            L.sdqh_table_window_slide.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_slide_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

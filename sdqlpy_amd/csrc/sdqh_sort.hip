@@ -23,7 +23,8 @@
 //   k_sort_emit       the first min(limit, n) rows in order, columns as sdqh_table_compact lays them out
 //
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
-// (include/sdqh_sort_window.h) and sdqh_table_window_agg (include/sdqh_sort_frames.h): select -> order -> rank or aggregate -> emit
+// (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h) and sdqh_table_window_slide
+// (include/sdqh_sort_slide.h): select -> order -> rank, aggregate or slide -> emit
 // (ordered_impl).  What differs between them is
 // data, not code:
 //
@@ -66,6 +67,16 @@
 //                     only for RANGE / PARTITION frames, backwards: the first heads of the later tiles (suffix minimum), then per
 //                     position the last row of its tie run / partition, whose ROWS value is copied: the frames agree bit for bit.
 //                     Row j is sorted position j: the first m values are the output, k_sort_emit writes the rows as for a plain sort
+//   SLIDES            in their place (SortSlides).  sdqh_table_window_slide (include/sdqh_sort_slide.h) takes SUM / COUNT / MIN / MAX /
+//                     FIRST / LAST over ROWS BETWEEN lo AND hi of the same partitions.  Behind k_win_heads and k_win_scan:
+//
+//   k_wsl_rows        the row number of every position in its partition (k_win_rank's ROW_NUMBER arm), the tile's first partition head
+//   k_wagg_next / k_wsl_blocks
+//                     backwards: per position its partition's last position, every slide's element (perm -> refs -> stage, once) and
+//                     a byte of block-head flags — a slide of width w cuts the partitions into blocks of w positions
+//   k_wsl_tiles / k_wsl_scan / k_wsl_run
+//                     the tile scan of the frames, restarted at block heads, forwards (prefix folds) and backwards (suffix folds)
+//   k_wsl_fold        row j's frame [l, r] spans at most two blocks: suffix[l] (+) prefix[r], or one of them — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -78,7 +89,7 @@
 
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
-#include "sdqh_sort_frames.h"
+#include "sdqh_sort_slide.h"
 
 using namespace sdqh_host;
 
@@ -724,6 +735,216 @@ __global__ __launch_bounds__(TPB) void k_wagg_ends(DevWaggs ag, const uint8_t* _
     }
 }
 
+// ---- sliding frames (sdqh_table_window_slide) ------------------------------------------------------------------------------------
+// The frame of sorted row j is [l, r] = [max(j + lo, s), min(j + hi, e)] inside its partition [s, e].  COUNT is arithmetic on l and
+// r, FIRST / LAST gather the raw element at l / r.  SUM / MIN / MAX of width w = hi - lo + 1 (an unbounded side, or w >= n: w = n, a
+// block is the partition) cut every partition into BLOCKS of w positions aligned at the partition's start and fold every block
+// twice — an inclusive prefix from its first position, an inclusive suffix up to its last — so that a frame, which spans at most
+// two adjacent blocks, is suffix[l] (+) prefix[r], or one of the two alone: the work per row does not depend on w, exactly the
+// frame's rows enter, nothing is added and later subtracted.  The two folds are the tile scan of the frames above (tile carries ->
+// scan over the tiles -> the tile again) with block heads in the place of partition heads, once forwards and once backwards.
+constexpr int WSL_NONE = 3;                          // a slide's class when nothing is folded (COUNT, FIRST, LAST); else WAGG_*
+constexpr int WSL_FWD = 0, WSL_BWD = 1;
+struct DevWslide { DevWagg g; uint32_t w, _pad; int64_t lo, hi; uint64_t empty; };     // g.frame unused; lo / hi clamped to [-n, n]; 1 <= w <= n
+struct DevWslides { DevWslide a[SDQH_WSLIDE_MAX_AGGS]; int32_t n, _pad; };
+static_assert(SDQH_WSLIDE_MAX_AGGS * 2 <= 8, "a byte per position holds every slide's two block-head flags");
+
+// the batch of 64 positions at [b, ..) as one direction walks it: forwards lane i holds position b + i, backwards b + 63 - i, so
+// that "a lower lane" is "earlier in the fold" either way and wagg_wave_scan's lane rule holds unchanged
+__device__ __forceinline__ uint64_t wsl_pos(int dir, uint64_t b, uint32_t lane) { return dir == WSL_BWD ? b + (uint64_t)(WAVE - 1) - lane : b + lane; }
+// wagg_wave_scan with the operands in position order: backwards the lower lane is the higher position, the right operand
+__device__ __forceinline__ uint64_t wsl_wave_scan(int cls, int dir, uint64_t v, uint32_t lane, uint32_t first) {
+#pragma unroll
+    for (uint32_t d = 1; d < (uint32_t)WAVE; d <<= 1) {
+        const uint64_t o = (uint64_t)__shfl_up((long long)v, d, WAVE);
+        if (lane >= first + d) v = dir == WSL_BWD ? wagg_join(cls, v, o) : wagg_join(cls, o, v);
+    }
+    return v;
+}
+__device__ __forceinline__ uint64_t wsl_join(int cls, int dir, uint64_t before, uint64_t after) { return dir == WSL_BWD ? wagg_join(cls, after, before) : wagg_join(cls, before, after); }
+
+// 1. the row number of every position inside its partition, from 0 (k_win_rank's ROW_NUMBER arm: carry = k_win_scan's), and per
+// tile the position of its first partition head (n: none; what k_wagg_next scans)
+__global__ __launch_bounds__(TPB) void k_wsl_rows(const uint8_t* __restrict__ heads, const WinCarry* __restrict__ carry, uint32_t n, uint32_t* __restrict__ rown,
+                                                 WaggHeads* __restrict__ tfirst, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    WinCarry run = carry[w];
+    WaggHeads fh = {n, n};
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        if (h.mp && fh.part == n) fh.part = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (live) rown[r] = h.pl ? lane - h.first : run.cnt + lane;
+        win_step(run, h.mp, h.mt, (uint32_t)min((uint64_t)WAVE, r1 - b));
+    }
+    if (lane == 0) tfirst[w] = fh;
+}
+// 2. a tile walked backwards (k_wagg_ends' shape): per position the last position of its partition, every slide's element (the
+// measure read through perm -> refs -> stage once: raw for SUM / FIRST / LAST, the image for MIN / MAX, none for COUNT) and the
+// block-head flags of the folded slides, a byte: bit 2a = position opens a block of slide a, bit 2a + 1 = it closes one
+__global__ __launch_bounds__(TPB) void k_wsl_blocks(DevStage st, DevWslides sl, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ heads,
+                                                   const WaggHeads* __restrict__ tnext, const uint32_t* __restrict__ rown, uint32_t n, size_t stride,
+                                                   uint32_t* __restrict__ pend, uint8_t* __restrict__ bh, uint64_t* __restrict__ elem, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint32_t next = tnext[w].part;
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const uint64_t pg = h.mp & ~le;
+        const uint32_t pe = (pg ? (uint32_t)b + (uint32_t)__builtin_ctzll(pg) : next) - 1u;
+        if (live) {
+            const uint32_t rn = rown[r];
+            const uint32_t g = perm ? perm[r] : (uint32_t)r;
+            const bool ok = g < n;                                       // (a permutation of [0, n): always)
+            const int64_t idx = ok ? (int64_t)refs[g] : 0;
+            const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u;
+            uint32_t flags = 0u;
+#pragma unroll
+            for (int a = 0; a < SDQH_WSLIDE_MAX_AGGS; ++a) if (a < sl.n) {
+                const DevWslide& s = sl.a[a];
+                if (s.g.cls != WSL_NONE) {
+                    if (rn % s.w == 0u) flags |= 1u << (2 * a);
+                    if ((uint32_t)r == pe || (rn + 1u) % s.w == 0u) flags |= 2u << (2 * a);
+                }
+                if (s.g.op != SDQH_WAGG_COUNT) {
+                    uint64_t e = 0ull;
+                    if (ok) e = s.g.cls == WSL_NONE ? (uint64_t)sort_raw(s.g.sk, st, idx, hits) : wagg_element(s.g, st, idx, hits);
+                    elem[(size_t)a * stride + r] = e;
+                }
+            }
+            pend[r] = pe;
+            bh[r] = (uint8_t)flags;
+        }
+        if (h.mp) next = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (b == r0) break;
+    }
+}
+// One direction of one tile, 64 positions at a time — the segmented scan across the lanes restarted at block heads, the running
+// carry folded into the lanes whose block began before the batch.  `run` comes in as the tile's carry-in and leaves as its carry-out
+// (the elements folded since the tile's last head, or carry-in and whole tile); out != nullptr: the fold of every position is stored.
+// Returns whether the tile holds a head.  Dead lanes (past the tile's end) hold the identity and no head.
+__device__ __forceinline__ bool wsl_tile_fold(int cls, int dir, int a, const uint8_t* __restrict__ bh, const uint64_t* in, uint64_t* out,
+                                              uint64_t r0, uint64_t r1, uint32_t lane, uint64_t le, uint64_t& run) {
+    const uint32_t nb = (uint32_t)((r1 - r0 + WAVE - 1) / WAVE);
+    bool seen = false;
+    for (uint32_t k = 0; k < nb; ++k) {
+        const uint64_t b = r0 + (uint64_t)(dir == WSL_BWD ? nb - 1u - k : k) * WAVE;
+        const uint64_t r = wsl_pos(dir, b, lane);
+        const bool live = r < r1;
+        const uint32_t f = live ? bh[r] : 0u;
+        const uint64_t mh = __ballot((f >> (2 * a + dir)) & 1u);
+        const uint64_t hl = mh & le;
+        const uint64_t e = live ? in[r] : wagg_identity(cls);
+        const uint64_t s = wsl_wave_scan(cls, dir, e, lane, hl ? 63u - (uint32_t)__clzll((long long)hl) : 0u);
+        const uint64_t v = hl ? s : wsl_join(cls, dir, run, s);
+        if (out && live) out[r] = v;
+        const int last = dir == WSL_BWD ? WAVE - 1 : (int)min((uint64_t)WAVE, r1 - b) - 1;      // the lane that has seen the whole batch
+        run = (uint64_t)__shfl((long long)v, last, WAVE);
+        seen |= mh != 0ull;
+    }
+    return seen;
+}
+// 3. per tile, folded slide and direction the carry and whether the tile holds a block head: tval / thead[(dir * MAX_AGGS + a) * ntiles + tile]
+__global__ __launch_bounds__(TPB) void k_wsl_tiles(DevWslides sl, const uint8_t* __restrict__ bh, uint32_t n, size_t stride, const uint64_t* __restrict__ elem,
+                                                  uint64_t* __restrict__ tval, uint8_t* __restrict__ thead, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+#pragma unroll
+    for (int a = 0; a < SDQH_WSLIDE_MAX_AGGS; ++a) if (a < sl.n && sl.a[a].g.cls != WSL_NONE) {
+        const int cls = sl.a[a].g.cls;
+        for (int dir = WSL_FWD; dir <= WSL_BWD; ++dir) {
+            uint64_t run = wagg_identity(cls);
+            const bool seen = wsl_tile_fold(cls, dir, a, bh, elem + (size_t)a * stride, nullptr, r0, r1, lane, le, run);
+            if (lane == 0) { const size_t at = (size_t)(dir * SDQH_WSLIDE_MAX_AGGS + a) * ntiles + w; tval[at] = run; thead[at] = seen ? 1u : 0u; }
+        }
+    }
+}
+// 4. workgroup dir * MAX_AGGS + a: exclusive segmented scan of those carries over the tiles in the direction's order, in place —
+// k_wagg_scan's shape (a later side with a head wins; the operands stay in position order)
+__global__ __launch_bounds__(TPB) void k_wsl_scan(DevWslides sl, const uint8_t* __restrict__ thead, uint64_t* __restrict__ tval, uint32_t ntiles) {
+    __shared__ uint64_t s_v[TPB];
+    __shared__ uint32_t s_f[TPB];
+    const int dir = (int)blockIdx.x / SDQH_WSLIDE_MAX_AGGS, a = (int)blockIdx.x % SDQH_WSLIDE_MAX_AGGS;
+    if (a >= sl.n || sl.a[a].g.cls == WSL_NONE) return;
+    const int cls = sl.a[a].g.cls;
+    const uint64_t id = wagg_identity(cls);
+    uint64_t* __restrict__ v = tval + (size_t)blockIdx.x * ntiles;
+    const uint8_t* __restrict__ hd = thead + (size_t)blockIdx.x * ntiles;
+    const uint32_t per = (ntiles + TPB - 1) / TPB;
+    const uint64_t b0 = min((uint64_t)ntiles, (uint64_t)threadIdx.x * per), b1 = min((uint64_t)ntiles, b0 + per);
+    const auto tile = [&](uint64_t b) { return dir == WSL_BWD ? (uint64_t)ntiles - 1u - b : b; };      // the b-th tile the direction meets
+    uint64_t sum = id; uint32_t f = 0u;
+    for (uint64_t b = b0; b < b1; ++b) { const uint64_t t = tile(b); const bool hf = hd[t] != 0; sum = hf ? v[t] : wsl_join(cls, dir, sum, v[t]); f |= hf ? 1u : 0u; }
+    s_v[threadIdx.x] = sum; s_f[threadIdx.x] = f;
+    __syncthreads();
+    for (int off = 1; off < TPB; off <<= 1) {
+        uint64_t av = id; uint32_t af = 0u;
+        if ((int)threadIdx.x >= off) { av = s_v[threadIdx.x - off]; af = s_f[threadIdx.x - off]; }
+        __syncthreads();
+        if (!s_f[threadIdx.x]) { s_v[threadIdx.x] = wsl_join(cls, dir, av, s_v[threadIdx.x]); s_f[threadIdx.x] = af; }
+        __syncthreads();
+    }
+    uint64_t run = threadIdx.x > 0 ? s_v[threadIdx.x - 1] : id;
+    for (uint64_t b = b0; b < b1; ++b) { const uint64_t t = tile(b); const uint64_t x = v[t]; v[t] = run; run = hd[t] ? x : wsl_join(cls, dir, run, x); }
+}
+// 5. the tile again with its carries-in: pre[a * stride + r] = the fold of r's block from its first position to r; then, in place,
+// elem[a * stride + r] = the fold from r to the block's last position (the forward walk has read the tile's elements by then, and no
+// other wave touches them)
+__global__ __launch_bounds__(TPB) void k_wsl_run(DevWslides sl, const uint8_t* __restrict__ bh, uint32_t n, size_t stride, uint64_t* __restrict__ elem, uint64_t* __restrict__ pre,
+                                                const uint64_t* __restrict__ tval, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+#pragma unroll
+    for (int a = 0; a < SDQH_WSLIDE_MAX_AGGS; ++a) if (a < sl.n && sl.a[a].g.cls != WSL_NONE) {
+        const int cls = sl.a[a].g.cls;
+        uint64_t* __restrict__ e = elem + (size_t)a * stride;
+        for (int dir = WSL_FWD; dir <= WSL_BWD; ++dir) {
+            uint64_t run = tval[(size_t)(dir * SDQH_WSLIDE_MAX_AGGS + a) * ntiles + w];
+            (void)wsl_tile_fold(cls, dir, a, bh, e, dir == WSL_BWD ? e : pre + (size_t)a * stride, r0, r1, lane, le, run);
+        }
+    }
+}
+// 6. the value of every slide at the first m positions: fin[a * stride + j].  suf: elem after k_wsl_run (raw for FIRST / LAST)
+__global__ __launch_bounds__(TPB) void k_wsl_fold(DevWslides sl, const uint32_t* __restrict__ rown, const uint32_t* __restrict__ pend, uint32_t n, uint32_t m, size_t stride,
+                                                 const uint64_t* __restrict__ suf, const uint64_t* __restrict__ pre, uint64_t* __restrict__ fin) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t rn = rown[j];
+        const int64_t e = (int64_t)pend[j], s = (int64_t)j - (int64_t)rn;
+        if (s < 0 || e < (int64_t)j || e >= (int64_t)n) continue;           // (s <= j <= e < n: never taken)
+#pragma unroll
+        for (int a = 0; a < SDQH_WSLIDE_MAX_AGGS; ++a) if (a < sl.n) {
+            const DevWslide& d = sl.a[a];
+            const int64_t l = max((int64_t)j + d.lo, s), r = min((int64_t)j + d.hi, e);      // (|lo|, |hi| <= n < 2^32: no overflow)
+            uint64_t v;
+            if (d.g.op == SDQH_WAGG_COUNT) v = l > r ? 0ull : (uint64_t)(r - l + 1);
+            else if (l > r) v = d.empty;
+            else if (d.g.op == SDQH_WSLIDE_FIRST) v = suf[(size_t)a * stride + (size_t)l];
+            else if (d.g.op == SDQH_WSLIDE_LAST) v = suf[(size_t)a * stride + (size_t)r];
+            else {
+                const uint32_t rl = (uint32_t)(l - s), rr = (uint32_t)(r - s);           // row numbers of the frame's ends
+                const uint32_t bl = rl / d.w, br = rr / d.w;
+                const uint64_t p = pre[(size_t)a * stride + (size_t)r], q = suf[(size_t)a * stride + (size_t)l];
+                // two blocks: the tail of l's and the head of r's; one: l opens it, or else r closes it (a frame shorter than w that
+                // does not start at a block's first position was cut at the partition's end, which is its last block's end)
+                v = wagg_result(d.g, bl != br ? wagg_join(d.g.cls, q, p) : (rl == bl * d.w ? p : q));
+            }
+            fin[(size_t)a * stride + j] = v;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -920,19 +1141,22 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 struct SortWindow { int npart, kind; int64_t per_limit; int64_t* out_rank; };
 // ... or, in its place, aggregates over frames of the same partitions (sdqh_table_window_agg): every row kept, out[a * capacity + j]
 struct SortFrames { int npart; DevWaggs aggs; int64_t* out; };
+// ... or values over sliding frames (sdqh_table_window_slide): likewise; lo / hi as the caller gave them (sl's are set once n is known)
+struct SortSlides { int npart; DevWslides sl; int64_t lo[SDQH_WSLIDE_MAX_AGGS], hi[SDQH_WSLIDE_MAX_AGGS]; int64_t* out; };
 
-// The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr; never
-// both) -> emit.  who: the entry point's name in messages.
+// The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr) or
+// slide (slides != nullptr; at most one of the three) -> emit.  who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
-                        const SortFrames* frames, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+                        const SortFrames* frames, const SortSlides* slides, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     const std::string me(who);
     int64_t* out_rank = win ? win->out_rank : nullptr;
     const SortFrames* fr = frames && frames->out ? frames : nullptr;     // (no array for them: rows only, no aggregate pass)
+    const SortSlides* sd = slides && slides->out ? slides : nullptr;     // (likewise)
     Scratch scratch(ctx);
     SortState s;
     if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
-    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr;
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd;
     const bool all_kept = !win || win->per_limit >= n;               // a rank is at most n: nothing to filter, the count is known
     const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
     const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
@@ -947,7 +1171,56 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     const uint32_t un = (uint32_t)n;
     uint32_t *rank = nullptr, *sel = nullptr;
     const size_t agg_stride = round_up((size_t)n * 8) / 8;           // aggregate a's values start at a * agg_stride
-    const uint64_t* agg_rows = nullptr; const uint64_t* agg_fin = nullptr;
+    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "one list of result arrays serves frames and slides");
+    const uint64_t* agg_src[SDQH_WAGG_MAX_AGGS] = {nullptr, nullptr, nullptr, nullptr};      // where each aggregate's / slide's values lie once the passes ran
+    int64_t* agg_out = nullptr; int agg_n = 0;                        // ... and the caller's array for them: agg_out[a * capacity + j]
+    if (sd) {
+        // block 3: [heads | tile carries | row numbers | partition ends | block-head flags | elements, then suffix folds | prefix folds |
+        // values | fold carries | their head flags | first heads per tile | next heads per tile]
+        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+        DevWslides sl = sd->sl;
+        const size_t na = (size_t)sl.n;
+        bool folds = false;                                           // does some slide fold (SUM / MIN / MAX)?
+        for (size_t a = 0; a < na; ++a) {
+            // an offset of n or more reaches outside every partition, whichever it is: clamped, the arithmetic stays far inside 64 bits
+            DevWslide& d = sl.a[a];
+            d.lo = std::max<int64_t>(std::min<int64_t>(sd->lo[a], n), -n);
+            d.hi = std::max<int64_t>(std::min<int64_t>(sd->hi[a], n), -n);
+            d.w = (uint32_t)std::min<int64_t>(d.hi - d.lo + 1, n);
+            folds |= d.g.cls != WSL_NONE;
+        }
+        uint8_t *heads = nullptr, *bh = nullptr, *thead = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr;
+        uint64_t *elem = nullptr, *pre = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
+        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
+                heads = c.take<uint8_t>((size_t)n);
+                carry = c.take<WinCarry>(ntiles);
+                rown = c.take<uint32_t>((size_t)n);
+                pend = c.take<uint32_t>((size_t)n);
+                bh = c.take<uint8_t>((size_t)n);
+                elem = c.take<uint64_t>(agg_stride * na);
+                pre = c.take<uint64_t>(folds ? agg_stride * na : 0);
+                fin = c.take<uint64_t>(agg_stride * na);
+                tval = c.take<uint64_t>(folds ? (size_t)ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
+                thead = c.take<uint8_t>(folds ? (size_t)ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
+                tfirst = c.take<WaggHeads>(ntiles);
+                tnext = c.take<WaggHeads>(ntiles);
+            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, sd->npart, nsort, s.perm, un, heads, carry, ntiles);
+        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+        LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
+        LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
+        LAUNCH(ctx, "k_wsl_blocks", k_wsl_blocks, tgrid, table->stage, sl, s.refs, s.perm, heads, tnext, rown, un, agg_stride, pend, bh, elem, ntiles);
+        if (folds) {
+            LAUNCH(ctx, "k_wsl_tiles", k_wsl_tiles, tgrid, sl, bh, un, agg_stride, elem, tval, thead, ntiles);
+            LAUNCH(ctx, "k_wsl_scan", k_wsl_scan, 2 * SDQH_WSLIDE_MAX_AGGS, sl, thead, tval, ntiles);
+            LAUNCH(ctx, "k_wsl_run", k_wsl_run, tgrid, sl, bh, un, agg_stride, elem, pre, tval, ntiles);
+        }
+        const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+        LAUNCH(ctx, "k_wsl_fold", k_wsl_fold, fgrid, sl, rown, pend, un, (uint32_t)m, agg_stride, elem, pre, fin);
+        agg_out = sd->out; agg_n = sl.n;
+        for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
+    }
     if (win || fr) {
         // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack] for a window, [heads | tile carries |
         // ROWS values | RANGE / PARTITION values | value carries | first heads per tile | next heads per tile] for frames
@@ -985,7 +1258,8 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
                 LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
                 LAUNCH(ctx, "k_wagg_ends", k_wagg_ends, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), fr->aggs, heads, tnext, un, (uint32_t)m, agg_stride, elem, fin, mtiles);
             }
-            agg_rows = elem; agg_fin = fin;
+            agg_out = fr->out; agg_n = fr->aggs.n;                     // each from the array its frame left it in
+            for (int a = 0; a < agg_n; ++a) agg_src[a] = (fr->aggs.a[a].frame == SDQH_FRAME_ROWS ? elem : fin) + (size_t)a * agg_stride;
         }
         if (win) {
             const uint64_t pl = (uint64_t)win->per_limit;
@@ -1013,11 +1287,9 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, (uint32_t)m, r.o, r.extra);
     }
     call_end(ctx);                                                    // the call's device time ends here: the fetch is the host's
-    if (fr) {                                                         // the aggregates' first m values, each from the array its frame left them in
-        for (int a = 0; a < fr->aggs.n; ++a) {
-            const uint64_t* from = (fr->aggs.a[a].frame == SDQH_FRAME_ROWS ? agg_rows : agg_fin) + (size_t)a * agg_stride;
-            HIP_TRY(ctx, hipMemcpyAsync(fr->out + (size_t)a * (size_t)capacity, from, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        }
+    if (agg_n) {                                                      // the aggregates' or slides' first m values
+        for (int a = 0; a < agg_n; ++a)
+            HIP_TRY(ctx, hipMemcpyAsync(agg_out + (size_t)a * (size_t)capacity, agg_src[a], (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
         if (!r.narr) if (int rc = sync_stream(ctx)) return rc;
     }
     if (r.narr) if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
@@ -1073,7 +1345,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
@@ -1081,7 +1353,7 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hit
     if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1093,7 +1365,7 @@ int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
     const SortWindow win = {npartition, kind, per_limit, out_rank};
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1120,7 +1392,40 @@ int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hi
         }
         d.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op == SDQH_WAGG_SUM && d.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                            int nslides, const sdqh_window_slide* slides, int64_t limit, int64_t capacity,
+                            int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
+    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && slides && nslides >= 1 && nslides <= SDQH_WSLIDE_MAX_AGGS;
+    for (int a = 0; ok && a < nslides; ++a) ok = slides[a].op >= SDQH_WAGG_SUM && slides[a].op <= SDQH_WSLIDE_LAST && slides[a].lo <= slides[a].hi;
+    if (int rc = sort_enter(ctx, table, "table_window_slide", ok)) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_window_slide", nterms, in, false, terms)) return rc;
+    SortSlides sd; std::memset(&sd, 0, sizeof(sd));
+    sd.npart = npartition; sd.out = out_aggs; sd.sl.n = nslides;
+    for (int a = 0; a < nslides; ++a) {
+        const sdqh_window_slide& g = slides[a];
+        DevWslide& d = sd.sl.a[a];
+        d.g.op = g.op; d.empty = (uint64_t)g.empty; d.w = 1u;
+        sd.lo[a] = g.lo; sd.hi[a] = g.hi;
+        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
+            const std::string agg = "table_window_slide: slide " + std::to_string(a);
+            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
+            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
+            d.g.sk.kind = g.kind; d.g.sk.index = g.index;
+            d.g.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
+        }
+        d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_window_slide_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {
+    if (!ctx || !tile_rows || !narrow_max_width) return fail(ctx, SDQH_ERR_INVALID, "window_slide_geometry: bad arguments");
+    *tile_rows = SORT_TILE; *narrow_max_width = 0;                    // no kernel walks a frame row by row
+    return SDQH_OK;
 }
 
 int sdqh_window_agg_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {

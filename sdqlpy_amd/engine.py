@@ -23,7 +23,8 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import FRAMES, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, ResultSet, TextRefs, WindowRequest, decode_text
+from .result import FRAMES, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, ResultSet, SlideRequest, TextRefs, WindowRequest, \
+    decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
 TUPLE_SHAPES = {
@@ -166,6 +167,9 @@ class Engine:
         # aggregates over window frames (over: result.FrameRequest) fold on the device where the library has the window aggregate
         # extension (abi.Context.table_window_agg) — route "window_agg", noted with the extra keys "per" and "aggs"
         self.device_window_agg = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_AGG", "1") != "0"
+        # values over sliding frames (sliding: result.SlideRequest) likewise, where the library has the window slide extension
+        # (abi.Context.table_window_slide) — route "window_slide", noted with the extra keys "per" and "slides"
+        self.device_window_slide = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_SLIDE", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1693,31 +1697,37 @@ def _term_text(t):
 
 class _FrameSpec(list):
     """The sort terms of a FrameRequest and, beside them, `measures`: per aggregate its measure as a plain sort column (None for a
-    count) — or None as a whole when some measure is no underived numeric column of the table (text, packed, decoded)."""
+    count) — or None as a whole when some measure is no underived numeric column of the table (text, packed, decoded).  A
+    SlideRequest's likewise; int_values: the columns the table keeps as integer-valued doubles (their results are converted back)."""
     measures = None
+    int_values = ()
 
 
 def _order_spec(top, spec_of):
     """The device's columns for `top`: spec_of(order, eng_or_None) is _device_sort_spec over the table at hand.  A FrameRequest's
     measures go through the same mapping with no engine to derive anything: whatever needs a decoder or a derivation is None there."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, FrameRequest):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest)):
         return spec
     spec = _FrameSpec(spec)
-    cols = list(dict.fromkeys(col for _, _, col, _ in top.aggs if col is not None))
+    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else top.slides)]
+    cols = list(dict.fromkeys(col for col in measured if col is not None))
     plain = spec_of([(c, "asc") for c in cols], False)
     if plain is not None:
         by_name = dict(zip(cols, plain))
-        spec.measures = [by_name.get(col) for _, _, col, _ in top.aggs]
+        spec.measures = [by_name.get(col) for col in measured]
     return spec
 
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide") and _term_text(t) is not None]}
     if isinstance(top, FrameRequest):                        # "order" / "per" as for a window; the aggregates in the order of their columns
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["aggs"] = [list(a) for a in top.aggs]
+    elif isinstance(top, SlideRequest):                      # likewise; lag / lead as the `first` they are, unbounded sides None
+        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+        note["slides"] = [list(a) for a in top.slides]
     elif isinstance(top, WindowRequest):                     # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
@@ -1751,6 +1761,11 @@ def _finish_top(rs, ordered, top):
             if name in rs.columns:
                 raise KeyError("over: the result already has a column %r" % name)
         return ResultSet(rs.columns + [name for name, _, _, _ in top.aggs], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
+    if isinstance(top, SlideRequest):                       # the device's slides, a column each
+        for name in (a[0] for a in top.slides):
+            if name in rs.columns:
+                raise KeyError("sliding: the result already has a column %r" % name)
+        return ResultSet(rs.columns + [a[0] for a in top.slides], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
     if isinstance(top, WindowRequest) and top.name is not None:
         if top.name in rs.columns:
             raise KeyError("window: the result already has a column %r" % top.name)
@@ -1791,6 +1806,9 @@ def _order_route(eng, top, spec):
                  partitions (the window extension and Engine.device_window on; derived terms need what "sorted_by" needs)
     "window_agg" abi.Context.table_window_agg: a FrameRequest of at most WAGG_MAX_AGGS aggregates whose measures are underived numeric
                  columns (the window aggregate extension and Engine.device_window_agg on; terms as for "window")
+    "window_slide" abi.Context.table_window_slide: a SlideRequest of at most WSLIDE_MAX_AGGS slides whose measures are underived numeric
+                 columns (the window slide extension and Engine.device_window_slide on; terms as for "window"); not with a default
+                 beyond 2^53 for a column the table keeps as integer-valued doubles
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1803,6 +1821,12 @@ def _order_route(eng, top, spec):
     if isinstance(top, FrameRequest):
         fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.aggs) <= abi.WAGG_MAX_AGGS and getattr(spec, "measures", None) is not None
         return "window_agg" if fits and on("device_window_agg", "has_window_agg") and terms_ok else "host"
+    if isinstance(top, SlideRequest):
+        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.slides) <= abi.WSLIDE_MAX_AGGS and getattr(spec, "measures", None) is not None
+        # a column the table keeps as integer-valued doubles takes its default as a double and back: one no double holds stays on the host
+        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
+                                for _, _, col, _, _, default in top.slides)
+        return "window_slide" if fits and on("device_window_slide", "has_window_slide") and terms_ok else "host"
     if isinstance(top, WindowRequest):
         return "window" if 1 <= n <= abi.SORT_MAX_KEYS and on("device_window", "has_window") and terms_ok else "host"
     if derived:
@@ -1813,9 +1837,9 @@ def _order_route(eng, top, spec):
 
 
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
-    """The routes "sorted", "sorted_by", "window" and "window_agg" of _order_route: one waited-for call whose arrays are sized from the previous run
+    """The routes "sorted", "sorted_by", "window", "window_agg" and "window_slide" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -1828,6 +1852,18 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
         aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + ((abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3]))
                 for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
         got = eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
+    elif route == "window_slide":
+        slides = []
+        for (_, op, measure, lo, hi, default), col in zip(top.slides, spec.measures):
+            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
+            empty = 0
+            if col is not None:                                  # the default's 64 bits as the device holds the column: a double where the
+                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)  # engine keeps integers as integer-valued doubles (converted back with the rest)
+                fill = slide_empty(default, as_f64 and measure not in spec.int_values)
+                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            slides.append((SLIDE_OPS.index(op), kind, index, is_f64, abi.SLIDE_UNBOUNDED_PRECEDING if lo is None else lo,
+                           abi.SLIDE_UNBOUNDED_FOLLOWING if hi is None else hi, empty))
+        got = eng.ctx.table_window_slide(table, min_hits, top.npartition, terms, slides, k, cap, want_hits=want_hits)
     else:
         got = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap,
                                    want_hits=want_hits, want_rank=top.name is not None)
@@ -1885,6 +1921,8 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         spec = _order_spec(top, lambda order, derive: _device_sort_spec(bt, out_key_fields, vnames, count_idx, order, eng if derive else None, fields_of)) \
             if top is not None and entry_is_group else None
         lazy = lazy_ok and bool(getattr(eng, "lazy_results", False)) and _lazy_rows_ok(bt, out_key_fields, fields_of, top)
+        if isinstance(spec, _FrameSpec):
+            spec.int_values = bt.int_values
         want_hits = count_idx is not None or (spec is not None and any(s[0] == abi.SORT_HITS for s in spec))
         hint = eng.compact_hints.get(hint_key)
         if lazy and defer and hint is not None:
@@ -1918,6 +1956,8 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         keys, payload, values, hits, ordered = _fetch_entries(eng, bt.table, 1, hint_key, top, spec, want_hits=want_hits, lazy=lazy)
         if isinstance(ordered, _Ranked) and isinstance(top, FrameRequest):      # an integer-valued sum folded as doubles: the conversion its own column gets
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _) in zip(ordered.rank, top.aggs)]
+        if isinstance(ordered, _Ranked) and isinstance(top, SlideRequest):      # likewise: whatever a slide takes of such a column is an integer
+            ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.slides)]
         values = [values[j] for j in range(nv)]
         if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:    # several key fields in one mixed-radix integer
             from . import xplan
@@ -2052,7 +2092,7 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, FrameRequest) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
@@ -2063,6 +2103,8 @@ def _finalize(eng, op, env, top=None):
             route["order"], route["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         if isinstance(top, FrameRequest):
             route["aggs"] = [list(a) for a in top.aggs]
+        if isinstance(top, SlideRequest):
+            route["slides"] = [list(a) for a in top.slides]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)

@@ -130,6 +130,11 @@ def check_window_columns(req, columns):
             raise KeyError("over: the result has no column %r" % col)
         if name in columns:
             raise KeyError("over: the result already has a column %r" % name)
+    for name, _, col, _, _, _ in getattr(req, "slides", ()):
+        if col is not None and col not in columns:
+            raise KeyError("sliding: the result has no column %r" % col)
+        if name in columns:
+            raise KeyError("sliding: the result already has a column %r" % name)
 
 
 WAGG_OPS = ("sum", "count", "min", "max")                 # their positions are abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX
@@ -183,6 +188,93 @@ def frame_request(columns, by, order, aggs, frame="range", k=WINDOW_ALL):
     if columns is not None:
         check_window_columns(req, columns)
     return req
+
+
+SLIDE_OPS = ("sum", "count", "min", "max", "first", "last")      # their positions are abi.WAGG_SUM .. WAGG_MAX, WSLIDE_FIRST, WSLIDE_LAST
+
+
+class SlideRequest(WindowRequest):
+    """Values over sliding window frames, travelling where a FrameRequest travels (every row is kept): [0] = the limit on the whole
+    result, [1] = the PARTITION BY terms followed by the ORDER BY terms, npartition, and slides = [(name of the new column, op: a name
+    of SLIDE_OPS, measure column or None for a count, lo, hi: the frame's offsets from the row — negative = preceding, None =
+    unbounded —, default: what an empty frame gives, None = 0 for an int64 measure and NaN for a float64 one)] in the order the
+    columns are appended.  lag / lead are `first` over (-k, -k) / (k, k) by the time they are here."""
+
+    def __new__(cls, k, terms, npartition, slides):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.slides = [(str(n), str(op), None if col is None else str(col), lo, hi, default) for n, op, col, lo, hi, default in slides]
+        if not self.slides or any(op not in SLIDE_OPS or (col is None and op != "count") or (lo is not None and hi is not None and lo > hi)
+                                  for _, op, col, lo, hi, _ in self.slides):
+            raise ValueError("sliding: bad aggregate")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
+        names = names or {}
+        return SlideRequest(self[0], terms, self.npartition, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.slides])
+
+
+def _slide_int(x, what):
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+        raise ValueError("sliding: %s is an integer, not %r" % (what, x))
+    return int(x)
+
+
+def slide_request(columns, by, order, aggs, k=WINDOW_ALL):
+    """The checked SlideRequest of `sliding`: by / order as window_request takes them; aggs = {new column: (op, measure column or None,
+    lo, hi[, default])} with op a name of SLIDE_OPS and lo / hi ints relative to the row (negative = preceding, None = unbounded), or
+    ("lag" | "lead", measure, k[, default]) with k >= 0: `first` over (-k, -k) / (k, k).  columns: the result's column names when they
+    are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has already, ValueError
+    for everything else (a default that does not fit its column is found when the column is known: slide_empty)."""
+    req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("sliding: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default])}")
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) < 2:
+            raise ValueError("sliding: an aggregate is name: (op, measure, lo, hi[, default]) or (lag | lead, measure, k[, default])")
+        op, col = spec[0], spec[1]
+        if op in ("lag", "lead"):
+            if len(spec) not in (3, 4):
+                raise ValueError("sliding: %s is (%s, measure, k[, default])" % (op, op))
+            back = _slide_int(spec[2], "k")
+            if back < 0:
+                raise ValueError("sliding: k is at least 0")
+            lo = hi = -back if op == "lag" else back
+            op, default = "first", (spec[3] if len(spec) == 4 else None)
+        else:
+            if op not in SLIDE_OPS:
+                raise ValueError("sliding: op is one of %s, lag, lead, not %r" % (", ".join(SLIDE_OPS), op))
+            if len(spec) not in (4, 5):
+                raise ValueError("sliding: an aggregate is name: (op, measure, lo, hi[, default])")
+            lo = None if spec[2] is None else _slide_int(spec[2], "a bound")
+            hi = None if spec[3] is None else _slide_int(spec[3], "a bound")
+            default = spec[4] if len(spec) == 5 else None
+            if lo is not None and hi is not None and lo > hi:
+                raise ValueError("sliding: the frame (%d, %d) ends before it starts" % (lo, hi))
+        if col is None and op != "count":
+            raise ValueError("sliding: %s needs a measure column" % op)
+        if col is not None and not isinstance(col, str):
+            raise ValueError("sliding: a measure is a column name")
+        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
+            raise ValueError("sliding: a default is a number, not %r" % (default,))
+        out.append((name, op, col, lo, hi, default))
+    req = SlideRequest(req[0], req[1], req.npartition, out)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
+
+
+def slide_empty(default, is_f64, what="sliding"):
+    """What an empty frame gives for a measure of dtype float64 (is_f64) or int64: `default`, or with None NaN / 0.  ValueError for a
+    default that does not fit the dtype: a float for an int64 column, an int outside int64."""
+    if is_f64:
+        return np.float64(np.nan if default is None else default)
+    if default is None:
+        return np.int64(0)
+    if isinstance(default, (float, np.floating)) or not -(1 << 63) <= int(default) < (1 << 63):
+        raise ValueError("%s: the default %r does not fit an int64 column" % (what, default))
+    return np.int64(int(default))
 
 
 def order_image(a, descending):
@@ -385,6 +477,67 @@ class ResultSet:
         cols = [a[idx[:k]] for a in self._cols]                          # undecoded text stays undecoded
         return ResultSet(self.columns + [nm for nm, _ in new], cols + [a[:k] for _, a in new])
 
+    def slid(self, req):
+        """Every row in a SlideRequest's order (the first req[0] of them) with its columns appended: what sdqh_table_window_slide does on
+        the device (include/sdqh_sort_slide.h), on the host.  The frame of sorted row j in a partition [s, e] is [max(j + lo, s),
+        min(j + hi, e)].  COUNT is arithmetic, FIRST / LAST gather, an integer SUM is a difference of wrapping prefix sums (exact
+        mod 2^64); a double SUM and MIN / MAX (on the images of sdqh_extrema.h) fold exactly the frame's rows, nothing is subtracted:
+        row by row for narrow frames, else through prefix and suffix folds of blocks of the frame's width, as the device does."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, part_head, _ = self._window_heads(req.by, req.order)
+        n = self._n
+        pos = np.arange(n, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(part_head, pos, 0)) if n else pos
+        heads = np.nonzero(part_head)[0]
+        end = (np.append(heads[1:], n) - 1)[np.cumsum(part_head) - 1] if n else pos
+        top = np.uint64(1) << np.uint64(63)
+        new = []
+        for name, op, col, lo, hi, default in req.slides:
+            x = None if op == "count" else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("sliding: %s of column %r: the measure is not numeric" % (op, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            fill = None if op == "count" else slide_empty(default, is_f)
+            lo_c = -n if lo is None else max(-n, min(n, lo))             # an offset of n or more leaves every partition
+            hi_c = n if hi is None else max(-n, min(n, hi))
+            left, right = np.maximum(pos + lo_c, start), np.minimum(pos + hi_c, end)
+            empty = left > right
+            a, b = np.where(empty, pos, left), np.where(empty, pos, right)       # (an empty frame reads its own row, then takes the default)
+            if op == "count":
+                new.append((name, np.where(empty, 0, right - left + 1).astype(np.int64)))
+                continue
+            x = np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+            if op in ("first", "last"):
+                v = x[a] if op == "first" else x[b]
+            elif op == "sum" and not is_f:
+                c = np.concatenate((np.zeros(1, np.uint64), np.cumsum(x.view(np.uint64), dtype=np.uint64)))
+                v = (c[b + 1] - c[a]).view(np.int64)
+            else:
+                if op == "sum":
+                    e, fold = x, np.add
+                else:                                                    # unsigned maximum of the images, reversed for MIN, NaN = 0
+                    e, fold = order_image(x, op == "min"), np.maximum
+                    e = np.where(np.isnan(x), np.uint64(0), e) if is_f else e
+                v = _slide_fold(e, fold, a, b, start, end, max(1, min(hi_c - lo_c + 1, n)))
+                if op != "sum":
+                    u = ~v if op == "min" else v
+                    if is_f:
+                        v = np.where(v == 0, np.uint64(0x7FF8000000000000), np.where(u >> np.uint64(63) != 0, u ^ top, ~u)).view(np.float64)
+                    else:
+                        v = (u ^ top).view(np.int64)
+            bits = np.where(empty, np.array(fill).view(np.uint64), np.ascontiguousarray(v).view(np.uint64))      # (by bits: a NaN default keeps its payload)
+            new.append((name, bits.view(np.float64 if is_f else np.int64)))
+        k = max(0, min(int(req[0]), n))
+        cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:k] for _, c in new])
+
+    def sliding(self, by, order, aggs):
+        """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:
+        aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS, the frame rows [row + lo, row + hi] of
+        the group (None: unbounded), or ("lag" | "lead", measure, k[, default]).  An empty frame gives `default` (0 / NaN), a count 0."""
+        return self.slid(slide_request(self.columns, by, order, aggs))
+
     def over(self, by, order, aggs, frame="range"):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over the row's frame inside its group of `by`:
         aggs = {new column: (op, measure column or None[, frame])}, op in WAGG_OPS, frame in FRAMES ("rows": group start .. this
@@ -395,6 +548,8 @@ class ResultSet:
         """The rows a WindowRequest keeps, in its order, with its rank column when it names one (a FrameRequest: framed)."""
         if isinstance(req, FrameRequest):
             return self.framed(req)
+        if isinstance(req, SlideRequest):
+            return self.slid(req)
         self._wait()
         check_window_columns(req, self.columns)
         idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])
@@ -483,6 +638,39 @@ class DictResult:
 
     def __str__(self):
         return str(self.to_dict())
+
+
+SLIDE_WALK_MAX = 32          # frames at most this wide are folded row by row on the host
+
+
+def _slide_fold(e, fold, a, b, start, end, w):
+    """fold over e[a[j] .. b[j]] for every j (a <= b, both inside j's partition [start, end], b - a < w): left to right row by row
+    for w <= SLIDE_WALK_MAX; else the partitions are cut into blocks of w positions from their start, every block is folded from its
+    first position (prefix) and up to its last (suffix), and a frame — it spans at most two adjacent blocks — is suffix[a] then
+    prefix[b], or whichever of the two covers it alone.  The two folds are segmented scans by doubling over the whole array (after the
+    step of distance d a position holds the fold of the min(2d, its distance into the block) positions ending at it): log2(w) numpy
+    passes whatever the number of partitions, every row of a block entering once, the lower positions on the left."""
+    n = len(e)
+    if n == 0:
+        return e.copy()
+    if w <= SLIDE_WALK_MAX:
+        v = e[a]
+        for d in range(1, w):
+            at = a + d
+            inside = at <= b
+            v = np.where(inside, fold(v, e[np.where(inside, at, a)]), v)
+        return v
+    pos = np.arange(n, dtype=np.int64)
+    first = start + (pos - start) // w * w                               # the block's first and last position
+    last = np.minimum(first + w - 1, end)
+    pre, suf, d = e, e, 1
+    while d < min(w, n):
+        pre = np.where(pos - d >= first, fold(pre[np.maximum(pos - d, 0)], pre), pre)
+        suf = np.where(pos + d <= last, fold(suf, suf[np.minimum(pos + d, n - 1)]), suf)
+        d *= 2
+    ra, rb = a - start, b - start
+    two = ra // w != rb // w
+    return np.where(two, fold(suf[a], pre[b]), np.where(ra % w == 0, pre[b], suf[a]))
 
 
 class Pending:

@@ -424,11 +424,28 @@ def sdql_compile(in_type):
             req = frame_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, frame)     # checked before anything is launched
             return lambda *args: run(args, req)
 
+        def sliding(by, order, aggs):
+            """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a SLIDING frame inside the row's
+            group of `by`: aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in "sum" / "count" / "min" / "max" /
+            "first" / "last", the frame the rows [row + lo, row + hi] of the group (negative = preceding, None = unbounded), or
+            ("lag" | "lead", measure, k[, default]), e.g. ``q3.sliding(["o_orderdate"], [("revenue", "desc")], {"prev": ("lag",
+            "revenue", 1), "ma3": ("sum", "revenue", -2, 0), "n3": ("count", None, -2, 0)})(li, cu, ord)``.  An empty frame gives
+            `default` (0 for an int64 measure, NaN for a float64 one), a count 0.  Names, ops, bounds and k are checked here, before
+            anything is launched; whether a default fits its column (a float for an int64 measure does not) can only be told once the
+            query has run and the column's dtype is known: that ValueError comes from the call."""
+            from . import engine, frontend
+            from .result import slide_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = slide_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
         wrapper.numbered = numbered
         wrapper.over = over
+        wrapper.sliding = sliding
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
