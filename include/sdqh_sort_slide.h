@@ -11,8 +11,8 @@
  * bitmap-only table or a compile-only context (argument checks first) and the wait for the stream are exactly those of
  * sdqh_table_window_agg, declared in sdqh_sort_frames.h.  What differs is the frame.
  *
- * Not here: value-based frames (RANGE BETWEEN x PRECEDING ...), GROUPS frames, AVG (divide a SUM by a COUNT of the same frame), text
- * measures, and the multi-GPU runner. */
+ * Not here: AVG (divide a SUM by a COUNT of the same frame), text measures, and the multi-GPU runner.  Value-based frames (RANGE BETWEEN x
+ * PRECEDING ...) and GROUPS frames are the sixth extension's: sdqh_sort_range.h. */
 #ifndef SDQH_SORT_SLIDE_H
 #define SDQH_SORT_SLIDE_H
 

@@ -43,6 +43,12 @@ WINDOW_SLIDE_EXPORTS = ["sdqh_table_window_slide", "sdqh_window_slide_geometry"]
 WSLIDE_FIRST, WSLIDE_LAST = 4, 5
 SLIDE_UNBOUNDED_PRECEDING, SLIDE_UNBOUNDED_FOLLOWING = -(1 << 63), (1 << 63) - 1
 WSLIDE_MAX_AGGS = 4
+# ... and its sixth (include/sdqh_sort_range.h, Library.has_window_range): the same six ops over VALUE and GROUP frames — RANGE / GROUPS
+# BETWEEN lo AND hi, offsets of the ORDER BY value or counts of tie runs
+WINDOW_RANGE_EXPORTS = ["sdqh_table_window_range", "sdqh_window_range_geometry"]
+WRANGE_VALUE, WRANGE_GROUPS = 0, 1
+WRANGE_LO_UNBOUNDED, WRANGE_HI_UNBOUNDED = 1, 2
+WRANGE_MAX_AGGS = 4
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -53,6 +59,17 @@ MAX_IPRED, MAX_FPRED, MAX_SPRED, MAX_STR_CONST = 4, 4, 1, 64
 MAX_PROBE, MAX_PAYLOAD, MAX_GROUPKEYS, MAX_SMALL_GROUPS, MAX_COMPACT_COLS = 2, 4, 2, 64, 6
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def _range_offset(x):
+    """A frame offset of sdqh_window_range as its int64: an int as it is, a float as its bits, None (unbounded: ignored) as 0."""
+    if x is None:
+        return 0
+    if isinstance(x, (float, np.floating)):
+        return int(np.float64(x).view(np.int64))
+    if not INT64_MIN <= int(x) <= INT64_MAX:                 # (ctypes would cut it to 64 bits without a word)
+        raise SdqhError(ERR_INVALID, "table_window_range: the offset %d does not fit int64" % int(x))
+    return int(x)
 
 
 class SdqhError(RuntimeError):
@@ -115,6 +132,13 @@ class WindowAgg(C.Structure):
 class WindowSlide(C.Structure):
     """sdqh_window_slide: an op, its measure (as a SortKey names a column), the frame's signed offsets and the 64 bits of an empty frame."""
     _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
+
+
+class WindowRange(C.Structure):
+    """sdqh_window_range: an op, its measure (as a SortKey names a column), the frame's unit and unbounded-side flags, its signed offsets
+    (int64, or the bits of doubles for a VALUE frame over a double term) and the 64 bits of an empty frame."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32),
+                ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
 
 
 SRC_COLUMN, SRC_LOOKUP, SRC_LOOKUP_YEAR = 0, 1, 2
@@ -1313,6 +1337,35 @@ class Context:
         self._check(self.lib.sdqh_window_slide_geometry(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def _need_window_range(self, what):
+        if not self.library.has_window_range:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window range extension (include/sdqh_sort_range.h)" % (what, self.library.path))
+
+    def table_window_range(self, table, min_hits, npartition, terms, ranges, limit, capacity, want_hits=True):
+        """Values over value and group frames of the ordered entries: terms and npartition as table_window takes them; ranges: [(op,
+        kind, index, is_f64, unit, lo, hi, empty)] — op and the measure as table_window_slide takes them, unit WRANGE_VALUE (offsets
+        of the one ORDER BY term's value: ints for an integer term, floats for a double one) or WRANGE_GROUPS (offsets count tie runs),
+        lo / hi signed along the order (negative = preceding, None: unbounded), empty: the 64 bits an empty frame gives, as an int64.
+        Every selected row is kept; the first min(limit, n) in sorted order.  Returns what table_window_slide returns."""
+        self._need_window_range("table_window_range")
+        arr = (WindowRange * max(1, len(ranges)))()
+        for i, (op, kind, index, is_f64, unit, lo, hi, empty) in enumerate(ranges):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64, arr[i].unit = int(op), int(kind), int(index), 1 if is_f64 else 0, int(unit)
+            arr[i].flags = (WRANGE_LO_UNBOUNDED if lo is None else 0) | (WRANGE_HI_UNBOUNDED if hi is None else 0)
+            arr[i].lo, arr[i].hi, arr[i].empty = _range_offset(lo), _range_offset(hi), int(empty)
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(ranges)), arr, C.c_int64(limit))
+        got = self._sorted_call("table_window_range", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(ranges)))
+        as_f64 = [r[0] != WAGG_COUNT and (r[1] == SORT_VALUE or (r[1] == SORT_PAYLOAD and bool(r[3]))) for r in ranges]
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def window_range_geometry(self):
+        """(sorted positions per tile of sdqh_table_window_range's passes, the largest frame width a kernel walks row by row or 0): what
+        the tests size their cases from."""
+        self._need_window_range("window_range_geometry")
+        a, b = C.c_int64(), C.c_int64()
+        self._check(self.lib.sdqh_window_range_geometry(self.handle, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1582,6 +1635,11 @@ class Library:
             L.sdqh_table_window_slide.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_slide_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_window_range = self.has_window_slide and all(hasattr(L, s) for s in WINDOW_RANGE_EXPORTS)    # ... and value / group frames (include/sdqh_sort_range.h)
+        if self.has_window_range:
+            L.sdqh_table_window_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_range_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -23,8 +23,8 @@
 //   k_sort_emit       the first min(limit, n) rows in order, columns as sdqh_table_compact lays them out
 //
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
-// (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h) and sdqh_table_window_slide
-// (include/sdqh_sort_slide.h): select -> order -> rank, aggregate or slide -> emit
+// (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h), sdqh_table_window_slide
+// (include/sdqh_sort_slide.h) and sdqh_table_window_range (include/sdqh_sort_range.h): select -> order -> rank, aggregate, slide or range -> emit
 // (ordered_impl).  What differs between them is
 // data, not code:
 //
@@ -77,6 +77,15 @@
 //   k_wsl_tiles / k_wsl_scan / k_wsl_run
 //                     the tile scan of the frames, restarted at block heads, forwards (prefix folds) and backwards (suffix folds)
 //   k_wsl_fold        row j's frame [l, r] spans at most two blocks: suffix[l] (+) prefix[r], or one of them — see the section
+//   RANGES            in their place (SortRanges).  sdqh_table_window_range (include/sdqh_sort_range.h) takes the same six ops over VALUE
+//                     and GROUP frames, whose width depends on the data.  Behind k_win_heads, k_win_scan, k_wsl_rows and k_wagg_next:
+//
+//   k_win_rank        only with a GROUPS range: the dense rank of every position (every row kept)
+//   k_wrg_stage       backwards: per position its partition's last position, one ordered 64-bit key (the ORDER BY term's sort key /
+//                     the rank's image) and every range's element — raw, or as a leaf of the range's fold tree
+//   k_wrg_tiles / k_wrg_upper
+//                     the fold trees bottom-up: nine levels inside the wave that owns a tile, the rest in one workgroup per range
+//   k_wrg_fold        per row two binary searches of its partition for the frame's ends, then the tree's iterative query — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -84,12 +93,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
-#include "sdqh_sort_slide.h"
+#include "sdqh_sort_range.h"
 
 using namespace sdqh_host;
 
@@ -945,6 +955,198 @@ __global__ __launch_bounds__(TPB) void k_wsl_fold(DevWslides sl, const uint32_t*
     }
 }
 
+// ---- value and group frames (sdqh_table_window_range) ----------------------------------------------------------------------------
+// The frame of sorted row j is an interval [l, r] of its partition [s, e] whose ends depend on the data: the positions whose ORDER
+// BY value (VALUE) or tie-run number (GROUPS) lies within the offsets of row j's.  Both are found by binary search over one ordered
+// 64-bit KEY per sorted position — VALUE: the sort key of the one ORDER BY term (the order-preserving image k_sort_keys made,
+// ascending with the position whatever the term's direction, from which v(j) is decoded again); GROUPS: the image of the dense rank
+// k_win_rank stored — against bounds made without a wrapping add (128-bit integers) or with the one IEEE add (doubles).  COUNT is
+// r - l + 1, FIRST / LAST gather the raw element at l / r.  SUM / MIN / MAX read a bottom-up binary FOLD TREE over the sorted
+// positions (node k = node 2k (+) node 2k + 1, the leaves at [cap, cap + n), cap = the power of two at or above n): the iterative
+// query keeps a left and a right accumulator, joins at most 2 log2(r - l + 1) + 2 nodes in position order, and its association is a
+// function of (l, r) and cap alone — rows with the same frame get the same bits, nothing is subtracted, no atomics.  A node that
+// covers a position >= n is never read by a query (r < n) and stands for the identity wherever a parent is made of it.
+constexpr int WRG_TILE_LEVELS = 9;
+static_assert((1 << WRG_TILE_LEVELS) == SORT_TILE && SORT_TILE == 8 * WAVE, "a wave folds its tile's nine levels: three in a lane's registers, six by shuffles");
+// g.frame unused; g.cls: WSL_NONE when nothing is folded; slot: which fold tree (a folded range) / raw element array (FIRST, LAST) is
+// this range's — each kind numbered from 0 on its own, so a COUNT takes neither and memory is one tree per FOLDED range
+struct DevWrange { DevWagg g; int32_t unit, flags; int64_t lo, hi; uint64_t empty; int32_t slot, _pad; };
+struct DevWranges { DevWrange a[SDQH_WRANGE_MAX_AGGS]; int32_t n, vcol, vdesc, vf64; };   // vcol: the ORDER BY term of the VALUE ranges (-1: none), its direction and type
+
+// One bounded side of an integer frame: the key a position's key is searched against.  Returns 0: `key` is set; 1: every row of the
+// partition lies inside this bound; 2: none does.  tv = v(j) + d * off in 128 bits; beyond int64 it is a bound that no value reaches.
+__device__ __forceinline__ int wrg_int_bound(int64_t vj, int64_t off, bool desc, bool lo_side, uint64_t& key) {
+    const __int128 tv = (__int128)vj + (desc ? -(__int128)off : (__int128)off);
+    const bool over = tv > (__int128)INT64_MAX, under = tv < (__int128)INT64_MIN;
+    if (over || under) return ((over != desc) != lo_side) ? 1 : 2;
+    key = sort_bits((int64_t)tv, 0, desc ? 1 : 0);
+    return 0;
+}
+// a double bound as a key: the lower end of an IEEE comparison takes -0.0 for a zero, the upper end +0.0, so both zeros are in or out
+__device__ __forceinline__ uint64_t wrg_f64_key(double x, bool lower, bool desc) {
+    if (x == 0.0) x = lower ? -0.0 : 0.0;
+    return sort_bits(__double_as_longlong(x), 1, desc ? 1 : 0);
+}
+// the first position of [a, b) whose key is >= k (b: none) / > k
+__device__ __forceinline__ uint32_t wrg_lower(const uint64_t* __restrict__ key, uint32_t a, uint32_t b, uint64_t k) {
+    while (a < b) { const uint32_t mid = a + (b - a) / 2u; if (key[mid] < k) a = mid + 1u; else b = mid; }
+    return a;
+}
+__device__ __forceinline__ uint32_t wrg_upper(const uint64_t* __restrict__ key, uint32_t a, uint32_t b, uint64_t k) {
+    while (a < b) { const uint32_t mid = a + (b - a) / 2u; if (key[mid] <= k) a = mid + 1u; else b = mid; }
+    return a;
+}
+
+// 1. a tile walked backwards (k_wsl_blocks' shape): per position the last position of its partition, the key of the VALUE ranges
+// (vkey[r] = the ORDER BY term's sort key of the entry at r; vkey == nullptr: no VALUE range) and of the GROUPS ranges (gkey[r] = the
+// image of the dense rank; nullptr: none), and every range's element — raw for FIRST / LAST into elem[slot * stride + r], the fold's
+// element for SUM / MIN / MAX into its tree's leaf tree[slot * tstride + cap + r], none for COUNT (perm -> refs -> stage once)
+__global__ __launch_bounds__(TPB) void k_wrg_stage(DevStage st, DevWranges rg, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ heads,
+                                                  const WaggHeads* __restrict__ tnext, const uint64_t* __restrict__ keys, const uint32_t* __restrict__ rank, uint32_t n, size_t stride,
+                                                  size_t tstride, uint64_t cap, uint32_t* __restrict__ pend, uint64_t* __restrict__ vkey, uint64_t* __restrict__ gkey,
+                                                  uint64_t* __restrict__ elem, uint64_t* __restrict__ tree, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint32_t next = tnext[w].part;
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const uint64_t pg = h.mp & ~le;
+        const uint32_t pe = (pg ? (uint32_t)b + (uint32_t)__builtin_ctzll(pg) : next) - 1u;
+        if (live) {
+            const uint32_t g = perm ? perm[r] : (uint32_t)r;
+            const bool ok = g < n;                                       // (a permutation of [0, n): always)
+            const int64_t idx = ok ? (int64_t)refs[g] : 0;
+            const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u;
+#pragma unroll
+            for (int a = 0; a < SDQH_WRANGE_MAX_AGGS; ++a) if (a < rg.n) {
+                const DevWrange& d = rg.a[a];
+                if (d.g.op == SDQH_WAGG_COUNT) continue;
+                if (d.g.cls == WSL_NONE) elem[(size_t)d.slot * stride + r] = ok ? (uint64_t)sort_raw(d.g.sk, st, idx, hits) : 0ull;
+                else tree[(size_t)d.slot * tstride + cap + r] = ok ? wagg_element(d.g, st, idx, hits) : wagg_identity(d.g.cls);
+            }
+            pend[r] = pe;
+            if (vkey) vkey[r] = ok ? keys[g] : 0ull;
+            if (gkey) gkey[r] = sort_bits((int64_t)rank[r], 0, 0);
+        }
+        if (h.mp) next = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (b == r0) break;
+    }
+}
+// 2. the lowest nine levels of every folded range's tree, a wave per tile of SORT_TILE leaves: lane i takes the eight leaves
+// [8i, 8i + 8) of the tile (past n: the identity) and folds three levels in its registers, the wave folds six more by shuffles —
+// the lane whose number is a multiple of 2^k holds the node over lanes [lane, lane + 2^k) — and every node is stored at its level:
+// node (cap >> h) + ((first leaf) >> h) covers 2^h leaves.  Operands stay in position order.
+__global__ __launch_bounds__(TPB) void k_wrg_tiles(DevWranges rg, uint32_t n, size_t tstride, uint64_t cap, uint64_t* __restrict__ tree, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+#pragma unroll
+    for (int a = 0; a < SDQH_WRANGE_MAX_AGGS; ++a) if (a < rg.n && rg.a[a].g.cls != WSL_NONE) {
+        const int cls = rg.a[a].g.cls;
+        const uint64_t id = wagg_identity(cls);
+        uint64_t* __restrict__ t = tree + (size_t)rg.a[a].slot * tstride;
+        const uint64_t p0 = r0 + 8ull * lane;                            // this lane's first leaf
+        uint64_t v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = p0 + i < r1 ? t[cap + p0 + i] : id;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { v[i] = wagg_join(cls, v[2 * i], v[2 * i + 1]); t[(cap >> 1) + (p0 >> 1) + i] = v[i]; }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) { v[i] = wagg_join(cls, v[2 * i], v[2 * i + 1]); t[(cap >> 2) + (p0 >> 2) + i] = v[i]; }
+        uint64_t x = wagg_join(cls, v[0], v[1]);
+        t[(cap >> 3) + (p0 >> 3)] = x;
+#pragma unroll
+        for (int k = 1; k <= WRG_TILE_LEVELS - 3; ++k) {
+            const uint64_t o = (uint64_t)__shfl_down((long long)x, 1u << (k - 1), WAVE);
+            if ((lane & ((1u << k) - 1u)) == 0u) { x = wagg_join(cls, x, o); t[(cap >> (3 + k)) + (p0 >> (3 + k))] = x; }
+        }
+    }
+}
+// 3. workgroup b: the levels above the tiles of tree b (the folded range whose slot is b), one level at a time (a workgroup barrier between two levels:
+// every node is written by one thread and read by another of this workgroup).  Level h has cap >> h nodes; node i of it covers the
+// tiles from i << (h - 9) on, and one whose first tile is not below ntiles was never written: the identity.
+__global__ __launch_bounds__(TPB) void k_wrg_upper(DevWranges rg, size_t tstride, uint64_t cap, uint64_t* __restrict__ tree, uint32_t ntiles) {
+    int a = 0;
+    while (a < rg.n && !(rg.a[a].g.cls != WSL_NONE && rg.a[a].slot == (int)blockIdx.x)) ++a;
+    if (a >= rg.n) return;
+    const int cls = rg.a[a].g.cls;
+    const uint64_t id = wagg_identity(cls);
+    uint64_t* t = tree + (size_t)blockIdx.x * tstride;
+    for (int h = WRG_TILE_LEVELS + 1; (cap >> h) >= 1ull; ++h) {
+        const uint64_t cnt = cap >> h;                                   // nodes of this level: [cnt, 2 cnt)
+        const int up = h - WRG_TILE_LEVELS;                              // a node of it covers 2^up tiles
+        const uint64_t live = min(cnt, (((uint64_t)ntiles - 1ull) >> up) + 1ull);      // those whose first tile exists
+        for (uint64_t i = threadIdx.x; i < live; i += TPB) {
+            const uint64_t right_first = (2ull * i + 1ull) << (up - 1);
+            const uint64_t l = t[2ull * (cnt + i)], r = right_first < (uint64_t)ntiles ? t[2ull * (cnt + i) + 1ull] : id;
+            t[cnt + i] = wagg_join(cls, l, r);
+        }
+        __syncthreads();
+    }
+}
+// 4. the value of every range at the first m positions: fin[a * stride + j] — the two ends of the frame searched in [s, e], then
+// COUNT / FIRST / LAST off the ends or the tree's iterative query.  rown: k_wsl_rows' (s = j - rown[j]); pend: k_wrg_stage's (e).
+__global__ __launch_bounds__(TPB) void k_wrg_fold(DevWranges rg, const uint32_t* __restrict__ rown, const uint32_t* __restrict__ pend, const uint64_t* __restrict__ vkey,
+                                                 const uint64_t* __restrict__ gkey, uint32_t n, uint32_t m, size_t stride, size_t tstride, uint64_t cap,
+                                                 const uint64_t* __restrict__ elem, const uint64_t* __restrict__ tree, uint64_t* __restrict__ fin) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t rn = rown[j], e = pend[j];
+        if ((uint64_t)rn > j || (uint64_t)e < j || e >= n) continue;       // (s <= j <= e < n: never taken)
+        const uint32_t s = (uint32_t)j - rn;
+#pragma unroll
+        for (int a = 0; a < SDQH_WRANGE_MAX_AGGS; ++a) if (a < rg.n) {
+            const DevWrange& d = rg.a[a];
+            const bool groups = d.unit == SDQH_WRANGE_GROUPS;
+            const uint64_t* __restrict__ key = groups ? gkey : vkey;
+            const bool desc = !groups && rg.vdesc != 0, f64 = !groups && rg.vf64 != 0;
+            const uint64_t kj = key[j];
+            // each side: 0 = search for `kl` / `kr`, 1 = the partition's end, 2 = no row at all
+            int sl = (d.flags & SDQH_WRANGE_LO_UNBOUNDED) ? 1 : 0, sr = (d.flags & SDQH_WRANGE_HI_UNBOUNDED) ? 1 : 0;
+            uint64_t kl = kj, kr = kj;
+            if (!f64) {
+                const int64_t vj = (int64_t)((desc ? ~kj : kj) ^ (1ull << 63));
+                if (sl == 0) sl = wrg_int_bound(vj, d.lo, desc, true, kl);
+                if (sr == 0) sr = wrg_int_bound(vj, d.hi, desc, false, kr);
+            } else {
+                const uint64_t u = desc ? ~kj : kj;
+                const double vj = __longlong_as_double((long long)((u >> 63) ? (u ^ (1ull << 63)) : ~u));
+                if (vj == vj) {                                          // a NaN row: its own tie run on every bounded side (kl = kr = kj)
+                    const double lo = __longlong_as_double(d.lo), hi = __longlong_as_double(d.hi);
+                    const double fa = vj + (desc ? -lo : lo), fb = vj + (desc ? -hi : hi);
+                    // ascending the lo side is the lower value bound, descending the upper one; with both sides the smaller bounds below
+                    double x = desc ? fb : fa, y = desc ? fa : fb;
+                    if (sl == 0 && sr == 0 && x > y) { const double t = x; x = y; y = t; }
+                    if (desc) { kl = wrg_f64_key(y, false, true); kr = wrg_f64_key(x, true, true); }
+                    else { kl = wrg_f64_key(x, true, false); kr = wrg_f64_key(y, false, false); }
+                }
+            }
+            const uint32_t l = sl == 1 ? s : wrg_lower(key, s, e + 1u, kl);
+            const uint32_t r1 = sr == 1 ? e + 1u : wrg_upper(key, s, e + 1u, kr);       // one past the frame's last position
+            const bool none = sl == 2 || sr == 2 || l >= r1;
+            uint64_t v;
+            if (d.g.op == SDQH_WAGG_COUNT) v = none ? 0ull : (uint64_t)(r1 - l);
+            else if (none) v = d.empty;
+            else if (d.g.op == SDQH_WSLIDE_FIRST) v = elem[(size_t)d.slot * stride + l];
+            else if (d.g.op == SDQH_WSLIDE_LAST) v = elem[(size_t)d.slot * stride + (r1 - 1u)];
+            else {
+                const int cls = d.g.cls;
+                const uint64_t* __restrict__ t = tree + (size_t)d.slot * tstride;
+                uint64_t left = wagg_identity(cls), right = left;
+                for (uint64_t p = cap + l, q = cap + r1; p < q; p >>= 1, q >>= 1) {
+                    if (p & 1ull) left = wagg_join(cls, left, t[p++]);
+                    if (q & 1ull) right = wagg_join(cls, t[--q], right);
+                }
+                v = wagg_result(d.g, wagg_join(cls, left, right));
+            }
+            fin[(size_t)a * stride + j] = v;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1143,20 +1345,23 @@ struct SortWindow { int npart, kind; int64_t per_limit; int64_t* out_rank; };
 struct SortFrames { int npart; DevWaggs aggs; int64_t* out; };
 // ... or values over sliding frames (sdqh_table_window_slide): likewise; lo / hi as the caller gave them (sl's are set once n is known)
 struct SortSlides { int npart; DevWslides sl; int64_t lo[SDQH_WSLIDE_MAX_AGGS], hi[SDQH_WSLIDE_MAX_AGGS]; int64_t* out; };
+// ... or values over value and group frames (sdqh_table_window_range): likewise
+struct SortRanges { int npart; DevWranges rg; int64_t* out; };
 
 // The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr) or
-// slide (slides != nullptr; at most one of the three) -> emit.  who: the entry point's name in messages.
+// slide (slides != nullptr) or range (ranges != nullptr; at most one of the four) -> emit.  who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
-                        const SortFrames* frames, const SortSlides* slides, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+                        const SortFrames* frames, const SortSlides* slides, const SortRanges* ranges, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     const std::string me(who);
     int64_t* out_rank = win ? win->out_rank : nullptr;
     const SortFrames* fr = frames && frames->out ? frames : nullptr;     // (no array for them: rows only, no aggregate pass)
     const SortSlides* sd = slides && slides->out ? slides : nullptr;     // (likewise)
+    const SortRanges* rr = ranges && ranges->out ? ranges : nullptr;     // (likewise)
     Scratch scratch(ctx);
     SortState s;
     if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
-    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd;
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd && !rr;
     const bool all_kept = !win || win->per_limit >= n;               // a rank is at most n: nothing to filter, the count is known
     const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
     const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
@@ -1171,7 +1376,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     const uint32_t un = (uint32_t)n;
     uint32_t *rank = nullptr, *sel = nullptr;
     const size_t agg_stride = round_up((size_t)n * 8) / 8;           // aggregate a's values start at a * agg_stride
-    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "one list of result arrays serves frames and slides");
+    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "one list of result arrays serves frames, slides and ranges");
     const uint64_t* agg_src[SDQH_WAGG_MAX_AGGS] = {nullptr, nullptr, nullptr, nullptr};      // where each aggregate's / slide's values lie once the passes ran
     int64_t* agg_out = nullptr; int agg_n = 0;                        // ... and the caller's array for them: agg_out[a * capacity + j]
     if (sd) {
@@ -1219,6 +1424,57 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
         LAUNCH(ctx, "k_wsl_fold", k_wsl_fold, fgrid, sl, rown, pend, un, (uint32_t)m, agg_stride, elem, pre, fin);
         agg_out = sd->out; agg_n = sl.n;
+        for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
+    }
+    if (rr) {
+        // block 3: [heads | tile carries | row numbers | partition ends | dense ranks | kept per tile | VALUE keys | GROUPS keys | raw
+        // elements, an array per FIRST / LAST range | fold trees, one per folded range | values | first heads per tile | next heads per tile]
+        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+        DevWranges rg = rr->rg;
+        const size_t na = (size_t)rg.n;
+        int nfold = 0, nraw = 0; bool groups = false;                   // folded ranges (SUM / MIN / MAX), FIRST / LAST ranges, any GROUPS range
+        for (size_t a = 0; a < na; ++a) {
+            DevWrange& d = rg.a[a];
+            d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
+            groups |= d.unit == SDQH_WRANGE_GROUPS;
+        }
+        uint64_t cap = SORT_TILE;                                      // the trees' leaf count: the power of two at or above n
+        while (cap < (uint64_t)n) cap <<= 1;
+        const size_t tstride = nfold ? (size_t)(2 * cap) : 0;          // a tree: nodes [1, cap), leaves [cap, 2 cap)
+        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
+        uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
+        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
+                heads = c.take<uint8_t>((size_t)n);
+                carry = c.take<WinCarry>(ntiles);
+                rown = c.take<uint32_t>((size_t)n);
+                pend = c.take<uint32_t>((size_t)n);
+                dense = c.take<uint32_t>(groups ? (size_t)n : 0);
+                tile_kept = c.take<uint32_t>(groups ? ntiles : 0);
+                vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
+                gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+                elem = c.take<uint64_t>(agg_stride * (size_t)nraw);
+                tree = c.take<uint64_t>(tstride * (size_t)nfold);
+                fin = c.take<uint64_t>(agg_stride * na);
+                tfirst = c.take<WaggHeads>(ntiles);
+                tnext = c.take<WaggHeads>(ntiles);
+            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+        if (rg.vcol < 0) vkey = nullptr;
+        if (!groups) { dense = nullptr; gkey = nullptr; }
+        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, rr->npart, nsort, s.perm, un, heads, carry, ntiles);
+        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+        LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
+        LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
+        if (groups) LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, ntiles);
+        LAUNCH(ctx, "k_wrg_stage", k_wrg_stage, tgrid, table->stage, rg, s.refs, s.perm, heads, tnext, rg.vcol >= 0 ? s.keys + (size_t)rg.vcol * s.key_stride : nullptr, dense, un,
+               agg_stride, tstride, cap, pend, vkey, gkey, elem, tree, ntiles);
+        if (nfold) {
+            LAUNCH(ctx, "k_wrg_tiles", k_wrg_tiles, tgrid, rg, un, tstride, cap, tree, ntiles);
+            if (cap > (uint64_t)SORT_TILE) LAUNCH(ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, ntiles);
+        }
+        const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+        LAUNCH(ctx, "k_wrg_fold", k_wrg_fold, fgrid, rg, rown, pend, vkey, gkey, un, (uint32_t)m, agg_stride, tstride, cap, elem, tree, fin);
+        agg_out = rr->out; agg_n = rg.n;
         for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
     }
     if (win || fr) {
@@ -1345,7 +1601,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
@@ -1353,7 +1609,7 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hit
     if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1365,7 +1621,7 @@ int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
     const SortWindow win = {npartition, kind, per_limit, out_rank};
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1392,7 +1648,7 @@ int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hi
         }
         d.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op == SDQH_WAGG_SUM && d.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1419,7 +1675,60 @@ int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
         }
         d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                            int nranges, const sdqh_window_range* ranges, int64_t limit, int64_t capacity,
+                            int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
+    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && ranges && nranges >= 1 && nranges <= SDQH_WRANGE_MAX_AGGS;
+    bool value = false;
+    for (int a = 0; ok && a < nranges; ++a) {
+        const sdqh_window_range& g = ranges[a];
+        ok = g.op >= SDQH_WAGG_SUM && g.op <= SDQH_WSLIDE_LAST && (g.unit == SDQH_WRANGE_VALUE || g.unit == SDQH_WRANGE_GROUPS) &&
+             !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+    }
+    bool vf64 = false;
+    if (ok && value) {                                                // exactly one ORDER BY term, and one with arithmetic
+        ok = nterms == npartition + 1 && in[npartition].ranks == nullptr;
+        if (ok) vf64 = in[npartition].kind == SDQH_SORT_VALUE || (in[npartition].kind == SDQH_SORT_PAYLOAD && in[npartition].is_f64);
+    }
+    for (int a = 0; ok && a < nranges; ++a) {
+        const sdqh_window_range& g = ranges[a];
+        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
+            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
+            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
+            ok = lo_ok && hi_ok && !(both && lo > hi);
+        } else ok = !(both && g.lo > g.hi);
+    }
+    if (int rc = sort_enter(ctx, table, "table_window_range", ok)) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_window_range", nterms, in, false, terms)) return rc;
+    SortRanges sr; std::memset(&sr, 0, sizeof(sr));
+    sr.npart = npartition; sr.out = out_aggs; sr.rg.n = nranges;
+    sr.rg.vcol = value ? npartition : -1; sr.rg.vdesc = value ? terms[npartition].sk.desc : 0; sr.rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    for (int a = 0; a < nranges; ++a) {
+        const sdqh_window_range& g = ranges[a];
+        DevWrange& d = sr.rg.a[a];
+        d.g.op = g.op; d.empty = (uint64_t)g.empty; d.unit = g.unit; d.flags = g.flags; d.lo = g.lo; d.hi = g.hi;
+        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
+            const std::string agg = "table_window_range: range " + std::to_string(a);
+            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
+            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
+            d.g.sk.kind = g.kind; d.g.sk.index = g.index;
+            d.g.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
+        }
+        d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_range", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, &sr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {
+    if (!ctx || !tile_rows || !narrow_max_width) return fail(ctx, SDQH_ERR_INVALID, "window_range_geometry: bad arguments");
+    *tile_rows = SORT_TILE; *narrow_max_width = 0;                    // no kernel walks a frame row by row: two searches and a tree query
+    return SDQH_OK;
 }
 
 int sdqh_window_slide_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {

@@ -23,8 +23,8 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import FRAMES, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, ResultSet, SlideRequest, TextRefs, WindowRequest, \
-    decode_text, slide_empty
+from .result import FRAMES, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, RangeRequest, ResultSet, SlideRequest, \
+    TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
 TUPLE_SHAPES = {
@@ -170,6 +170,9 @@ class Engine:
         # values over sliding frames (sliding: result.SlideRequest) likewise, where the library has the window slide extension
         # (abi.Context.table_window_slide) — route "window_slide", noted with the extra keys "per" and "slides"
         self.device_window_slide = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_SLIDE", "1") != "0"
+        # values over value and group frames (ranged: result.RangeRequest) likewise, where the library has the window range extension
+        # (abi.Context.table_window_range) — route "window_range", noted with the extra keys "per", "unit" and "ranges"
+        self.device_window_range = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_RANGE", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1685,6 +1688,25 @@ def _device_sort_spec(bt, key_fields, vnames, count_idx, order, eng=None, fields
     return spec
 
 
+def _order_column_decoded(bt, key_fields, name, fields_of=None):
+    """Does the result column `name` reach the host through a decoder or as text — a dictionary code, a row reference, the code units
+    of a substr — whatever the device orders it by?  The device's term may then be plain arithmetic (a sorted dictionary's code is
+    its rank, a substr part is a number of several digits), but the column has none: a value frame over it is the host's to refuse."""
+    if getattr(bt, "key_radix", None) is not None:
+        for pname, _, kind in bt.key_radix[0]:
+            if pname == name:
+                return kind[0] == "chars" or kind[1] is not None
+    if bt.key_parts is not None and name in bt.key_parts:
+        decs = getattr(bt, "key_part_decoders", None) or [None, None]
+        return decs[list(bt.key_parts).index(name)] is not None
+    for fname, src in key_fields:
+        if fname == name:
+            if src == "key":
+                return bt.key_decoder is not None
+            return bt.decoder_of(fields_of.get(name) if fields_of is not None else name, src) is not None
+    return False
+
+
 def _term_derived(t):
     """Is sort term t the 8-tuple (..., div, mod, add, text) of abi.Context.table_sorted_by, not a plain 4-tuple column?"""
     return len(t) > 4
@@ -1698,19 +1720,24 @@ def _term_text(t):
 class _FrameSpec(list):
     """The sort terms of a FrameRequest and, beside them, `measures`: per aggregate its measure as a plain sort column (None for a
     count) — or None as a whole when some measure is no underived numeric column of the table (text, packed, decoded).  A
-    SlideRequest's likewise; int_values: the columns the table keeps as integer-valued doubles (their results are converted back)."""
+    SlideRequest's and a RangeRequest's likewise; int_values: the columns the table keeps as integer-valued doubles (their results are converted back)."""
     measures = None
     int_values = ()
+    decoded_order = ()       # the ORDER BY columns of a RangeRequest that are text or decoded on the host (_order_column_decoded)
 
 
-def _order_spec(top, spec_of):
+def _order_spec(top, spec_of, decoded_of):
     """The device's columns for `top`: spec_of(order, eng_or_None) is _device_sort_spec over the table at hand.  A FrameRequest's
-    measures go through the same mapping with no engine to derive anything: whatever needs a decoder or a derivation is None there."""
+    measures go through the same mapping with no engine to derive anything: whatever needs a decoder or a derivation is None there.
+    decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
+    text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest)):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest)):
         return spec
     spec = _FrameSpec(spec)
-    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else top.slides)]
+    if isinstance(top, RangeRequest):
+        spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
+    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else (top.slides if isinstance(top, SlideRequest) else top.ranges))]
     cols = list(dict.fromkeys(col for col in measured if col is not None))
     plain = spec_of([(c, "asc") for c in cols], False)
     if plain is not None:
@@ -1721,13 +1748,16 @@ def _order_spec(top, spec_of):
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range") and _term_text(t) is not None]}
     if isinstance(top, FrameRequest):                        # "order" / "per" as for a window; the aggregates in the order of their columns
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["aggs"] = [list(a) for a in top.aggs]
     elif isinstance(top, SlideRequest):                      # likewise; lag / lead as the `first` they are, unbounded sides None
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["slides"] = [list(a) for a in top.slides]
+    elif isinstance(top, RangeRequest):                      # likewise, and the frames' unit
+        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+        note["unit"], note["ranges"] = top.unit, [list(a) for a in top.ranges]
     elif isinstance(top, WindowRequest):                     # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
@@ -1766,6 +1796,11 @@ def _finish_top(rs, ordered, top):
             if name in rs.columns:
                 raise KeyError("sliding: the result already has a column %r" % name)
         return ResultSet(rs.columns + [a[0] for a in top.slides], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
+    if isinstance(top, RangeRequest):                       # the device's ranges, a column each
+        for name in (a[0] for a in top.ranges):
+            if name in rs.columns:
+                raise KeyError("ranged: the result already has a column %r" % name)
+        return ResultSet(rs.columns + [a[0] for a in top.ranges], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
     if isinstance(top, WindowRequest) and top.name is not None:
         if top.name in rs.columns:
             raise KeyError("window: the result already has a column %r" % top.name)
@@ -1809,6 +1844,9 @@ def _order_route(eng, top, spec):
     "window_slide" abi.Context.table_window_slide: a SlideRequest of at most WSLIDE_MAX_AGGS slides whose measures are underived numeric
                  columns (the window slide extension and Engine.device_window_slide on; terms as for "window"); not with a default
                  beyond 2^53 for a column the table keeps as integer-valued doubles
+    "window_range" abi.Context.table_window_range: a RangeRequest under "window_slide"'s conditions (at most WRANGE_MAX_AGGS ranges; the
+                 window range extension and Engine.device_window_range on) whose offsets the device's order term can take
+                 (_range_offsets): a value frame needs an underived or arithmetically derived term, no text ranks
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1827,6 +1865,12 @@ def _order_route(eng, top, spec):
         fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
                                 for _, _, col, _, _, default in top.slides)
         return "window_slide" if fits and on("device_window_slide", "has_window_slide") and terms_ok else "host"
+    if isinstance(top, RangeRequest):
+        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.ranges) <= abi.WRANGE_MAX_AGGS and getattr(spec, "measures", None) is not None
+        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
+                                for _, _, col, _, _, default in top.ranges)
+        fits = fits and _range_offsets(top, spec) is not None
+        return "window_range" if fits and on("device_window_range", "has_window_range") and terms_ok else "host"
     if isinstance(top, WindowRequest):
         return "window" if 1 <= n <= abi.SORT_MAX_KEYS and on("device_window", "has_window") and terms_ok else "host"
     if derived:
@@ -1836,10 +1880,49 @@ def _order_route(eng, top, spec):
     return "sorted" if k >= 1 and n <= abi.SORT_MAX_KEYS and on("device_sort", "has_sort") else "host"
 
 
+def _range_offsets(top, spec):
+    """The offsets [(lo, hi)] of a RangeRequest as the device's order term takes them, or None where it cannot.  Groups: ints as they
+    are.  Value: the one order term must order by its own arithmetic (no text ranks); an integer term takes ints (an integral float
+    is one), a double term floats — a column the table keeps as integer-valued doubles takes integer offsets as doubles, and one
+    beyond 2^53 (no double holds it) stays on the host.  A column that is text or decoded on the host (spec.decoded_order) has no
+    arithmetic even where the device's term is a plain number, and an integer offset outside int64 does not fit the call's struct:
+    both stay on the host, which refuses the first and saturates the second."""
+    def fits(x):                                                 # (the struct's offsets are int64: a wider one would be cut, not saturated)
+        return x is None or isinstance(x, (float, np.floating)) or -(1 << 63) <= int(x) < (1 << 63)
+    if not all(fits(lo) and fits(hi) for _, _, _, lo, hi, _ in top.ranges):
+        return None
+    if top.unit == "groups":
+        return [(lo, hi) for _, _, _, lo, hi, _ in top.ranges]
+    if len(spec) != top.npartition + 1:
+        return None
+    t = spec[top.npartition]
+    if _term_text(t) is not None or top.order[0][0] in spec.decoded_order:
+        return None
+    is_f64 = t[0] == abi.SORT_VALUE or (t[0] == abi.SORT_PAYLOAD and bool(t[3]))
+    as_int = top.order[0][0] in spec.int_values                  # the host sees integers there
+
+    def one(x):
+        if x is None:
+            return True, None
+        integral = not isinstance(x, (float, np.floating)) or float(x) == int(x)
+        if is_f64 and not as_int:
+            return True, float(x)
+        if not integral or (is_f64 and abs(int(x)) > 1 << 53) or not -(1 << 63) <= int(x) < (1 << 63):
+            return False, None
+        return True, (float(int(x)) if is_f64 else int(x))
+    out = []
+    for _, _, _, lo, hi, _ in top.ranges:
+        (ok_lo, lo), (ok_hi, hi) = one(lo), one(hi)
+        if not (ok_lo and ok_hi) or (lo is not None and hi is not None and lo > hi):
+            return None
+        out.append((lo, hi))
+    return out
+
+
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
-    """The routes "sorted", "sorted_by", "window", "window_agg" and "window_slide" of _order_route: one waited-for call whose arrays are sized from the previous run
+    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide" and "window_range" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -1864,6 +1947,17 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
             slides.append((SLIDE_OPS.index(op), kind, index, is_f64, abi.SLIDE_UNBOUNDED_PRECEDING if lo is None else lo,
                            abi.SLIDE_UNBOUNDED_FOLLOWING if hi is None else hi, empty))
         got = eng.ctx.table_window_slide(table, min_hits, top.npartition, terms, slides, k, cap, want_hits=want_hits)
+    elif route == "window_range":
+        ranges = []
+        for (_, op, measure, _, _, default), col, (lo, hi) in zip(top.ranges, spec.measures, _range_offsets(top, spec)):
+            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
+            empty = 0
+            if col is not None:                                  # (the default's 64 bits as the device holds the column: see "window_slide")
+                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)
+                fill = slide_empty(default, as_f64 and measure not in spec.int_values, "ranged")
+                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
+        got = eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
     else:
         got = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap,
                                    want_hits=want_hits, want_rank=top.name is not None)
@@ -1918,7 +2012,8 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         out_key_fields, vnames, count_idx, key_is_record, val_is_record, nv = bt.agg
         entry_is_group = any(src == "key" for _, src in out_key_fields) or bt.shared_groups
         fields_of = bt.agg_fields
-        spec = _order_spec(top, lambda order, derive: _device_sort_spec(bt, out_key_fields, vnames, count_idx, order, eng if derive else None, fields_of)) \
+        spec = _order_spec(top, lambda order, derive: _device_sort_spec(bt, out_key_fields, vnames, count_idx, order, eng if derive else None, fields_of),
+                           lambda nm: _order_column_decoded(bt, out_key_fields, nm, fields_of)) \
             if top is not None and entry_is_group else None
         lazy = lazy_ok and bool(getattr(eng, "lazy_results", False)) and _lazy_rows_ok(bt, out_key_fields, fields_of, top)
         if isinstance(spec, _FrameSpec):
@@ -1958,6 +2053,8 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _) in zip(ordered.rank, top.aggs)]
         if isinstance(ordered, _Ranked) and isinstance(top, SlideRequest):      # likewise: whatever a slide takes of such a column is an integer
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.slides)]
+        if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
+            ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
         if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:    # several key fields in one mixed-radix integer
             from . import xplan
@@ -2048,8 +2145,9 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         d.ordered = sel is not None
         return d
     if isinstance(value, BuiltTable):
-        spec = _order_spec(top, lambda order, derive: _device_sort_spec(value, [(value.key_name, "key")] + [(f, src) for f, src in value.val_fields if src != "key"],
-                                                                        [], None, order, eng if derive else None)) if top is not None else None
+        built_fields = [(value.key_name, "key")] + [(f, src) for f, src in value.val_fields if src != "key"]
+        spec = _order_spec(top, lambda order, derive: _device_sort_spec(value, built_fields, [], None, order, eng if derive else None),
+                           lambda nm: _order_column_decoded(value, built_fields, nm)) if top is not None else None
         got = _fetch_ordered(eng, value.table, 0, hint_key, top, spec, False)
         if got is not None:
             keys, payload = got[0], got[1]
@@ -2092,7 +2190,7 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
@@ -2105,6 +2203,8 @@ def _finalize(eng, op, env, top=None):
             route["aggs"] = [list(a) for a in top.aggs]
         if isinstance(top, SlideRequest):
             route["slides"] = [list(a) for a in top.slides]
+        if isinstance(top, RangeRequest):
+            route["ranges"] = [list(a) for a in top.ranges]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)

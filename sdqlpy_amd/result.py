@@ -135,6 +135,11 @@ def check_window_columns(req, columns):
             raise KeyError("sliding: the result has no column %r" % col)
         if name in columns:
             raise KeyError("sliding: the result already has a column %r" % name)
+    for name, _, col, _, _, _ in getattr(req, "ranges", ()):
+        if col is not None and col not in columns:
+            raise KeyError("ranged: the result has no column %r" % col)
+        if name in columns:
+            raise KeyError("ranged: the result already has a column %r" % name)
 
 
 WAGG_OPS = ("sum", "count", "min", "max")                 # their positions are abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX
@@ -263,6 +268,91 @@ def slide_request(columns, by, order, aggs, k=WINDOW_ALL):
     if columns is not None:
         check_window_columns(req, columns)
     return req
+
+
+RANGE_UNITS = ("value", "groups")       # their positions are abi.WRANGE_VALUE / WRANGE_GROUPS
+
+
+class RangeRequest(WindowRequest):
+    """Values over value and group window frames, travelling where a SlideRequest travels (every row is kept): [0] = the limit on the
+    whole result, [1] = the PARTITION BY terms followed by the ORDER BY terms, npartition, unit (a name of RANGE_UNITS) and ranges =
+    [(name of the new column, op: a name of SLIDE_OPS, measure column or None for a count, lo, hi: the frame's offsets along the order
+    — of the ORDER BY value (unit "value": ints or floats) or in tie runs (unit "groups": ints), negative = preceding, None = unbounded
+    —, default: what an empty frame gives, None = 0 for an int64 measure and NaN for a float64 one)] in the order the columns are
+    appended."""
+
+    def __new__(cls, k, terms, npartition, unit, ranges):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.unit = str(unit)
+        self.ranges = [(str(n), str(op), None if col is None else str(col), lo, hi, default) for n, op, col, lo, hi, default in ranges]
+        if self.unit not in RANGE_UNITS or not self.ranges or any(op not in SLIDE_OPS or (col is None and op != "count") or (lo is not None and hi is not None and lo > hi)
+                                                                   for _, op, col, lo, hi, _ in self.ranges):
+            raise ValueError("ranged: bad aggregate")
+        if self.unit == "value" and len(terms) != npartition + 1:
+            raise ValueError("ranged: a value frame is ordered by exactly one column")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
+        names = names or {}
+        return RangeRequest(self[0], terms, self.npartition, self.unit, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.ranges])
+
+
+def _range_offset(x, unit):
+    """A frame offset of `ranged`: an int, or — unit "value" only — a finite float."""
+    if not isinstance(x, bool) and isinstance(x, (int, np.integer)):
+        return int(x)
+    if unit == "value" and isinstance(x, (float, np.floating)) and np.isfinite(x):
+        return float(x)
+    raise ValueError("ranged: a bound is %s, not %r" % ("an integer or a finite float" if unit == "value" else "an integer", x))
+
+
+def range_request(columns, by, order, aggs, unit="value", k=WINDOW_ALL):
+    """The checked RangeRequest of `ranged`: by / order as window_request takes them; unit a name of RANGE_UNITS; aggs = {new column:
+    (op, measure column or None, lo, hi[, default])} with op a name of SLIDE_OPS and lo / hi offsets along the order (negative =
+    preceding, None = unbounded): ints, or floats as well for unit "value".  columns: the result's column names when they are known
+    (None: checked when the result is).  KeyError for a column the result lacks or a new column it has already, ValueError for
+    everything else (a default that does not fit its column, or an order column without arithmetic, is found when the column is
+    known)."""
+    req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    if unit not in RANGE_UNITS:
+        raise ValueError("ranged: unit is one of %s, not %r" % (", ".join(RANGE_UNITS), unit))
+    if unit == "value" and len(req[1]) != req.npartition + 1:
+        raise ValueError("ranged: a value frame is ordered by exactly one column, not %d" % (len(req[1]) - req.npartition))
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("ranged: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default])}")
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5):
+            raise ValueError("ranged: an aggregate is name: (op, measure, lo, hi[, default])")
+        op, col = spec[0], spec[1]
+        if op not in SLIDE_OPS:
+            raise ValueError("ranged: op is one of %s, not %r" % (", ".join(SLIDE_OPS), op))
+        lo = None if spec[2] is None else _range_offset(spec[2], unit)
+        hi = None if spec[3] is None else _range_offset(spec[3], unit)
+        default = spec[4] if len(spec) == 5 else None
+        if lo is not None and hi is not None and lo > hi:
+            raise ValueError("ranged: the frame (%r, %r) ends before it starts" % (lo, hi))
+        if col is None and op != "count":
+            raise ValueError("ranged: %s needs a measure column" % op)
+        if col is not None and not isinstance(col, str):
+            raise ValueError("ranged: a measure is a column name")
+        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
+            raise ValueError("ranged: a default is a number, not %r" % (default,))
+        out.append((name, op, col, lo, hi, default))
+    req = RangeRequest(req[0], req[1], req.npartition, unit, out)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
+
+
+def _range_int_offset(x):
+    """A frame offset over an integer order column as an int: an int as it is, an integral float converted; ValueError otherwise."""
+    if x is None or isinstance(x, (int, np.integer)):
+        return x if x is None else int(x)
+    if float(x) != int(x):
+        raise ValueError("ranged: the offset %r over an integer column is not an integer" % (x,))
+    return int(x)
 
 
 def slide_empty(default, is_f64, what="sliding"):
@@ -532,6 +622,92 @@ class ResultSet:
         cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
         return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:k] for _, c in new])
 
+    def ranged_by(self, req):
+        """Every row in a RangeRequest's order (the first req[0] of them) with its columns appended: what sdqh_table_window_range does on
+        the device (include/sdqh_sort_range.h), on the host.  Per sorted position one ordered key — the order_image of the one ORDER BY
+        column (unit "value"), the tie run's number inside the partition (unit "groups") — and per row two np.searchsorted over its
+        partition's keys for the frame's ends, against bounds made without a wrapping add (integers: saturating; doubles: the one IEEE
+        add, -0.0 / +0.0 as one value, NaN rows their own tie run).  COUNT is arithmetic, FIRST / LAST gather, an integer SUM is a
+        difference of wrapping prefix sums (exact mod 2^64); a double SUM and MIN / MAX (on the images of sdqh_extrema.h) fold exactly
+        the frame's rows through a binary fold tree over the sorted positions, lower positions on the left: nothing is subtracted."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, part_head, tie_head = self._window_heads(req.by, req.order)
+        n = self._n
+        pos = np.arange(n, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(part_head, pos, 0)) if n else pos
+        heads = np.nonzero(part_head)[0]
+        stops = np.append(heads[1:], n)
+        end = (stops - 1)[np.cumsum(part_head) - 1] if n else pos
+        top = np.uint64(1) << np.uint64(63)
+        desc, is_fv = False, False
+        if req.unit == "groups":
+            g = np.cumsum(tie_head).astype(np.int64)
+            key = (g - g[start] + 1 if n else g).view(np.uint64) ^ top
+            v = key
+        else:
+            (name, direction), = req.order
+            col = self.column(name)
+            if col.dtype.kind not in "iubf":
+                raise ValueError("ranged: a value frame over column %r: the order column is not numeric" % name)
+            desc, is_fv = direction == "desc", col.dtype.kind == "f"
+            v = np.ascontiguousarray(col[idx], np.float64 if is_fv else np.int64)
+            key = order_image(v, desc)
+        new = []
+        for name, op, col, lo, hi, default in req.ranges:
+            x = None if op == "count" else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("ranged: %s of column %r: the measure is not numeric" % (op, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            fill = None if op == "count" else slide_empty(default, is_f, "ranged")
+            # per side: the key searched for, and where no search is needed whether every row of the partition lies inside (all) or none
+            if is_fv:
+                sides = _range_f64_bounds(v, key, None if lo is None else float(lo), None if hi is None else float(hi), desc)
+            else:
+                vj = (key ^ top).view(np.int64) if req.unit == "groups" else v
+                sides = (_range_int_bound(vj, _range_int_offset(lo), desc, True), _range_int_bound(vj, _range_int_offset(hi), desc, False))
+            (kl, all_l, none_l), (kr, all_r, none_r) = sides
+            left, right = np.empty(n, np.int64), np.empty(n, np.int64)
+            for a, b in zip(heads, stops):                              # the ends of every row's frame inside its partition [a, b)
+                left[a:b] = a + np.searchsorted(key[a:b], kl[a:b], "left")
+                right[a:b] = a + np.searchsorted(key[a:b], kr[a:b], "right") - 1
+            left, right = np.where(all_l, start, left), np.where(all_r, end, right)
+            empty = none_l | none_r | (left > right)
+            a, b = np.where(empty, pos, left), np.where(empty, pos, right)       # (an empty frame reads its own row, then takes the default)
+            if op == "count":
+                new.append((name, np.where(empty, 0, right - left + 1).astype(np.int64)))
+                continue
+            x = np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+            if op in ("first", "last"):
+                val = x[a] if op == "first" else x[b]
+            elif op == "sum" and not is_f:
+                c = np.concatenate((np.zeros(1, np.uint64), np.cumsum(x.view(np.uint64), dtype=np.uint64)))
+                val = (c[b + 1] - c[a]).view(np.int64)
+            elif op == "sum":
+                val = _tree_fold(x, np.add, np.float64(-0.0), a, b)
+            else:                                                        # unsigned maximum of the images, reversed for MIN, NaN = 0
+                e = order_image(x, op == "min")
+                e = np.where(np.isnan(x), np.uint64(0), e) if is_f else e
+                val = _tree_fold(e, np.maximum, np.uint64(0), a, b)
+                u = ~val if op == "min" else val
+                if is_f:
+                    val = np.where(val == 0, np.uint64(0x7FF8000000000000), np.where(u >> np.uint64(63) != 0, u ^ top, ~u)).view(np.float64)
+                else:
+                    val = (u ^ top).view(np.int64)
+            bits = np.where(empty, np.array(fill).view(np.uint64), np.ascontiguousarray(val).view(np.uint64))      # (by bits: a NaN default keeps its payload)
+            new.append((name, bits.view(np.float64 if is_f else np.int64)))
+        k = max(0, min(int(req[0]), n))
+        cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:k] for _, c in new])
+
+    def ranged(self, by, order, aggs, unit="value"):
+        """Every row, ordered by `by` then `order`, plus one column per aggregate over a value or group frame inside the row's group of
+        `by`: aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS.  unit "value": the rows whose
+        (one, numeric) order column lies within [lo, hi] of this row's, along the order (RANGE BETWEEN); unit "groups": the rows whose
+        tie run lies within [lo, hi] runs of this row's (GROUPS BETWEEN).  None: unbounded.  An empty frame gives `default` (0 / NaN),
+        a count 0."""
+        return self.ranged_by(range_request(self.columns, by, order, aggs, unit))
+
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:
         aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS, the frame rows [row + lo, row + hi] of
@@ -550,6 +726,8 @@ class ResultSet:
             return self.framed(req)
         if isinstance(req, SlideRequest):
             return self.slid(req)
+        if isinstance(req, RangeRequest):
+            return self.ranged_by(req)
         self._wait()
         check_window_columns(req, self.columns)
         idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])
@@ -640,6 +818,7 @@ class DictResult:
         return str(self.to_dict())
 
 
+INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
 SLIDE_WALK_MAX = 32          # frames at most this wide are folded row by row on the host
 
 
@@ -671,6 +850,74 @@ def _slide_fold(e, fold, a, b, start, end, w):
     ra, rb = a - start, b - start
     two = ra // w != rb // w
     return np.where(two, fold(suf[a], pre[b]), np.where(ra % w == 0, pre[b], suf[a]))
+
+
+def _range_int_bound(v, off, desc, lo_side):
+    """One side of an integer value / group frame for every row: (the key to search for, all: every row of the partition lies inside
+    this bound, none: no row does).  The target v + d * off is made in Python integers, once per distinct value: nothing wraps, and
+    beyond int64 it is a bound that no value reaches."""
+    n = len(v)
+    if off is None:
+        return np.zeros(n, np.uint64), np.ones(n, bool), np.zeros(n, bool)
+    u, inv = np.unique(v, return_inverse=True)
+    inv = inv.reshape(-1)
+    t = u.astype(object) + (-int(off) if desc else int(off))
+    over, under = (t > INT64_MAX).astype(bool)[inv], (t < INT64_MIN).astype(bool)[inv]
+    key = order_image(np.clip(t, INT64_MIN, INT64_MAX).astype(np.int64)[inv], desc)
+    out = over | under
+    every = (over != desc) != lo_side
+    return key, out & every, out & ~every
+
+
+def _range_f64_bounds(v, key, lo, hi, desc):
+    """Both sides of a double value frame for every row, as _range_int_bound gives one: the bounds a = v + d * lo, b = v + d * hi (one
+    IEEE addition each) as keys of the total order — the lower end of the IEEE comparison takes -0.0 for a zero, the upper end +0.0 —
+    and a NaN row its own key on every bounded side."""
+    n = len(v)
+    nan = np.isnan(v)
+    with np.errstate(over="ignore", invalid="ignore"):
+        fa = None if lo is None else v + (-lo if desc else lo)
+        fb = None if hi is None else v + (-hi if desc else hi)
+    x, y = (fb, fa) if desc else (fa, fb)                            # the lower and the upper value bound
+    if x is not None and y is not None:
+        x, y = np.minimum(x, y), np.maximum(x, y)
+
+    def side(bound, lower):
+        if bound is None:
+            return np.zeros(n, np.uint64), np.ones(n, bool), np.zeros(n, bool)
+        z = np.where(bound == 0.0, -0.0 if lower else 0.0, np.where(nan, 0.0, bound))
+        return np.where(nan, key, order_image(z, desc)), np.zeros(n, bool), np.zeros(n, bool)
+    return (side(y, False), side(x, True)) if desc else (side(x, True), side(y, False))
+
+
+def _tree_fold(e, fold, identity, a, b):
+    """fold over e[a[j] .. b[j]] for every j (a <= b) through a bottom-up binary fold tree over the positions, as the device's range
+    frames are folded: node k = node 2k then node 2k + 1, the leaves padded to a power of two with the identity; the iterative query
+    keeps a left and a right accumulator and reads at most 2 log2(width) + 2 nodes, the lower positions on the left."""
+    n = len(e)
+    if n == 0:
+        return e.copy()
+    cap = 1
+    while cap < n:
+        cap *= 2
+    t = np.full(2 * cap, identity, e.dtype)
+    t[cap:cap + n] = e
+    width = cap
+    while width > 1:
+        half = width // 2
+        t[half:width] = fold(t[width:2 * width:2], t[width + 1:2 * width:2])
+        width = half
+    p, q = a.astype(np.int64) + cap, b.astype(np.int64) + 1 + cap
+    left, right = np.full(len(a), identity, e.dtype), np.full(len(a), identity, e.dtype)
+    while np.any(p < q):
+        m = (p < q) & ((p & 1) == 1)
+        left = np.where(m, fold(left, t[np.where(m, p, 1)]), left)
+        p = p + m
+        m = (p < q) & ((q & 1) == 1)
+        q = q - m
+        right = np.where(m, fold(t[np.where(m, q, 1)], right), right)
+        p, q = p >> 1, q >> 1
+    return fold(left, right)
 
 
 class Pending:

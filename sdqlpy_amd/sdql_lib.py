@@ -440,12 +440,30 @@ def sdql_compile(in_type):
             req = slide_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs)     # checked before anything is launched
             return lambda *args: run(args, req)
 
+        def ranged(by, order, aggs, unit="value"):
+            """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a VALUE or GROUP frame inside the
+            row's group of `by`: aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in "sum" / "count" / "min" /
+            "max" / "first" / "last".  unit "value" (RANGE BETWEEN): the rows whose order column — exactly one, numeric — lies within
+            [lo, hi] of this row's, along the order; unit "groups" (GROUPS BETWEEN): the rows whose tie run lies within [lo, hi] runs
+            of this row's, any order.  Negative = preceding, None = unbounded; ints, or floats as well for "value", e.g.
+            ``q3.ranged(["o_orderdate"], [("revenue", "desc")], {"near": ("count", None, -1000.0, 1000.0)})(li, cu, ord)``.  An empty
+            frame gives `default` (0 for an int64 measure, NaN for a float64 one), a count 0.  Names, ops, the unit and bounds are
+            checked here, before anything is launched; what depends on a column's dtype (a default that does not fit, an order column
+            without arithmetic) can only be told once the query has run: that ValueError comes from the call."""
+            from . import engine, frontend
+            from .result import range_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = range_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, unit)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
         wrapper.numbered = numbered
         wrapper.over = over
         wrapper.sliding = sliding
+        wrapper.ranged = ranged
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
