@@ -12,7 +12,8 @@
  * sdqh_table_window_agg, declared in sdqh_sort_frames.h.  What differs is the frame.
  *
  * Not here: AVG (divide a SUM by a COUNT of the same frame), text measures, and the multi-GPU runner.  Value-based frames (RANGE BETWEEN x
- * PRECEDING ...) and GROUPS frames are the sixth extension's: sdqh_sort_range.h. */
+ * PRECEDING ...) and GROUPS frames are the sixth extension's: sdqh_sort_range.h.  NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and the
+ * percentiles are the seventh's: sdqh_sort_quantile.h. */
 #ifndef SDQH_SORT_SLIDE_H
 #define SDQH_SORT_SLIDE_H
 

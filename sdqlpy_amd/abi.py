@@ -49,6 +49,11 @@ WINDOW_RANGE_EXPORTS = ["sdqh_table_window_range", "sdqh_window_range_geometry"]
 WRANGE_VALUE, WRANGE_GROUPS = 0, 1
 WRANGE_LO_UNBOUNDED, WRANGE_HI_UNBOUNDED = 1, 2
 WRANGE_MAX_AGGS = 4
+# ... and its seventh (include/sdqh_sort_quantile.h, Library.has_window_quantile): the functions of the partition's size — NTILE,
+# PERCENT_RANK, CUME_DIST, NTH from either end, PERCENTILE_DISC / _CONT — for every row or the first per_limit rows of every partition
+WINDOW_QUANTILE_EXPORTS = ["sdqh_table_window_quantile", "sdqh_window_quantile_geometry"]
+WQ_NTILE, WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_NTH, WQ_PERCENTILE_DISC, WQ_PERCENTILE_CONT = 0, 1, 2, 3, 4, 5
+WQUANT_MAX_COLS = 4
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -139,6 +144,12 @@ class WindowRange(C.Structure):
     (int64, or the bits of doubles for a VALUE frame over a double term) and the 64 bits of an empty frame."""
     _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32),
                 ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
+
+
+class WindowQuantile(C.Structure):
+    """sdqh_window_quantile: a function, its measure (as a SortKey names a column; NTH and the percentiles), its integer argument (NTILE's
+    b, NTH's k), its p (the percentiles) and the 64 bits NTH gives beyond the partition."""
+    _fields_ = [("fn", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("arg", C.c_int64), ("p", C.c_double), ("empty", C.c_int64)]
 
 
 SRC_COLUMN, SRC_LOOKUP, SRC_LOOKUP_YEAR = 0, 1, 2
@@ -1366,6 +1377,40 @@ class Context:
         self._check(self.lib.sdqh_window_range_geometry(self.handle, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def _need_window_quantile(self, what):
+        if not self.library.has_window_quantile:
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window quantile extension (include/sdqh_sort_quantile.h)" % (what, self.library.path))
+
+    def table_window_quantile(self, table, min_hits, npartition, terms, cols, per_limit, limit, capacity, want_hits=True, want_cols=True):
+        """Functions of the partition's size beside the ordered entries: terms and npartition as table_window takes them; cols: [(fn,
+        kind, index, is_f64, arg, p, empty)] — fn one of WQ_NTILE (arg = b >= 1) / WQ_PERCENT_RANK / WQ_CUME_DIST / WQ_NTH (arg = k != 0,
+        empty: the 64 bits beyond the partition, as an int64) / WQ_PERCENTILE_DISC / WQ_PERCENTILE_CONT (p in [0, 1]), the measure as a
+        sort column is named (the first three ignore it).  Only the rows whose row number inside their partition is <= per_limit are
+        returned (SORT_ALL: every row), the first min(limit, kept) in sorted order.  Returns (keys, payload, values, hits, cols) — cols
+        one array per column: int64 for NTILE, float64 for PERCENT_RANK / CUME_DIST / PERCENTILE_CONT, the measure's dtype for NTH /
+        PERCENTILE_DISC; None without want_cols."""
+        self._need_window_quantile("table_window_quantile")
+        arr = (WindowQuantile * max(1, len(cols)))()
+        for i, (fn, kind, index, is_f64, arg, p, empty) in enumerate(cols):
+            if not INT64_MIN <= int(arg) <= INT64_MAX:           # (ctypes would cut it to 64 bits without a word)
+                raise SdqhError(ERR_INVALID, "table_window_quantile: the argument %d does not fit int64" % int(arg))
+            arr[i].fn, arr[i].kind, arr[i].index, arr[i].is_f64 = int(fn), int(kind), int(index), 1 if is_f64 else 0
+            arr[i].arg, arr[i].p, arr[i].empty = int(arg), float(p), int(empty)
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(cols)), arr, C.c_int64(per_limit), C.c_int64(limit))
+        got = self._sorted_call("table_window_quantile", table, lead, limit, capacity, want_hits, bool(want_cols), naggs=max(1, len(cols)))
+        if got[4] is None:
+            return got
+        as_f64 = [fn in (WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_PERCENTILE_CONT) or (fn in (WQ_NTH, WQ_PERCENTILE_DISC) and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))))
+                  for fn, kind, _, is_f64, _, _, _ in cols]
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def window_quantile_geometry(self):
+        """Sorted positions per tile of sdqh_table_window_quantile's passes: what the tests size their cases from."""
+        self._need_window_quantile("window_quantile_geometry")
+        a = C.c_int64()
+        self._check(self.lib.sdqh_window_quantile_geometry(self.handle, C.byref(a)))
+        return a.value
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1640,6 +1685,11 @@ class Library:
             L.sdqh_table_window_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_range_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.has_window_quantile = self.has_window_slide and all(hasattr(L, s) for s in WINDOW_QUANTILE_EXPORTS)    # ... and functions of the partition's size (include/sdqh_sort_quantile.h)
+        if self.has_window_quantile:
+            L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_quantile_geometry.argtypes = [C.c_void_p, C.c_void_p]
         self.has_extrema = all(hasattr(L, s) for s in EXTREMA_EXPORTS)    # the extrema extension (include/sdqh_extrema.h)
         if self.has_extrema:
             L.sdqh_table_extrema_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]

@@ -24,7 +24,8 @@
 //
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
 // (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h), sdqh_table_window_slide
-// (include/sdqh_sort_slide.h) and sdqh_table_window_range (include/sdqh_sort_range.h): select -> order -> rank, aggregate, slide or range -> emit
+// (include/sdqh_sort_slide.h), sdqh_table_window_range (include/sdqh_sort_range.h) and sdqh_table_window_quantile
+// (include/sdqh_sort_quantile.h): select -> order -> rank, aggregate, slide, range or quantiles -> emit
 // (ordered_impl).  What differs between them is
 // data, not code:
 //
@@ -86,6 +87,15 @@
 //   k_wrg_tiles / k_wrg_upper
 //                     the fold trees bottom-up: nine levels inside the wave that owns a tile, the rest in one workgroup per range
 //   k_wrg_fold        per row two binary searches of its partition for the frame's ends, then the tree's iterative query — see the section
+//   QUANTILES         in their place (SortQuantiles).  sdqh_table_window_quantile (include/sdqh_sort_quantile.h) takes NTILE / PERCENT_RANK /
+//                     CUME_DIST / NTH / PERCENTILE_DISC / PERCENTILE_CONT — everything that needs the partition's size — and keeps the
+//                     rows whose row number is <= per_limit (k_win_rank / k_sort_scan / k_win_place, as a window does).  Behind k_win_heads,
+//                     k_win_scan, k_wsl_rows and k_wagg_next:
+//
+//   k_wq_ties         only with a CUME_DIST column: the first tie head of every tile, for k_wagg_next to scan
+//   k_win_rank        only with a PERCENT_RANK column: the RANK of every position = its tie run's first offset + 1 (every row kept)
+//   k_wq_stage        backwards: per position its partition's and its tie run's last position, every distinct measure's element once
+//   k_wq_value        per returned row the indices, one or two gathers and the arithmetic — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -100,6 +110,7 @@
 #define SDQH_DECLS_ONLY 1            // argument structs and device helpers of the kernel header, not a second copy of its kernels
 #include "sdqh_host.hpp"
 #include "sdqh_sort_range.h"
+#include "sdqh_sort_quantile.h"
 
 using namespace sdqh_host;
 
@@ -1147,6 +1158,111 @@ __global__ __launch_bounds__(TPB) void k_wrg_fold(DevWranges rg, const uint32_t*
     }
 }
 
+// ---- functions of the partition's size (sdqh_table_window_quantile) --------------------------------------------------------------
+// Sorted position j lies in a partition [s, e] of m = e - s + 1 rows at offset i = j - s, inside a tie run [s + f, s + l].  Every
+// column is arithmetic on (i, m, f, l) and at most two gathers at positions that arithmetic names: NTILE from i and m; PERCENT_RANK
+// f / (m - 1); CUME_DIST (l + 1) / m; NTH, PERCENTILE_DISC and PERCENTILE_CONT read the measure at s + an offset computed from k or
+// p and m.  i is k_wsl_rows' row number, e and l come from one backwards pass over the tile (k_wq_stage), f from k_win_rank's RANK
+// arm; nothing walks a partition, the work per row does not depend on m.  Columns that name the same measure share one element
+// array (a SLOT), so a median and a p90 of one column gather it once.
+struct DevWquant { int32_t fn, slot, is_f64, _pad; int64_t arg; double p; uint64_t empty; };     // slot: the element array of the measure (-1: none)
+struct DevWquants { DevWquant a[SDQH_WQUANT_MAX_COLS]; DevSortKey slot[SDQH_WQUANT_MAX_COLS]; int32_t n, nslots; };      // slot[k]: measure k (desc unused)
+
+// 1. only with a CUME_DIST column: the first tie head of every tile into tfirst[w].tie, beside the first partition head k_wsl_rows
+// left there (it sets .tie to n: none) — what k_wagg_next then scans into the next tie head of the later tiles
+__global__ __launch_bounds__(TPB) void k_wq_ties(const uint8_t* __restrict__ heads, uint32_t n, WaggHeads* __restrict__ tfirst, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    uint32_t tie = n;
+    for (uint64_t b = r0; b < r1 && tie == n; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        const uint64_t mt = __ballot(r < r1 && (heads[r] & WIN_TIE));
+        if (mt) tie = (uint32_t)b + (uint32_t)__builtin_ctzll(mt);
+    }
+    if (lane_id() == 0) tfirst[w].tie = tie;
+}
+// 2. a tile walked backwards (k_wsl_blocks' shape): per position the last position of its partition (pend), of its tie run (tend;
+// nullptr: no column asks) — the next head read off the ballots above the lane, else off the batches and tiles behind — and the 64
+// bits of every measure (elem[slot * stride + r], read through perm -> refs -> stage exactly once; no slot: nothing is gathered)
+__global__ __launch_bounds__(TPB) void k_wq_stage(DevStage st, DevWquants q, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ heads,
+                                                 const WaggHeads* __restrict__ tnext, uint32_t n, size_t stride, uint32_t* __restrict__ pend, uint32_t* __restrict__ tend,
+                                                 uint64_t* __restrict__ elem, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    WaggHeads next = tnext[w];
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const uint64_t pg = h.mp & ~le, tg = h.mt & ~le;
+        const uint32_t pe = (pg ? (uint32_t)b + (uint32_t)__builtin_ctzll(pg) : next.part) - 1u;
+        const uint32_t te = (tg ? (uint32_t)b + (uint32_t)__builtin_ctzll(tg) : next.tie) - 1u;
+        if (live) {
+            pend[r] = pe;
+            if (tend) tend[r] = te;
+            if (q.nslots > 0) {
+                const uint32_t g = perm ? perm[r] : (uint32_t)r;
+                const bool ok = g < n;                                   // (a permutation of [0, n): always)
+                const int64_t idx = ok ? (int64_t)refs[g] : 0;
+                const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u;
+#pragma unroll
+                for (int k = 0; k < SDQH_WQUANT_MAX_COLS; ++k) if (k < q.nslots) elem[(size_t)k * stride + r] = ok ? (uint64_t)sort_raw(q.slot[k], st, idx, hits) : 0ull;
+            }
+        }
+        if (h.mp) next.part = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (h.mt) next.tie = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mt);
+        if (b == r0) break;
+    }
+}
+// the measure at a position as a double: its bits, or an int64 by one round-to-nearest conversion
+__device__ __forceinline__ double wq_f64(uint64_t bits, bool is_f64) { return is_f64 ? __longlong_as_double((long long)bits) : (double)(int64_t)bits; }
+// 3. the value of every column at the first m returned rows: fin[c * stride + j], row j = sorted position sel[j] (nullptr: j itself).
+// rown: k_wsl_rows' (i); pend / tend: k_wq_stage's (e, s + l); frank: k_win_rank's RANK (f + 1; nullptr: no PERCENT_RANK column)
+__global__ __launch_bounds__(TPB) void k_wq_value(DevWquants q, const uint32_t* __restrict__ sel, const uint32_t* __restrict__ rown, const uint32_t* __restrict__ pend,
+                                                 const uint32_t* __restrict__ tend, const uint32_t* __restrict__ frank, uint32_t n, uint32_t m, size_t stride,
+                                                 const uint64_t* __restrict__ elem, uint64_t* __restrict__ fin) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t pos = sel ? sel[j] : (uint32_t)j;
+        if (pos >= n) continue;                                          // (kept positions are positions: never taken)
+        const uint32_t rn = rown[pos], e = pend[pos];
+        if (rn > pos || e < pos || e >= n) continue;                     // (s <= pos <= e < n: never taken)
+        const uint64_t s = (uint64_t)(pos - rn), i = rn, size = (uint64_t)e - s + 1ull;      // the partition's start, the row's offset, m
+#pragma unroll
+        for (int c = 0; c < SDQH_WQUANT_MAX_COLS; ++c) if (c < q.n) {
+            const DevWquant& d = q.a[c];
+            const uint64_t* __restrict__ x = elem + (size_t)(d.slot < 0 ? 0 : d.slot) * stride;
+            uint64_t v = 0ull;
+            if (d.fn == SDQH_WQ_NTILE) {
+                const uint64_t b = (uint64_t)d.arg, qq = size / b, r = size % b, big = r * (qq + 1ull);      // (b > m: qq = 0, big = m > i; else big < 2 m)
+                v = i < big ? i / (qq + 1ull) + 1ull : r + (i - big) / qq + 1ull;
+            } else if (d.fn == SDQH_WQ_PERCENT_RANK) {
+                const uint32_t f = frank[pos] - 1u;
+                v = (uint64_t)__double_as_longlong(size == 1ull ? 0.0 : (double)f / (double)(size - 1ull));
+            } else if (d.fn == SDQH_WQ_CUME_DIST) {
+                const uint64_t l1 = (uint64_t)tend[pos] - s + 1ull;     // l + 1: the rows up to the end of the tie run
+                v = (uint64_t)__double_as_longlong((double)l1 / (double)size);
+            } else if (d.fn == SDQH_WQ_NTH) {
+                const uint64_t ak = d.arg < 0 ? 0ull - (uint64_t)d.arg : (uint64_t)d.arg;      // |k|, INT64_MIN included
+                v = ak > size ? d.empty : x[d.arg > 0 ? s + ak - 1ull : (uint64_t)e + 1ull - ak];
+            } else if (d.fn == SDQH_WQ_PERCENTILE_DISC) {
+                const double up = ceil(d.p * (double)size);             // (0 <= p <= 1: 0 <= up <= m)
+                const uint64_t at = up >= 1.0 ? min((uint64_t)up - 1ull, size - 1ull) : 0ull;
+                v = x[s + at];
+            } else {
+                const double t = d.p * (double)(size - 1ull), lo = floor(t), hi = ceil(t);      // (0 <= lo <= hi <= m - 1)
+                const uint64_t al = min((uint64_t)lo, size - 1ull), ah = min((uint64_t)hi, size - 1ull);
+                const double a = wq_f64(x[s + al], d.is_f64 != 0), b = wq_f64(x[s + ah], d.is_f64 != 0);
+                // four IEEE operations in this order: the unit is built with -ffp-contract=off, so (b - a) * (t - lo) is not fused into the sum
+                const double y = al == ah ? a : a + (b - a) * (t - lo);
+                v = (uint64_t)__double_as_longlong(y);
+            }
+            fin[(size_t)c * stride + j] = v;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1347,22 +1463,27 @@ struct SortFrames { int npart; DevWaggs aggs; int64_t* out; };
 struct SortSlides { int npart; DevWslides sl; int64_t lo[SDQH_WSLIDE_MAX_AGGS], hi[SDQH_WSLIDE_MAX_AGGS]; int64_t* out; };
 // ... or values over value and group frames (sdqh_table_window_range): likewise
 struct SortRanges { int npart; DevWranges rg; int64_t* out; };
+// ... or functions of the partition's size (sdqh_table_window_quantile): out[c * capacity + i] beside the i-th returned row, and —
+// alone among the four — a window's per_limit on the row number: out == nullptr still filters
+struct SortQuantiles { int npart; DevWquants q; int64_t per_limit; int64_t* out; };
 
 // The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr) or
-// slide (slides != nullptr) or range (ranges != nullptr; at most one of the four) -> emit.  who: the entry point's name in messages.
+// slide (slides != nullptr) or range (ranges != nullptr) or quantiles (quants != nullptr; at most one of the five) -> emit.  who: the
+// entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
-                        const SortFrames* frames, const SortSlides* slides, const SortRanges* ranges, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+                        const SortFrames* frames, const SortSlides* slides, const SortRanges* ranges, const SortQuantiles* quants, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     const std::string me(who);
     int64_t* out_rank = win ? win->out_rank : nullptr;
     const SortFrames* fr = frames && frames->out ? frames : nullptr;     // (no array for them: rows only, no aggregate pass)
     const SortSlides* sd = slides && slides->out ? slides : nullptr;     // (likewise)
     const SortRanges* rr = ranges && ranges->out ? ranges : nullptr;     // (likewise)
+    const bool qv = quants && quants->out;                            // (likewise; the rows may still be filtered)
     Scratch scratch(ctx);
     SortState s;
     if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
-    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd && !rr;
-    const bool all_kept = !win || win->per_limit >= n;               // a rank is at most n: nothing to filter, the count is known
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd && !rr && !qv;
+    const bool all_kept = (!win || win->per_limit >= n) && (!quants || quants->per_limit >= n);      // a rank is at most n: nothing to filter, the count is known
     const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
     const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
     // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering window knows its count
@@ -1371,12 +1492,13 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     if (n == 0) return done(0);                                       // nothing selected (limit >= 1: m = 0 means n = 0)
     if (all_kept && count_only) return done(m);                       // count-only call
     if (all_kept && m > capacity) return overflow(m);                 // the needed count, nothing written
-    if (!win) *out_n = m;
+    if (!win && !quants) *out_n = m;
     if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
     const uint32_t un = (uint32_t)n;
     uint32_t *rank = nullptr, *sel = nullptr;
     const size_t agg_stride = round_up((size_t)n * 8) / 8;           // aggregate a's values start at a * agg_stride
-    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "one list of result arrays serves frames, slides and ranges");
+    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
+                  "one list of result arrays serves frames, slides, ranges and quantiles");
     const uint64_t* agg_src[SDQH_WAGG_MAX_AGGS] = {nullptr, nullptr, nullptr, nullptr};      // where each aggregate's / slide's values lie once the passes ran
     int64_t* agg_out = nullptr; int agg_n = 0;                        // ... and the caller's array for them: agg_out[a * capacity + j]
     if (sd) {
@@ -1476,6 +1598,66 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         LAUNCH(ctx, "k_wrg_fold", k_wrg_fold, fgrid, rg, rown, pend, vkey, gkey, un, (uint32_t)m, agg_stride, tstride, cap, elem, tree, fin);
         agg_out = rr->out; agg_n = rg.n;
         for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
+    }
+    if (quants && (qv || !all_kept)) {
+        // block 3: [heads | tile carries | row numbers | partition ends | tie-run ends | tie-run ranks | kept per tile of that pass | row
+        // numbers from 1 | kept per tile | kept positions | measure elements, an array per distinct measure | values | first heads per
+        // tile | next heads per tile] — the tie arrays only with a CUME_DIST / PERCENT_RANK column, the three kept arrays only when
+        // per_limit filters, the rest only when values are asked for
+        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+        const DevWquants& q = quants->q;
+        bool need_f = false, need_l = false;                            // does some column read the tie run's first / last position?
+        for (int c = 0; qv && c < q.n; ++c) { need_f |= q.a[c].fn == SDQH_WQ_PERCENT_RANK; need_l |= q.a[c].fn == SDQH_WQ_CUME_DIST; }
+        const size_t nv = qv ? (size_t)n : 0, nt = qv ? ntiles : 0;
+        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr, *tend = nullptr, *frank = nullptr, *fkept = nullptr, *tile_kept = nullptr;
+        uint64_t *elem = nullptr, *fin = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
+        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
+                heads = c.take<uint8_t>((size_t)n);
+                carry = c.take<WinCarry>(ntiles);
+                rown = c.take<uint32_t>(nv);
+                pend = c.take<uint32_t>(nv);
+                tend = c.take<uint32_t>(need_l ? (size_t)n : 0);
+                frank = c.take<uint32_t>(need_f ? (size_t)n : 0);
+                fkept = c.take<uint32_t>(need_f ? ntiles : 0);
+                rank = c.take<uint32_t>(all_kept ? 0 : (size_t)n);
+                tile_kept = c.take<uint32_t>(all_kept ? 0 : ntiles);
+                sel = c.take<uint32_t>(all_kept ? 0 : (size_t)n);
+                elem = c.take<uint64_t>(qv ? agg_stride * (size_t)q.nslots : 0);
+                fin = c.take<uint64_t>(qv ? agg_stride * (size_t)q.n : 0);
+                tfirst = c.take<WaggHeads>(nt);
+                tnext = c.take<WaggHeads>(nt);
+            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
+        if (!need_l) tend = nullptr;
+        if (!need_f) frank = nullptr;
+        if (all_kept) { rank = nullptr; sel = nullptr; }
+        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, quants->npart, nsort, s.perm, un, heads, carry, ntiles);
+        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
+        if (!all_kept) {                                              // sdqh_table_window's ROW_NUMBER filter: counted, the ways out again, then placed
+            const uint64_t pl = (uint64_t)quants->per_limit;
+            LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_ROW_NUMBER, pl, rank, tile_kept, ntiles);
+            LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (int rc = sync_stream(ctx)) return rc;
+            unsigned long long kept;
+            std::memcpy(&kept, ctx->result_host, 8);
+            m = std::min<int64_t>(limit, (int64_t)kept);
+            if (count_only || m == 0) return done(m);
+            if (m > capacity) return overflow(m);
+            LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
+        }
+        if (qv) {
+            LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
+            if (need_l) LAUNCH(ctx, "k_wq_ties", k_wq_ties, tgrid, heads, un, tfirst, ntiles);
+            LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
+            if (need_f) LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_RANK, ~0ull, frank, fkept, ntiles);
+            LAUNCH(ctx, "k_wq_stage", k_wq_stage, tgrid, table->stage, q, s.refs, s.perm, heads, tnext, un, agg_stride, pend, tend, elem, ntiles);
+            const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+            LAUNCH(ctx, "k_wq_value", k_wq_value, fgrid, q, sel, rown, pend, tend, frank, un, (uint32_t)m, agg_stride, elem, fin);
+            agg_out = quants->out; agg_n = q.n;
+            for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
+        }
+        rank = nullptr;                                               // (no rank column is emitted)
     }
     if (win || fr) {
         // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack] for a window, [heads | tile carries |
@@ -1601,7 +1783,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
@@ -1609,7 +1791,7 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hit
     if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1621,7 +1803,7 @@ int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
     const SortWindow win = {npartition, kind, per_limit, out_rank};
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1648,7 +1830,7 @@ int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hi
         }
         d.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op == SDQH_WAGG_SUM && d.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1675,7 +1857,7 @@ int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
         }
         d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
@@ -1722,7 +1904,50 @@ int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
         }
         d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_range", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, &sr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_range", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, &sr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_table_window_quantile(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                               int ncols, const sdqh_window_quantile* cols, int64_t per_limit, int64_t limit, int64_t capacity,
+                               int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
+    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && per_limit >= 1 && cols && ncols >= 1 && ncols <= SDQH_WQUANT_MAX_COLS;
+    for (int c = 0; ok && c < ncols; ++c) {
+        const sdqh_window_quantile& g = cols[c];
+        ok = g.fn >= SDQH_WQ_NTILE && g.fn <= SDQH_WQ_PERCENTILE_CONT;
+        if (g.fn == SDQH_WQ_NTILE) ok = ok && g.arg >= 1;
+        if (g.fn == SDQH_WQ_NTH) ok = ok && g.arg != 0;
+        if (g.fn == SDQH_WQ_PERCENTILE_DISC || g.fn == SDQH_WQ_PERCENTILE_CONT) ok = ok && g.p >= 0.0 && g.p <= 1.0;      // (a NaN fails both)
+    }
+    if (int rc = sort_enter(ctx, table, "table_window_quantile", ok)) return rc;
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = sort_terms_set(ctx, table, "table_window_quantile", nterms, in, false, terms)) return rc;
+    SortQuantiles sq; std::memset(&sq, 0, sizeof(sq));
+    sq.npart = npartition; sq.per_limit = per_limit; sq.out = out_cols; sq.q.n = ncols;
+    for (int c = 0; c < ncols; ++c) {
+        const sdqh_window_quantile& g = cols[c];
+        DevWquant& d = sq.q.a[c];
+        d.fn = g.fn; d.arg = g.arg; d.p = g.p; d.empty = (uint64_t)g.empty; d.slot = -1;
+        if (g.fn >= SDQH_WQ_NTH) {                                    // (the others have no measure)
+            const std::string col = "table_window_quantile: column " + std::to_string(c);
+            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, col + " names a field the table does not have");
+            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, col + ": keys and hit counts are integers");
+            DevSortKey sk; std::memset(&sk, 0, sizeof(sk));
+            sk.kind = g.kind; sk.index = g.index;
+            sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
+            d.is_f64 = sk.is_f64;
+            int k = 0;                                                // the measure's element array: shared with an earlier column of the same measure
+            while (k < sq.q.nslots && !(sq.q.slot[k].kind == sk.kind && sq.q.slot[k].index == sk.index && sq.q.slot[k].is_f64 == sk.is_f64)) ++k;
+            if (k == sq.q.nslots) sq.q.slot[sq.q.nslots++] = sk;
+            d.slot = k;
+        }
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_quantile", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, &sq, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
+int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
+    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_quantile_geometry: bad arguments");
+    *tile_rows = SORT_TILE;
+    return SDQH_OK;
 }
 
 int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {

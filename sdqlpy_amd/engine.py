@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import FRAMES, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, RangeRequest, ResultSet, SlideRequest, \
+from .result import FRAMES, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -173,6 +173,9 @@ class Engine:
         # values over value and group frames (ranged: result.RangeRequest) likewise, where the library has the window range extension
         # (abi.Context.table_window_range) — route "window_range", noted with the extra keys "per", "unit" and "ranges"
         self.device_window_range = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_RANGE", "1") != "0"
+        # functions of the group's size (quantiles: result.QuantileRequest) likewise, where the library has the window quantile extension
+        # (abi.Context.table_window_quantile) — route "window_quantile", noted with the extra keys "per", "per_limit" and "quantiles"
+        self.device_window_quantile = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_QUANTILE", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1720,7 +1723,7 @@ def _term_text(t):
 class _FrameSpec(list):
     """The sort terms of a FrameRequest and, beside them, `measures`: per aggregate its measure as a plain sort column (None for a
     count) — or None as a whole when some measure is no underived numeric column of the table (text, packed, decoded).  A
-    SlideRequest's and a RangeRequest's likewise; int_values: the columns the table keeps as integer-valued doubles (their results are converted back)."""
+    SlideRequest's, a RangeRequest's and a QuantileRequest's likewise (None too for a function without a measure); int_values: the columns the table keeps as integer-valued doubles (their results are converted back)."""
     measures = None
     int_values = ()
     decoded_order = ()       # the ORDER BY columns of a RangeRequest that are text or decoded on the host (_order_column_decoded)
@@ -1732,14 +1735,15 @@ def _order_spec(top, spec_of, decoded_of):
     decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
     text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest)):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest)):
         return spec
     spec = _FrameSpec(spec)
     if isinstance(top, RangeRequest):
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
-    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else (top.slides if isinstance(top, SlideRequest) else top.ranges))]
+    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else (top.slides if isinstance(top, SlideRequest) else
+                                                                              (top.ranges if isinstance(top, RangeRequest) else top.quants)))]
     cols = list(dict.fromkeys(col for col in measured if col is not None))
-    plain = spec_of([(c, "asc") for c in cols], False)
+    plain = spec_of([(c, "asc") for c in cols], False) if cols else []      # (a QuantileRequest may measure nothing)
     if plain is not None:
         by_name = dict(zip(cols, plain))
         spec.measures = [by_name.get(col) for col in measured]
@@ -1748,7 +1752,7 @@ def _order_spec(top, spec_of, decoded_of):
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile") and _term_text(t) is not None]}
     if isinstance(top, FrameRequest):                        # "order" / "per" as for a window; the aggregates in the order of their columns
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["aggs"] = [list(a) for a in top.aggs]
@@ -1758,6 +1762,9 @@ def _note_order_route(eng, top, spec, route):
     elif isinstance(top, RangeRequest):                      # likewise, and the frames' unit
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["unit"], note["ranges"] = top.unit, [list(a) for a in top.ranges]
+    elif isinstance(top, QuantileRequest):                   # likewise, and the per-group limit it filters by
+        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+        note["per_limit"], note["quantiles"] = int(min(top.per_limit, abi.SORT_ALL)), [list(a) for a in top.quants]
     elif isinstance(top, WindowRequest):                     # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
         note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
@@ -1801,6 +1808,11 @@ def _finish_top(rs, ordered, top):
             if name in rs.columns:
                 raise KeyError("ranged: the result already has a column %r" % name)
         return ResultSet(rs.columns + [a[0] for a in top.ranges], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
+    if isinstance(top, QuantileRequest):                    # the device's columns, one each
+        for name in (a[0] for a in top.quants):
+            if name in rs.columns:
+                raise KeyError("quantiles: the result already has a column %r" % name)
+        return ResultSet(rs.columns + [a[0] for a in top.quants], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
     if isinstance(top, WindowRequest) and top.name is not None:
         if top.name in rs.columns:
             raise KeyError("window: the result already has a column %r" % top.name)
@@ -1847,6 +1859,9 @@ def _order_route(eng, top, spec):
     "window_range" abi.Context.table_window_range: a RangeRequest under "window_slide"'s conditions (at most WRANGE_MAX_AGGS ranges; the
                  window range extension and Engine.device_window_range on) whose offsets the device's order term can take
                  (_range_offsets): a value frame needs an underived or arithmetically derived term, no text ranks
+    "window_quantile" abi.Context.table_window_quantile: a QuantileRequest under "window_slide"'s conditions (at most WQUANT_MAX_COLS
+                 columns, underived numeric measures, NTH's default within 2^53 for a column kept as integer-valued doubles; the window
+                 quantile extension and Engine.device_window_quantile on; terms as for "window")
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1871,6 +1886,11 @@ def _order_route(eng, top, spec):
                                 for _, _, col, _, _, default in top.ranges)
         fits = fits and _range_offsets(top, spec) is not None
         return "window_range" if fits and on("device_window_range", "has_window_range") and terms_ok else "host"
+    if isinstance(top, QuantileRequest):
+        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.quants) <= abi.WQUANT_MAX_COLS and getattr(spec, "measures", None) is not None
+        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
+                                for _, _, col, _, _, default in top.quants)
+        return "window_quantile" if fits and on("device_window_quantile", "has_window_quantile") and terms_ok else "host"
     if isinstance(top, WindowRequest):
         return "window" if 1 <= n <= abi.SORT_MAX_KEYS and on("device_window", "has_window") and terms_ok else "host"
     if derived:
@@ -1920,9 +1940,9 @@ def _range_offsets(top, spec):
 
 
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
-    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide" and "window_range" of _order_route: one waited-for call whose arrays are sized from the previous run
+    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range" and "window_quantile" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -1958,6 +1978,17 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
                 empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
             ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
         got = eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
+    elif route == "window_quantile":
+        quants = []
+        for (_, fn, measure, arg, p, default), col in zip(top.quants, spec.measures):
+            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
+            empty = 0
+            if col is not None and fn == "nth":                  # (the default's 64 bits as the device holds the column: see "window_slide")
+                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)
+                fill = slide_empty(default, as_f64 and measure not in spec.int_values, "quantiles")
+                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            quants.append((QUANTILE_FNS.index(fn), kind, index, is_f64, 0 if arg is None else arg, 0.0 if p is None else p, empty))
+        got = eng.ctx.table_window_quantile(table, min_hits, top.npartition, terms, quants, min(int(top.per_limit), abi.SORT_ALL), k, cap, want_hits=want_hits)
     else:
         got = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap,
                                    want_hits=want_hits, want_rank=top.name is not None)
@@ -2053,6 +2084,9 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _) in zip(ordered.rank, top.aggs)]
         if isinstance(ordered, _Ranked) and isinstance(top, SlideRequest):      # likewise: whatever a slide takes of such a column is an integer
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.slides)]
+        if isinstance(ordered, _Ranked) and isinstance(top, QuantileRequest):   # likewise for what is copied (nth, percentile_disc); a percentile_cont of such a
+            ordered.rank = [np.rint(a).astype(np.int64) if fn in ("nth", "percentile_disc") and col in bt.int_values else a     # column read its doubles as they are
+                            for a, (_, fn, col, _, _, _) in zip(ordered.rank, top.quants)]
         if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
@@ -2190,7 +2224,7 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
@@ -2205,6 +2239,8 @@ def _finalize(eng, op, env, top=None):
             route["slides"] = [list(a) for a in top.slides]
         if isinstance(top, RangeRequest):
             route["ranges"] = [list(a) for a in top.ranges]
+        if isinstance(top, QuantileRequest):
+            route["quantiles"] = [list(a) for a in top.quants]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)

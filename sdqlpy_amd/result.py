@@ -140,6 +140,11 @@ def check_window_columns(req, columns):
             raise KeyError("ranged: the result has no column %r" % col)
         if name in columns:
             raise KeyError("ranged: the result already has a column %r" % name)
+    for name, _, col, _, _, _ in getattr(req, "quants", ()):
+        if col is not None and col not in columns:
+            raise KeyError("quantiles: the result has no column %r" % col)
+        if name in columns:
+            raise KeyError("quantiles: the result already has a column %r" % name)
 
 
 WAGG_OPS = ("sum", "count", "min", "max")                 # their positions are abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX
@@ -219,9 +224,9 @@ class SlideRequest(WindowRequest):
         return SlideRequest(self[0], terms, self.npartition, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.slides])
 
 
-def _slide_int(x, what):
+def _slide_int(x, what, who="sliding"):
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
-        raise ValueError("sliding: %s is an integer, not %r" % (what, x))
+        raise ValueError("%s: %s is an integer, not %r" % (who, what, x))
     return int(x)
 
 
@@ -353,6 +358,80 @@ def _range_int_offset(x):
     if float(x) != int(x):
         raise ValueError("ranged: the offset %r over an integer column is not an integer" % (x,))
     return int(x)
+
+
+QUANTILE_FNS = ("ntile", "percent_rank", "cume_dist", "nth", "percentile_disc", "percentile_cont")     # their positions are abi.WQ_NTILE .. WQ_PERCENTILE_CONT
+
+
+class QuantileRequest(WindowRequest):
+    """Functions of the partition's size, travelling where a WindowRequest travels — and filtering as one: it reads as ROW_NUMBER with
+    per_limit (the rows whose row number in their group is at most per_limit are kept; WINDOW_ALL: every row) and no rank column.
+    quants = [(name of the new column, fn: a name of QUANTILE_FNS, measure column or None, arg: NTILE's b / NTH's k or None, p: a
+    percentile's or None, default: what NTH gives beyond the group, None = 0 for an int64 measure and NaN for a float64 one)] in the
+    order the columns are appended.  median is percentile_cont at 0.5 by the time it is here."""
+
+    def __new__(cls, k, terms, npartition, per_limit, quants):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, per_limit, None)
+        self.quants = [(str(n), str(fn), None if col is None else str(col), arg, p, default) for n, fn, col, arg, p, default in quants]
+        if not self.quants or self.per_limit < 1 or any(fn not in QUANTILE_FNS or ((col is None) != (fn in QUANTILE_FNS[:3])) for _, fn, col, _, _, _ in self.quants):
+            raise ValueError("quantiles: bad column")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
+        names = names or {}
+        return QuantileRequest(self[0], terms, self.npartition, self.per_limit, [(n, fn, names.get(col, col), arg, p, d) for n, fn, col, arg, p, d in self.quants])
+
+
+def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
+    """The checked QuantileRequest of `quantiles`: by / order as window_request takes them; cols = {new column: ("ntile", b) |
+    ("percent_rank",) | ("cume_dist",) | ("nth", measure, k[, default]) | ("percentile_disc", measure, p) | ("percentile_cont",
+    measure, p) | ("median", measure)} with 1 <= b < 2^63, k != 0 inside int64 (negative: from the group's end), 0 <= p <= 1; per: only
+    the first `per` rows of every group are returned (None: all; 1: one row per group).  columns: the result's column names when they
+    are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has already, ValueError
+    for everything else (a default that does not fit its column is found when the column is known: slide_empty)."""
+    if per is not None and (isinstance(per, bool) or not isinstance(per, (int, np.integer)) or int(per) < 1):
+        raise ValueError("quantiles: per is None or an integer of at least 1, not %r" % (per,))
+    req = window_request(None, by, order, "row_number", WINDOW_ALL if per is None else int(per), k=k)     # (its checks of by / order / k)
+    if not isinstance(cols, dict) or not cols:
+        raise ValueError("quantiles: cols is a non-empty dict {new column: (function, ...)}")
+    shapes = {"ntile": (2,), "percent_rank": (1,), "cume_dist": (1,), "nth": (3, 4), "percentile_disc": (3,), "percentile_cont": (3,), "median": (2,)}
+    out = []
+    for name, spec in cols.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) < 1:
+            raise ValueError("quantiles: a column is name: (function, ...)")
+        fn = spec[0]
+        if not isinstance(fn, str) or fn not in shapes:
+            raise ValueError("quantiles: the function is one of %s, median, not %r" % (", ".join(QUANTILE_FNS), fn))
+        if len(spec) not in shapes[fn]:
+            raise ValueError("quantiles: %s takes %s arguments, not %d" % (fn, " or ".join(str(s - 1) for s in shapes[fn]), len(spec) - 1))
+        col = arg = p = default = None
+        if fn == "ntile":
+            arg = _slide_int(spec[1], "b", "quantiles")
+            if not 1 <= arg < (1 << 63):
+                raise ValueError("quantiles: ntile's b is at least 1 and fits int64, not %d" % arg)
+        elif fn in ("nth", "percentile_disc", "percentile_cont", "median"):
+            col = spec[1]
+            if not isinstance(col, str):
+                raise ValueError("quantiles: a measure is a column name, not %r" % (col,))
+            if fn == "nth":
+                arg = _slide_int(spec[2], "k", "quantiles")
+                if arg == 0 or not -(1 << 63) <= arg < (1 << 63):
+                    raise ValueError("quantiles: nth's k is not 0 and fits int64, not %d" % arg)
+                default = spec[3] if len(spec) == 4 else None
+                if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
+                    raise ValueError("quantiles: a default is a number, not %r" % (default,))
+            else:
+                p = 0.5 if fn == "median" else spec[2]
+                if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:      # (a NaN fails both)
+                    raise ValueError("quantiles: p lies in [0, 1], not %r" % (p,))
+                p = float(p)
+                fn = "percentile_cont" if fn == "median" else fn
+        out.append((name, fn, col, arg, p, default))
+    req = QuantileRequest(req[0], req[1], req.npartition, req.per_limit, out)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
 
 
 def slide_empty(default, is_f64, what="sliding"):
@@ -708,6 +787,70 @@ class ResultSet:
         a count 0."""
         return self.ranged_by(range_request(self.columns, by, order, aggs, unit))
 
+    def quantiled(self, req):
+        """The rows a QuantileRequest keeps, in its order (the first req[0] of them), with its columns appended: what
+        sdqh_table_window_quantile does on the device (include/sdqh_sort_quantile.h), on the host, under the same key images
+        (order_image) and with the same IEEE expressions, so that both agree bit for bit on every value that is not a NaN.  For sorted
+        row j in a partition [s, e]: m = e - s + 1, i = j - s, [f, l] the offsets of its tie run; every function looks at the whole
+        partition, per_limit and the limit cut the rows off afterwards."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, part_head, tie_head = self._window_heads(req.by, req.order)
+        n = self._n
+        pos = np.arange(n, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(part_head, pos, 0)) if n else pos
+        heads = np.nonzero(part_head)[0]
+        end = (np.append(heads[1:], n) - 1)[np.cumsum(part_head) - 1] if n else pos
+        m, i = end - start + 1, pos - start
+        new = []
+        for name, fn, col, arg, p, default in req.quants:
+            x = None if col is None else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("quantiles: %s of column %r: the measure is not numeric" % (fn, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            if x is not None:
+                x = np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+            if fn == "ntile":
+                q, r = m // arg, m % arg                                 # (b > m: q = 0 and r = m, every row takes the first arm)
+                big = r * (q + 1)
+                v = np.where(i < big, i // (q + 1) + 1, r + (i - big) // np.maximum(q, 1) + 1).astype(np.int64)
+            elif fn == "percent_rank":
+                f = (np.maximum.accumulate(np.where(tie_head, pos, 0)) if n else pos) - start
+                v = np.where(m == 1, np.float64(0.0), f.astype(np.float64) / np.maximum(m - 1, 1).astype(np.float64))
+            elif fn == "cume_dist":
+                ties = np.nonzero(tie_head)[0]
+                last = (np.append(ties[1:], n) - 1)[np.cumsum(tie_head) - 1] if n else pos
+                v = (last - start + 1).astype(np.float64) / m.astype(np.float64)
+            elif fn == "nth":
+                fill = slide_empty(default, is_f, "quantiles")
+                ak = min(abs(arg), n + 1)                                # (a k beyond n lies outside every partition: no wide arithmetic)
+                inside = ak <= m
+                src = np.where(inside, start + ak - 1 if arg > 0 else end + 1 - ak, pos)
+                bits = np.where(inside, x[src].view(np.uint64), np.array(fill).view(np.uint64))      # (by bits: a NaN keeps its payload)
+                v = bits.view(np.float64 if is_f else np.int64)
+            elif fn == "percentile_disc":
+                up = np.ceil(np.float64(p) * m.astype(np.float64))
+                at = np.minimum(np.where(up >= 1.0, up - 1.0, 0.0).astype(np.int64), m - 1)
+                v = x[start + at]
+            else:
+                t = np.float64(p) * (m - 1).astype(np.float64)
+                lo, hi = np.floor(t), np.ceil(t)
+                al, ah = np.minimum(lo.astype(np.int64), m - 1), np.minimum(hi.astype(np.int64), m - 1)
+                a, b = x[start + al].astype(np.float64), x[start + ah].astype(np.float64)     # (an int64 by one round-to-nearest conversion)
+                with np.errstate(invalid="ignore", over="ignore"):
+                    v = np.where(al == ah, a, a + (b - a) * (t - lo))    # four IEEE operations, each a ufunc of its own: nothing is fused
+            new.append((name, np.ascontiguousarray(v)))
+        keep = np.nonzero(i < req.per_limit)[0][:max(0, int(req[0]))]
+        cols = [c[idx[keep]] for c in self._cols]                        # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[keep] for _, c in new])
+
+    def quantiles(self, by, order, cols, per=None):
+        """The rows ordered by `by` then `order` — every row, or with `per` the first `per` of every group of `by` (1: one row per
+        group) — plus one column per function of the group's size: cols = {new column: ("ntile", b) | ("percent_rank",) |
+        ("cume_dist",) | ("nth", measure, k[, default]) | ("percentile_disc", measure, p) | ("percentile_cont", measure, p) |
+        ("median", measure)}.  Every function sees its whole group, whatever `per` keeps."""
+        return self.quantiled(quantile_request(self.columns, by, order, cols, per))
+
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:
         aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS, the frame rows [row + lo, row + hi] of
@@ -728,6 +871,8 @@ class ResultSet:
             return self.slid(req)
         if isinstance(req, RangeRequest):
             return self.ranged_by(req)
+        if isinstance(req, QuantileRequest):
+            return self.quantiled(req)
         self._wait()
         check_window_columns(req, self.columns)
         idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])

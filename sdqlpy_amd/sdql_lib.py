@@ -457,6 +457,24 @@ def sdql_compile(in_type):
             req = range_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, unit)     # checked before anything is launched
             return lambda *args: run(args, req)
 
+        def quantiles(by, order, cols, per=None):
+            """The same query finished with ORDER BY `by`, `order` and one column per function of the size of the row's group of `by`:
+            cols = {new column: ("ntile", b) | ("percent_rank",) | ("cume_dist",) | ("nth", measure, k[, default]) |
+            ("percentile_disc", measure, p) | ("percentile_cont", measure, p) | ("median", measure)} — median is percentile_cont at
+            0.5, a negative k counts from the group's end.  per: only the first `per` rows of every group are returned (None: every
+            row; 1: one row per group, the GROUP BY form), e.g. ``q3.quantiles(["o_orderdate"], [("revenue", "asc")], {"med":
+            ("median", "revenue"), "p90": ("percentile_disc", "revenue", 0.9)}, per=1)(li, cu, ord)``.  ntile is int64; percent_rank,
+            cume_dist and percentile_cont are float64; nth and percentile_disc take the measure's dtype, nth beyond the group gives
+            `default` (0 for an int64 measure, NaN for a float64 one).  Names, functions, b, k and p are checked here, before anything
+            is launched; whether a default fits its column can only be told once the query has run: that ValueError comes from the
+            call."""
+            from . import engine, frontend
+            from .result import quantile_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = quantile_request(engine.result_columns(cache["plan"]), list(by), list(order), cols, per)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -464,6 +482,7 @@ def sdql_compile(in_type):
         wrapper.over = over
         wrapper.sliding = sliding
         wrapper.ranged = ranged
+        wrapper.quantiles = quantiles
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
