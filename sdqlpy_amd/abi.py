@@ -54,6 +54,14 @@ WRANGE_MAX_AGGS = 4
 WINDOW_QUANTILE_EXPORTS = ["sdqh_table_window_quantile", "sdqh_window_quantile_geometry"]
 WQ_NTILE, WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_NTH, WQ_PERCENTILE_DISC, WQ_PERCENTILE_CONT = 0, 1, 2, 3, 4, 5
 WQUANT_MAX_COLS = 4
+# the five of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
+WINDOW_EXTENSIONS = {
+    "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
+    "has_window_agg": (WINDOW_AGG_EXPORTS, "sdqh_sort_frames.h", "window aggregate", "has_window"),
+    "has_window_slide": (WINDOW_SLIDE_EXPORTS, "sdqh_sort_slide.h", "window slide", "has_window_agg"),
+    "has_window_range": (WINDOW_RANGE_EXPORTS, "sdqh_sort_range.h", "window range", "has_window_slide"),
+    "has_window_quantile": (WINDOW_QUANTILE_EXPORTS, "sdqh_sort_quantile.h", "window quantile", "has_window_slide"),
+}
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
 EXTREMA_EXPORTS = ["sdqh_table_extrema_begin", "sdqh_table_extrema_fold", "sdqh_table_extrema_end", "sdqh_column_extrema", "sdqh_extrema_geometry"]
@@ -64,6 +72,11 @@ MAX_IPRED, MAX_FPRED, MAX_SPRED, MAX_STR_CONST = 4, 4, 1, 64
 MAX_PROBE, MAX_PAYLOAD, MAX_GROUPKEYS, MAX_SMALL_GROUPS, MAX_COMPACT_COLS = 2, 4, 2, 64, 6
 
 INT64_MIN, INT64_MAX = -(1 << 63), (1 << 63) - 1
+
+
+def _measure_is_f64(kind, is_f64):
+    """Does a window call return the measure (kind, index, is_f64) as doubles?  A value is one; a payload column is what is_f64 says."""
+    return kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))
 
 
 def _range_offset(x):
@@ -1273,29 +1286,42 @@ class Context:
         self._check(self.lib.sdqh_sort_geometry(self.handle, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
-    def _need_window(self, what):
-        if not self.library.has_window:
-            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window extension (include/sdqh_sort_window.h)" % (what, self.library.path))
+    def _need(self, flag, what):
+        """`what` needs the window extension behind Library.`flag` (WINDOW_EXTENSIONS)."""
+        if not getattr(self.library, flag):
+            _, header, label, _ = WINDOW_EXTENSIONS[flag]
+            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no %s extension (include/%s)" % (what, self.library.path, label, header))
+
+    def _window_geometry(self, flag, nvalues):
+        """The geometry export of a window extension: its nvalues int64 results (one: as a scalar)."""
+        export = WINDOW_EXTENSIONS[flag][0][1]
+        self._need(flag, export[len("sdqh_"):])
+        out = [C.c_int64() for _ in range(nvalues)]
+        self._check(getattr(self.lib, export)(self.handle, *[C.byref(o) for o in out]))
+        return out[0].value if nvalues == 1 else tuple(o.value for o in out)
+
+    def _window_columns_call(self, name, table, min_hits, npartition, terms, arr, ncols, tail, limit, capacity, want_hits, want_cols, as_f64):
+        """What table_window_agg, _slide, _range and _quantile share behind their struct arrays `arr` of ncols columns: the call's leading
+        arguments (tail: those between the array and the limit), _sorted_call with one array per column, and the columns of as_f64
+        viewed as the doubles they are.  -> (keys, payload, values, hits, columns) — columns None without want_cols."""
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(ncols), arr) + tail + (C.c_int64(limit),)
+        got = self._sorted_call(name, table, lead, limit, capacity, want_hits, bool(want_cols), naggs=max(1, ncols))
+        if got[4] is None:
+            return got
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
 
     def table_window(self, table, min_hits, npartition, terms, kind, per_limit, limit, capacity, want_hits=True, want_rank=True):
         """Ranks inside partitions of the ordered entries: terms as table_sorted_by takes them, the first npartition of them PARTITION
         BY; kind in WIN_ROW_NUMBER / WIN_RANK / WIN_DENSE_RANK; the rows with rank <= per_limit (SORT_ALL: every row), in sorted order,
         the first min(limit, kept) of them.  The arrays are sized from `capacity`; a result that does not fit is fetched again with the
         exact size.  Returns (keys, payload, values, hits, ranks) — ranks None without want_rank."""
-        self._need_window("table_window")
+        self._need("has_window", "table_window")
         lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(kind), C.c_int64(per_limit), C.c_int64(limit))
         return self._sorted_call("table_window", table, lead, limit, capacity, want_hits, bool(want_rank))
 
     def window_geometry(self):
         """Sorted positions one wave ranks per step of sdqh_table_window's tile scan (what the tests size their cases from)."""
-        self._need_window("window_geometry")
-        a = C.c_int64()
-        self._check(self.lib.sdqh_window_geometry(self.handle, C.byref(a)))
-        return a.value
-
-    def _need_window_agg(self, what):
-        if not self.library.has_window_agg:
-            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window aggregate extension (include/sdqh_sort_frames.h)" % (what, self.library.path))
+        return self._window_geometry("has_window", 1)
 
     def table_window_agg(self, table, min_hits, npartition, terms, aggs, limit, capacity_hint, want_hits=True):
         """Aggregates over window frames of the ordered entries: terms and npartition as table_window takes them; aggs: [(op, frame,
@@ -1303,25 +1329,16 @@ class Context:
         the measure as a sort column is named (COUNT ignores it).  Every selected row is kept; the first min(limit, n) in sorted order.
         Returns (keys, payload, values, hits, aggs) — aggs one array per aggregate, float64 for a double measure under SUM / MIN / MAX,
         else int64."""
-        self._need_window_agg("table_window_agg")
+        self._need("has_window_agg", "table_window_agg")
         arr = (WindowAgg * max(1, len(aggs)))()
         for i, (op, frame, kind, index, is_f64) in enumerate(aggs):
             arr[i].op, arr[i].frame, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(frame), int(kind), int(index), 1 if is_f64 else 0
-        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(aggs)), arr, C.c_int64(limit))
-        got = self._sorted_call("table_window_agg", table, lead, limit, capacity_hint, want_hits, True, naggs=max(1, len(aggs)))
-        as_f64 = [op != WAGG_COUNT and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))) for op, _, kind, _, is_f64 in aggs]
-        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+        as_f64 = [op != WAGG_COUNT and _measure_is_f64(kind, is_f64) for op, _, kind, _, is_f64 in aggs]
+        return self._window_columns_call("table_window_agg", table, min_hits, npartition, terms, arr, len(aggs), (), limit, capacity_hint, want_hits, True, as_f64)
 
     def window_agg_geometry(self):
         """Sorted positions one wave aggregates per step of sdqh_table_window_agg's tile scan (what the tests size their cases from)."""
-        self._need_window_agg("window_agg_geometry")
-        a = C.c_int64()
-        self._check(self.lib.sdqh_window_agg_geometry(self.handle, C.byref(a)))
-        return a.value
-
-    def _need_window_slide(self, what):
-        if not self.library.has_window_slide:
-            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window slide extension (include/sdqh_sort_slide.h)" % (what, self.library.path))
+        return self._window_geometry("has_window_agg", 1)
 
     def table_window_slide(self, table, min_hits, npartition, terms, slides, limit, capacity, want_hits=True):
         """Values over sliding frames of the ordered entries: terms and npartition as table_window takes them; slides: [(op, kind,
@@ -1330,27 +1347,18 @@ class Context:
         SLIDE_UNBOUNDED_FOLLOWING: no bound), empty: the 64 bits an empty frame gives, as an int64.  Every selected row is kept; the
         first min(limit, n) in sorted order.  Returns (keys, payload, values, hits, slides) — slides one array per slide, float64 for a
         double measure under any op but COUNT, else int64."""
-        self._need_window_slide("table_window_slide")
+        self._need("has_window_slide", "table_window_slide")
         arr = (WindowSlide * max(1, len(slides)))()
         for i, (op, kind, index, is_f64, lo, hi, empty) in enumerate(slides):
             arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
             arr[i].lo, arr[i].hi, arr[i].empty = int(lo), int(hi), int(empty)
-        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(slides)), arr, C.c_int64(limit))
-        got = self._sorted_call("table_window_slide", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(slides)))
-        as_f64 = [op != WAGG_COUNT and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))) for op, kind, _, is_f64, _, _, _ in slides]
-        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+        as_f64 = [op != WAGG_COUNT and _measure_is_f64(kind, is_f64) for op, kind, _, is_f64, _, _, _ in slides]
+        return self._window_columns_call("table_window_slide", table, min_hits, npartition, terms, arr, len(slides), (), limit, capacity, want_hits, True, as_f64)
 
     def window_slide_geometry(self):
         """(sorted positions per tile of sdqh_table_window_slide's scans, the largest frame width a kernel walks row by row or 0): what
         the tests size their cases from."""
-        self._need_window_slide("window_slide_geometry")
-        a, b = C.c_int64(), C.c_int64()
-        self._check(self.lib.sdqh_window_slide_geometry(self.handle, C.byref(a), C.byref(b)))
-        return a.value, b.value
-
-    def _need_window_range(self, what):
-        if not self.library.has_window_range:
-            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window range extension (include/sdqh_sort_range.h)" % (what, self.library.path))
+        return self._window_geometry("has_window_slide", 2)
 
     def table_window_range(self, table, min_hits, npartition, terms, ranges, limit, capacity, want_hits=True):
         """Values over value and group frames of the ordered entries: terms and npartition as table_window takes them; ranges: [(op,
@@ -1358,28 +1366,19 @@ class Context:
         of the one ORDER BY term's value: ints for an integer term, floats for a double one) or WRANGE_GROUPS (offsets count tie runs),
         lo / hi signed along the order (negative = preceding, None: unbounded), empty: the 64 bits an empty frame gives, as an int64.
         Every selected row is kept; the first min(limit, n) in sorted order.  Returns what table_window_slide returns."""
-        self._need_window_range("table_window_range")
+        self._need("has_window_range", "table_window_range")
         arr = (WindowRange * max(1, len(ranges)))()
         for i, (op, kind, index, is_f64, unit, lo, hi, empty) in enumerate(ranges):
             arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64, arr[i].unit = int(op), int(kind), int(index), 1 if is_f64 else 0, int(unit)
             arr[i].flags = (WRANGE_LO_UNBOUNDED if lo is None else 0) | (WRANGE_HI_UNBOUNDED if hi is None else 0)
             arr[i].lo, arr[i].hi, arr[i].empty = _range_offset(lo), _range_offset(hi), int(empty)
-        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(ranges)), arr, C.c_int64(limit))
-        got = self._sorted_call("table_window_range", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(ranges)))
-        as_f64 = [r[0] != WAGG_COUNT and (r[1] == SORT_VALUE or (r[1] == SORT_PAYLOAD and bool(r[3]))) for r in ranges]
-        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+        as_f64 = [r[0] != WAGG_COUNT and _measure_is_f64(r[1], r[3]) for r in ranges]
+        return self._window_columns_call("table_window_range", table, min_hits, npartition, terms, arr, len(ranges), (), limit, capacity, want_hits, True, as_f64)
 
     def window_range_geometry(self):
         """(sorted positions per tile of sdqh_table_window_range's passes, the largest frame width a kernel walks row by row or 0): what
         the tests size their cases from."""
-        self._need_window_range("window_range_geometry")
-        a, b = C.c_int64(), C.c_int64()
-        self._check(self.lib.sdqh_window_range_geometry(self.handle, C.byref(a), C.byref(b)))
-        return a.value, b.value
-
-    def _need_window_quantile(self, what):
-        if not self.library.has_window_quantile:
-            raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no window quantile extension (include/sdqh_sort_quantile.h)" % (what, self.library.path))
+        return self._window_geometry("has_window_range", 2)
 
     def table_window_quantile(self, table, min_hits, npartition, terms, cols, per_limit, limit, capacity, want_hits=True, want_cols=True):
         """Functions of the partition's size beside the ordered entries: terms and npartition as table_window takes them; cols: [(fn,
@@ -1389,27 +1388,21 @@ class Context:
         returned (SORT_ALL: every row), the first min(limit, kept) in sorted order.  Returns (keys, payload, values, hits, cols) — cols
         one array per column: int64 for NTILE, float64 for PERCENT_RANK / CUME_DIST / PERCENTILE_CONT, the measure's dtype for NTH /
         PERCENTILE_DISC; None without want_cols."""
-        self._need_window_quantile("table_window_quantile")
+        self._need("has_window_quantile", "table_window_quantile")
         arr = (WindowQuantile * max(1, len(cols)))()
         for i, (fn, kind, index, is_f64, arg, p, empty) in enumerate(cols):
             if not INT64_MIN <= int(arg) <= INT64_MAX:           # (ctypes would cut it to 64 bits without a word)
                 raise SdqhError(ERR_INVALID, "table_window_quantile: the argument %d does not fit int64" % int(arg))
             arr[i].fn, arr[i].kind, arr[i].index, arr[i].is_f64 = int(fn), int(kind), int(index), 1 if is_f64 else 0
             arr[i].arg, arr[i].p, arr[i].empty = int(arg), float(p), int(empty)
-        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(len(cols)), arr, C.c_int64(per_limit), C.c_int64(limit))
-        got = self._sorted_call("table_window_quantile", table, lead, limit, capacity, want_hits, bool(want_cols), naggs=max(1, len(cols)))
-        if got[4] is None:
-            return got
-        as_f64 = [fn in (WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_PERCENTILE_CONT) or (fn in (WQ_NTH, WQ_PERCENTILE_DISC) and (kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))))
+        as_f64 = [fn in (WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_PERCENTILE_CONT) or (fn in (WQ_NTH, WQ_PERCENTILE_DISC) and _measure_is_f64(kind, is_f64))
                   for fn, kind, _, is_f64, _, _, _ in cols]
-        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+        return self._window_columns_call("table_window_quantile", table, min_hits, npartition, terms, arr, len(cols), (C.c_int64(per_limit),), limit, capacity, want_hits,
+                                         want_cols, as_f64)
 
     def window_quantile_geometry(self):
         """Sorted positions per tile of sdqh_table_window_quantile's passes: what the tests size their cases from."""
-        self._need_window_quantile("window_quantile_geometry")
-        a = C.c_int64()
-        self._check(self.lib.sdqh_window_quantile_geometry(self.handle, C.byref(a)))
-        return a.value
+        return self._window_geometry("has_window_quantile", 1)
 
     def _need_extrema(self, what):
         if not self.library.has_extrema:
@@ -1665,27 +1658,24 @@ class Library:
             L.sdqh_text_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
             L.sdqh_table_sorted_by.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
-        self.has_window = self.has_sort_terms and all(hasattr(L, s) for s in WINDOW_EXPORTS)      # ... and ranks inside partitions (include/sdqh_sort_window.h)
+        for flag, (exports, _, _, base) in WINDOW_EXTENSIONS.items():      # ... and the five window extensions, each on the one before it
+            setattr(self, flag, bool(getattr(self, base)) and all(hasattr(L, s) for s in exports))
         if self.has_window:
             L.sdqh_table_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_geometry.argtypes = [C.c_void_p, C.c_void_p]
-        self.has_window_agg = self.has_window and all(hasattr(L, s) for s in WINDOW_AGG_EXPORTS)      # ... and aggregates over frames (include/sdqh_sort_frames.h)
         if self.has_window_agg:
             L.sdqh_table_window_agg.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_agg_geometry.argtypes = [C.c_void_p, C.c_void_p]
-        self.has_window_slide = self.has_window_agg and all(hasattr(L, s) for s in WINDOW_SLIDE_EXPORTS)      # ... and sliding frames (include/sdqh_sort_slide.h)
         if self.has_window_slide:
             L.sdqh_table_window_slide.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_slide_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        self.has_window_range = self.has_window_slide and all(hasattr(L, s) for s in WINDOW_RANGE_EXPORTS)    # ... and value / group frames (include/sdqh_sort_range.h)
         if self.has_window_range:
             L.sdqh_table_window_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_range_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        self.has_window_quantile = self.has_window_slide and all(hasattr(L, s) for s in WINDOW_QUANTILE_EXPORTS)    # ... and functions of the partition's size (include/sdqh_sort_quantile.h)
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -25,15 +25,20 @@
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
 // (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h), sdqh_table_window_slide
 // (include/sdqh_sort_slide.h), sdqh_table_window_range (include/sdqh_sort_range.h) and sdqh_table_window_quantile
-// (include/sdqh_sort_quantile.h): select -> order -> rank, aggregate, slide, range or quantiles -> emit
-// (ordered_impl).  What differs between them is
-// data, not code:
+// (include/sdqh_sort_quantile.h): select -> passes -> step -> emit -> fetch (ordered_impl, the spine).  What differs between them
+// is data, not code: their terms, and ONE step description (SortStep) that the spine hands to one dispatch.  On the host the step
+// is three pieces: the partition pass (Partitions + partition_pass: the arrays every family reads its partitions from, k_win_heads
+// and of k_win_scan / k_wsl_rows / k_wagg_next those the family names), the filter (rank_filter: k_win_rank -> k_sort_scan -> the
+// kept count to the host -> the ways out -> k_win_place; a window filters on its own ranks, quantiles on row numbers) and the family
+// steps (step_ranks / _frames / _slides / _ranges / _quantiles: each lays out scratch block 3, runs the pieces above and its own
+// kernels and says where each output column lies).  In front of them the entry points share window_enter, measure_set and
+// fold_class.  On the device:
 //
 //   a TERM            every sort column is a DevSortTerm.  k_sort_keys reads the column (sort_raw) and, for a DERIVED term, takes
 //                     field = (uint64(source) / div) % mod + add and a bounds-checked gather through a ranks column in front of
 //                     sort_bits; sdqh_table_sorted's keys are terms with no derivation.  sdqh_text_ranks makes such a ranks column of
 //                     a text column (k_text_masks / k_text_pack, the passes above, k_rank_count / k_rank_place: see there).
-//   a WINDOW          optional (SortWindow).  sdqh_table_window ranks the ordered entries inside PARTITIONS (maximal runs of sorted
+//   a WINDOW          optional (STEP_RANKS).  sdqh_table_window ranks the ordered entries inside PARTITIONS (maximal runs of sorted
 //                     positions whose first npartition keys are equal) and keeps the rows whose rank is <= per_limit — ROW_NUMBER /
 //                     RANK / DENSE_RANK OVER (PARTITION BY ... ORDER BY ...).  Without one the rank step launches nothing, allocates
 //                     nothing, and the emit reads the permutation directly.  With one, between the passes and the emit:
@@ -54,7 +59,7 @@
 //                     those counts scanned over the tiles, then the kept positions placed in order (ballot + lanes below: no atomic
 //                     cursor, because order is the contract).  per_limit >= n keeps everything: both are skipped
 //   k_sort_emit       then goes through the kept positions and writes the rank column beside the others
-//   FRAMES            in a window's place (SortFrames).  sdqh_table_window_agg (include/sdqh_sort_frames.h) folds a measure column over
+//   FRAMES            in a window's place (STEP_FRAMES).  sdqh_table_window_agg (include/sdqh_sort_frames.h) folds a measure column over
 //                     frames of the same partitions — SUM / COUNT / MIN / MAX OVER (PARTITION BY ... ORDER BY ... ROWS | RANGE | the
 //                     whole partition) — and keeps every row.  Behind k_win_heads, in place of the rank step:
 //
@@ -68,7 +73,7 @@
 //                     only for RANGE / PARTITION frames, backwards: the first heads of the later tiles (suffix minimum), then per
 //                     position the last row of its tie run / partition, whose ROWS value is copied: the frames agree bit for bit.
 //                     Row j is sorted position j: the first m values are the output, k_sort_emit writes the rows as for a plain sort
-//   SLIDES            in their place (SortSlides).  sdqh_table_window_slide (include/sdqh_sort_slide.h) takes SUM / COUNT / MIN / MAX /
+//   SLIDES            in their place (STEP_SLIDES).  sdqh_table_window_slide (include/sdqh_sort_slide.h) takes SUM / COUNT / MIN / MAX /
 //                     FIRST / LAST over ROWS BETWEEN lo AND hi of the same partitions.  Behind k_win_heads and k_win_scan:
 //
 //   k_wsl_rows        the row number of every position in its partition (k_win_rank's ROW_NUMBER arm), the tile's first partition head
@@ -78,7 +83,7 @@
 //   k_wsl_tiles / k_wsl_scan / k_wsl_run
 //                     the tile scan of the frames, restarted at block heads, forwards (prefix folds) and backwards (suffix folds)
 //   k_wsl_fold        row j's frame [l, r] spans at most two blocks: suffix[l] (+) prefix[r], or one of them — see the section
-//   RANGES            in their place (SortRanges).  sdqh_table_window_range (include/sdqh_sort_range.h) takes the same six ops over VALUE
+//   RANGES            in their place (STEP_RANGES).  sdqh_table_window_range (include/sdqh_sort_range.h) takes the same six ops over VALUE
 //                     and GROUP frames, whose width depends on the data.  Behind k_win_heads, k_win_scan, k_wsl_rows and k_wagg_next:
 //
 //   k_win_rank        only with a GROUPS range: the dense rank of every position (every row kept)
@@ -87,7 +92,7 @@
 //   k_wrg_tiles / k_wrg_upper
 //                     the fold trees bottom-up: nine levels inside the wave that owns a tile, the rest in one workgroup per range
 //   k_wrg_fold        per row two binary searches of its partition for the frame's ends, then the tree's iterative query — see the section
-//   QUANTILES         in their place (SortQuantiles).  sdqh_table_window_quantile (include/sdqh_sort_quantile.h) takes NTILE / PERCENT_RANK /
+//   QUANTILES         in their place (STEP_QUANTILES).  sdqh_table_window_quantile (include/sdqh_sort_quantile.h) takes NTILE / PERCENT_RANK /
 //                     CUME_DIST / NTH / PERCENTILE_DISC / PERCENTILE_CONT — everything that needs the partition's size — and keeps the
 //                     rows whose row number is <= per_limit (k_win_rank / k_sort_scan / k_win_place, as a window does).  Behind k_win_heads,
 //                     k_win_scan, k_wsl_rows and k_wagg_next:
@@ -1455,283 +1460,310 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
     return SDQH_OK;
 }
 
-// the optional third step of ordered_impl: ranks of `kind` inside partitions by the first npart terms, rows with rank <= per_limit kept
-struct SortWindow { int npart, kind; int64_t per_limit; int64_t* out_rank; };
-// ... or, in its place, aggregates over frames of the same partitions (sdqh_table_window_agg): every row kept, out[a * capacity + j]
-struct SortFrames { int npart; DevWaggs aggs; int64_t* out; };
-// ... or values over sliding frames (sdqh_table_window_slide): likewise; lo / hi as the caller gave them (sl's are set once n is known)
-struct SortSlides { int npart; DevWslides sl; int64_t lo[SDQH_WSLIDE_MAX_AGGS], hi[SDQH_WSLIDE_MAX_AGGS]; int64_t* out; };
-// ... or values over value and group frames (sdqh_table_window_range): likewise
-struct SortRanges { int npart; DevWranges rg; int64_t* out; };
-// ... or functions of the partition's size (sdqh_table_window_quantile): out[c * capacity + i] beside the i-th returned row, and —
-// alone among the four — a window's per_limit on the row number: out == nullptr still filters
-struct SortQuantiles { int npart; DevWquants q; int64_t per_limit; int64_t* out; };
+// ---- the step behind the sort ------------------------------------------------------------------------------------------------------
+// What an entry point asks for between the passes and the emit.  kind: nothing (the two plain sorts), ranks inside partitions or, in
+// their place, columns over the same partitions (frames, slides, ranges, quantiles).  The first npart terms are PARTITION BY.  The
+// filter: only the rows whose rank of `rank_kind` is <= per_limit are returned (filters false: the entry point has no such argument).
+// out: the rank column, or out[a * capacity + j] = column a beside returned row j — nullptr: rows only, no column is computed.  Then
+// the family's device arguments (a slide's lo / hi: the caller's).
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES };
+struct SortStep {
+    StepKind kind; int npart;
+    bool filters; int rank_kind; int64_t per_limit;
+    int64_t* out;
+    union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; };
+};
+static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
+              "one list of result arrays serves frames, slides, ranges and quantiles");
+static SortStep sort_step(StepKind kind, int npart, int64_t* out) {
+    SortStep st; std::memset(&st, 0, sizeof(st));
+    st.kind = kind; st.npart = npart; st.out = out; st.rank_kind = SDQH_WIN_ROW_NUMBER; st.per_limit = INT64_MAX;
+    return st;
+}
 
-// The table entry points behind their argument checks: select -> order -> rank (win != nullptr) or aggregate (frames != nullptr) or
-// slide (slides != nullptr) or range (ranges != nullptr) or quantiles (quants != nullptr; at most one of the five) -> emit.  who: the
-// entry point's name in messages.
-static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortWindow* win,
-                        const SortFrames* frames, const SortSlides* slides, const SortRanges* ranges, const SortQuantiles* quants, int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
+// One call between the passes and the emit: what the pieces of its step read, and what they leave for the emit and the fetch.
+struct StepRun {
+    sdqh_ctx* ctx; sdqh_table* table; const std::string& me; const SortStep& step; const SortState& s; Scratch& scratch;
+    int nsort; int64_t n, limit, capacity; bool count_only, all_kept; int64_t* out_n;
+    uint32_t un; size_t stride;                                       // n as the kernels take it; column a's values start at a * stride
+    int64_t m;                                                        // rows returned: min(limit, kept)
+    const uint32_t* sel = nullptr;                                    // their sorted positions (nullptr: the first m)
+    const uint32_t* rank = nullptr;                                   // the ranks the emit writes beside them (nullptr: no rank column)
+    const uint64_t* col_src[SDQH_WAGG_MAX_AGGS] = {nullptr, nullptr, nullptr, nullptr};      // where each of the ncols columns lies once the step ran
+    int ncols = 0;
+    bool ended = false;                                               // a way out was taken: *out_n is set and the call closed
+    unsigned row_grid() const { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8)); }      // a thread per returned row
+    void columns(const uint64_t* first, int count) { for (ncols = 0; ncols < count; ++ncols) col_src[ncols] = first + (size_t)ncols * stride; }
+    int done(int64_t rows) { *out_n = rows; call_end(ctx); ended = true; return SDQH_OK; }
+    int overflow(int64_t rows) { *out_n = rows; call_end(ctx); ended = true; return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
+    int nomem() const { return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory"); }
+};
+
+// The partition pass: the arrays every family reads its partitions from — out of the family's block 3 (take() inside its layout):
+// head flags and tile carries always, the others as its kernels read them (an array not asked for takes no bytes) — and the kernels
+// that fill them: `what` of the four, in this order.  A family whose own kernels come in between asks twice: frames fill the first
+// heads themselves (k_wagg_tiles), quantiles filter behind PP_SCAN and mark tie heads (k_wq_ties) in front of PP_NEXT.
+struct Partitions {
+    uint32_t ntiles = 0; unsigned tgrid = 0;                          // a wave per tile of SORT_TILE sorted positions
+    uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t* rown = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
+    void take(Carver& c, int64_t n, bool rows, bool firsts, bool nexts) {
+        ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE); tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        heads = c.take<uint8_t>((size_t)n);
+        carry = c.take<WinCarry>(ntiles);
+        rown = c.take<uint32_t>(rows ? (size_t)n : 0);
+        tfirst = c.take<WaggHeads>(firsts ? ntiles : 0);
+        tnext = c.take<WaggHeads>(nexts ? ntiles : 0);
+    }
+};
+enum { PP_HEADS = 1, PP_SCAN = 2, PP_ROWS = 4, PP_NEXT = 8 };
+static void partition_pass(const StepRun& r, const Partitions& p, int what) {
+    if (what & PP_HEADS) LAUNCH(r.ctx, "k_win_heads", k_win_heads, p.tgrid, r.s.keys, r.s.key_stride, r.step.npart, r.nsort, r.s.perm, r.un, p.heads, p.carry, p.ntiles);
+    if (what & PP_SCAN) LAUNCH(r.ctx, "k_win_scan", k_win_scan, 1, p.carry, p.ntiles);
+    if (what & PP_ROWS) LAUNCH(r.ctx, "k_wsl_rows", k_wsl_rows, p.tgrid, p.heads, p.carry, r.un, p.rown, p.tfirst, p.ntiles);
+    if (what & PP_NEXT) LAUNCH(r.ctx, "k_wagg_next", k_wagg_next, 1, p.tfirst, r.un, p.tnext, p.ntiles);
+}
+
+// The filter (behind PP_SCAN): the step's rank of every position into `rank`, the positions with rank <= per_limit counted per tile;
+// then, unless every row is kept, the count to the host (a second wait), the ways out again — a filtering call knows its count only
+// here — and the kept positions placed in order.  Leaves r.m and r.sel.
+static int rank_filter(StepRun& r, const Partitions& p, uint32_t* rank, uint32_t* tile_kept, uint32_t* sel) {
+    sdqh_ctx* ctx = r.ctx;
+    const uint64_t pl = (uint64_t)r.step.per_limit;
+    LAUNCH(ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, r.step.rank_kind, pl, rank, tile_kept, p.ntiles);
+    if (r.all_kept) return SDQH_OK;
+    LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)p.ntiles, r.s.info);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, r.s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    unsigned long long kept;
+    std::memcpy(&kept, ctx->result_host, 8);
+    r.m = std::min<int64_t>(r.limit, (int64_t)kept);
+    if (r.count_only || r.m == 0) return r.done(r.m);
+    if (r.m > r.capacity) return r.overflow(r.m);
+    LAUNCH(ctx, "k_win_place", k_win_place, p.tgrid, rank, r.un, pl, tile_kept, p.ntiles, sel, (uint32_t)r.m);
+    r.sel = sel;
+    return SDQH_OK;
+}
+
+// The family steps.  Each carves block 3 (scratch.p[3]: one pool block per call, the partition pass's arrays and its own in one
+// layout), runs the partition pass and its own kernels, and leaves what the emit and the fetch need in the StepRun.
+// Ranks (sdqh_table_window): block 3 = [partition pass | ranks | kept per tile | kept positions | slack].  The emit writes the ranks.
+static int step_ranks(StepRun& r) {
+    Partitions p;
+    uint32_t *rank = nullptr, *tile_kept = nullptr, *sel = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, r.n, false, false, false);
+            rank = c.take<uint32_t>((size_t)r.n);
+            tile_kept = c.take<uint32_t>(p.ntiles);
+            sel = c.take<uint32_t>(r.all_kept ? 0 : (size_t)r.n);
+            (void)c.take<char>(256);
+        })) return r.nomem();
+    partition_pass(r, p, PP_HEADS | PP_SCAN);
+    r.rank = rank;
+    return rank_filter(r, p, rank, tile_kept, sel);
+}
+
+// Aggregates over frames (sdqh_table_window_agg): block 3 = [partition pass | ROWS values | RANGE / PARTITION values | value carries].
+// Every position is kept: row j is sorted position j, the first m values are the output.
+static int step_frames(StepRun& r) {
+    const DevWaggs& ag = r.step.aggs;
+    const size_t na = (size_t)ag.n;
+    bool ends = false;                                                // does some aggregate ask for RANGE or PARTITION?
+    for (size_t a = 0; a < na; ++a) ends |= ag.a[a].frame != SDQH_FRAME_ROWS;
+    Partitions p;
+    uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, r.n, false, true, ends);
+            elem = c.take<uint64_t>(r.stride * na);
+            fin = c.take<uint64_t>(ends ? r.stride * na : 0);
+            tval = c.take<uint64_t>((size_t)p.ntiles * na);
+        })) return r.nomem();
+    partition_pass(r, p, PP_HEADS);
+    LAUNCH(r.ctx, "k_wagg_tiles", k_wagg_tiles, p.tgrid, r.table->stage, ag, r.s.refs, r.s.perm, p.heads, r.un, r.stride, elem, tval, p.tfirst, p.ntiles);
+    LAUNCH(r.ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, p.tfirst, r.un, tval, p.ntiles);
+    LAUNCH(r.ctx, "k_wagg_run", k_wagg_run, p.tgrid, ag, p.heads, r.un, r.stride, elem, tval, p.ntiles);
+    if (ends) {
+        const uint32_t mtiles = (uint32_t)((r.m + SORT_TILE - 1) / SORT_TILE);
+        partition_pass(r, p, PP_NEXT);
+        LAUNCH(r.ctx, "k_wagg_ends", k_wagg_ends, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), ag, p.heads, p.tnext, r.un, (uint32_t)r.m, r.stride, elem, fin, mtiles);
+    }
+    r.columns(elem, ag.n);                                            // each from the array its frame left it in
+    for (int a = 0; a < ag.n; ++a) if (ag.a[a].frame != SDQH_FRAME_ROWS) r.col_src[a] = fin + (size_t)a * r.stride;
+    return SDQH_OK;
+}
+
+// Values over sliding frames (sdqh_table_window_slide): block 3 = [partition pass | partition ends | block-head flags | elements, then
+// suffix folds | prefix folds | values | fold carries | their head flags]
+static int step_slides(StepRun& r) {
+    const int64_t n = r.n;
+    DevWslides sl = r.step.sl;
+    const size_t na = (size_t)sl.n;
+    bool folds = false;                                               // does some slide fold (SUM / MIN / MAX)?
+    for (size_t a = 0; a < na; ++a) {
+        // an offset of n or more reaches outside every partition, whichever it is: clamped, the arithmetic stays far inside 64 bits
+        DevWslide& d = sl.a[a];
+        d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
+        d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
+        d.w = (uint32_t)std::min<int64_t>(d.hi - d.lo + 1, n);
+        folds |= d.g.cls != WSL_NONE;
+    }
+    Partitions p;
+    uint8_t *bh = nullptr, *thead = nullptr; uint32_t* pend = nullptr;
+    uint64_t *elem = nullptr, *pre = nullptr, *fin = nullptr, *tval = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, n, true, true, true);
+            pend = c.take<uint32_t>((size_t)n);
+            bh = c.take<uint8_t>((size_t)n);
+            elem = c.take<uint64_t>(r.stride * na);
+            pre = c.take<uint64_t>(folds ? r.stride * na : 0);
+            fin = c.take<uint64_t>(r.stride * na);
+            tval = c.take<uint64_t>(folds ? (size_t)p.ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
+            thead = c.take<uint8_t>(folds ? (size_t)p.ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
+        })) return r.nomem();
+    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS | PP_NEXT);
+    LAUNCH(r.ctx, "k_wsl_blocks", k_wsl_blocks, p.tgrid, r.table->stage, sl, r.s.refs, r.s.perm, p.heads, p.tnext, p.rown, r.un, r.stride, pend, bh, elem, p.ntiles);
+    if (folds) {
+        LAUNCH(r.ctx, "k_wsl_tiles", k_wsl_tiles, p.tgrid, sl, bh, r.un, r.stride, elem, tval, thead, p.ntiles);
+        LAUNCH(r.ctx, "k_wsl_scan", k_wsl_scan, 2 * SDQH_WSLIDE_MAX_AGGS, sl, thead, tval, p.ntiles);
+        LAUNCH(r.ctx, "k_wsl_run", k_wsl_run, p.tgrid, sl, bh, r.un, r.stride, elem, pre, tval, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wsl_fold", k_wsl_fold, r.row_grid(), sl, p.rown, pend, r.un, (uint32_t)r.m, r.stride, elem, pre, fin);
+    r.columns(fin, sl.n);
+    return SDQH_OK;
+}
+
+// Values over value and group frames (sdqh_table_window_range): block 3 = [partition pass | partition ends | dense ranks | kept per
+// tile | VALUE keys | GROUPS keys | raw elements, an array per FIRST / LAST range | fold trees, one per folded range | values]
+static int step_ranges(StepRun& r) {
+    const int64_t n = r.n;
+    DevWranges rg = r.step.rg;
+    const size_t na = (size_t)rg.n;
+    int nfold = 0, nraw = 0; bool groups = false;                     // folded ranges (SUM / MIN / MAX), FIRST / LAST ranges, any GROUPS range
+    for (size_t a = 0; a < na; ++a) {
+        DevWrange& d = rg.a[a];
+        d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
+        groups |= d.unit == SDQH_WRANGE_GROUPS;
+    }
+    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
+    while (cap < (uint64_t)n) cap <<= 1;
+    const size_t tstride = nfold ? (size_t)(2 * cap) : 0;              // a tree: nodes [1, cap), leaves [cap, 2 cap)
+    Partitions p;
+    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
+    uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, n, true, true, true);
+            pend = c.take<uint32_t>((size_t)n);
+            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
+            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
+            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
+            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+            elem = c.take<uint64_t>(r.stride * (size_t)nraw);
+            tree = c.take<uint64_t>(tstride * (size_t)nfold);
+            fin = c.take<uint64_t>(r.stride * na);
+        })) return r.nomem();
+    if (rg.vcol < 0) vkey = nullptr;
+    if (!groups) { dense = nullptr; gkey = nullptr; }
+    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS | PP_NEXT);
+    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
+    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
+           r.stride, tstride, cap, pend, vkey, gkey, elem, tree, p.ntiles);
+    if (nfold) {
+        LAUNCH(r.ctx, "k_wrg_tiles", k_wrg_tiles, p.tgrid, rg, r.un, tstride, cap, tree, p.ntiles);
+        if (cap > (uint64_t)SORT_TILE) LAUNCH(r.ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wrg_fold", k_wrg_fold, r.row_grid(), rg, p.rown, pend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, elem, tree, fin);
+    r.columns(fin, rg.n);
+    return SDQH_OK;
+}
+
+// Functions of the partition's size (sdqh_table_window_quantile): block 3 = [partition pass | partition ends | tie-run ends | tie-run
+// ranks | kept per tile of that pass | row numbers from 1 | kept per tile | kept positions | measure elements, an array per distinct
+// measure | values] — the tie arrays only with a CUME_DIST / PERCENT_RANK column, the three kept arrays only when per_limit filters,
+// the rest (row numbers, first and next heads among them) only when columns are asked for
+static int step_quantiles(StepRun& r) {
+    const int64_t n = r.n;
+    const DevWquants& q = r.step.q;
+    const bool cols = r.step.out != nullptr;
+    bool need_f = false, need_l = false;                              // does some column read the tie run's first / last position?
+    for (int c = 0; cols && c < q.n; ++c) { need_f |= q.a[c].fn == SDQH_WQ_PERCENT_RANK; need_l |= q.a[c].fn == SDQH_WQ_CUME_DIST; }
+    Partitions p;
+    uint32_t *pend = nullptr, *tend = nullptr, *frank = nullptr, *fkept = nullptr, *rank = nullptr, *tile_kept = nullptr, *sel = nullptr;
+    uint64_t *elem = nullptr, *fin = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, n, cols, cols, cols);
+            pend = c.take<uint32_t>(cols ? (size_t)n : 0);
+            tend = c.take<uint32_t>(need_l ? (size_t)n : 0);
+            frank = c.take<uint32_t>(need_f ? (size_t)n : 0);
+            fkept = c.take<uint32_t>(need_f ? p.ntiles : 0);
+            rank = c.take<uint32_t>(r.all_kept ? 0 : (size_t)n);
+            tile_kept = c.take<uint32_t>(r.all_kept ? 0 : p.ntiles);
+            sel = c.take<uint32_t>(r.all_kept ? 0 : (size_t)n);
+            elem = c.take<uint64_t>(cols ? r.stride * (size_t)q.nslots : 0);
+            fin = c.take<uint64_t>(cols ? r.stride * (size_t)q.n : 0);
+        })) return r.nomem();
+    if (!need_l) tend = nullptr;
+    if (!need_f) frank = nullptr;
+    partition_pass(r, p, PP_HEADS | PP_SCAN);
+    if (!r.all_kept) {                                                // sdqh_table_window's filter on ROW_NUMBER, its ranks the filter's own
+        const int rc = rank_filter(r, p, rank, tile_kept, sel);
+        if (rc || r.ended) return rc;
+    }
+    if (!cols) return SDQH_OK;
+    partition_pass(r, p, PP_ROWS);
+    if (need_l) LAUNCH(r.ctx, "k_wq_ties", k_wq_ties, p.tgrid, p.heads, r.un, p.tfirst, p.ntiles);
+    partition_pass(r, p, PP_NEXT);
+    if (need_f) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_RANK, ~0ull, frank, fkept, p.ntiles);
+    LAUNCH(r.ctx, "k_wq_stage", k_wq_stage, p.tgrid, r.table->stage, q, r.s.refs, r.s.perm, p.heads, p.tnext, r.un, r.stride, pend, tend, elem, p.ntiles);
+    LAUNCH(r.ctx, "k_wq_value", k_wq_value, r.row_grid(), q, r.sel, p.rown, pend, tend, frank, r.un, (uint32_t)r.m, r.stride, elem, fin);
+    r.columns(fin, q.n);
+    return SDQH_OK;
+}
+
+// The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
+// who: the entry point's name in messages.
+static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
+                        int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
     const std::string me(who);
-    int64_t* out_rank = win ? win->out_rank : nullptr;
-    const SortFrames* fr = frames && frames->out ? frames : nullptr;     // (no array for them: rows only, no aggregate pass)
-    const SortSlides* sd = slides && slides->out ? slides : nullptr;     // (likewise)
-    const SortRanges* rr = ranges && ranges->out ? ranges : nullptr;     // (likewise)
-    const bool qv = quants && quants->out;                            // (likewise; the rows may still be filtered)
     Scratch scratch(ctx);
     SortState s;
     if (int rc = sort_select(ctx, table, me, min_hits, nsort, terms, scratch, s)) return rc;      // (a ranks column too short: *out_n untouched)
     const int64_t n = s.n;
-    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !out_rank && !fr && !sd && !rr && !qv;
-    const bool all_kept = (!win || win->per_limit >= n) && (!quants || quants->per_limit >= n);      // a rank is at most n: nothing to filter, the count is known
-    const auto done = [&](int64_t m) { *out_n = m; call_end(ctx); return SDQH_OK; };
-    const auto overflow = [&](int64_t m) { *out_n = m; call_end(ctx); return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); };
-    // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering window knows its count
+    const bool count_only = !out_keys && !out_payload && !out_values && !out_hits && !step.out;
+    const bool all_kept = !step.filters || step.per_limit >= n;      // a rank is at most n: nothing to filter, the count is known
+    StepRun r{ctx, table, me, step, s, scratch, nsort, n, limit, capacity, count_only, all_kept, out_n, (uint32_t)n, round_up((size_t)n * 8) / 8, std::min<int64_t>(limit, n)};
+    // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering call knows its count
     // only after the ranks, so of these it takes the first alone (and leaves *out_n untouched if a later step fails).
-    int64_t m = std::min<int64_t>(limit, n);
-    if (n == 0) return done(0);                                       // nothing selected (limit >= 1: m = 0 means n = 0)
-    if (all_kept && count_only) return done(m);                       // count-only call
-    if (all_kept && m > capacity) return overflow(m);                 // the needed count, nothing written
-    if (!win && !quants) *out_n = m;
+    if (n == 0) return r.done(0);                                     // nothing selected (limit >= 1: m = 0 means n = 0)
+    if (all_kept && count_only) return r.done(r.m);                   // count-only call
+    if (all_kept && r.m > capacity) return r.overflow(r.m);           // the needed count, nothing written
+    if (!step.filters) *out_n = r.m;
     if (int rc = sort_passes(ctx, me, nsort, scratch, s)) return rc;
-    const uint32_t un = (uint32_t)n;
-    uint32_t *rank = nullptr, *sel = nullptr;
-    const size_t agg_stride = round_up((size_t)n * 8) / 8;           // aggregate a's values start at a * agg_stride
-    static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
-                  "one list of result arrays serves frames, slides, ranges and quantiles");
-    const uint64_t* agg_src[SDQH_WAGG_MAX_AGGS] = {nullptr, nullptr, nullptr, nullptr};      // where each aggregate's / slide's values lie once the passes ran
-    int64_t* agg_out = nullptr; int agg_n = 0;                        // ... and the caller's array for them: agg_out[a * capacity + j]
-    if (sd) {
-        // block 3: [heads | tile carries | row numbers | partition ends | block-head flags | elements, then suffix folds | prefix folds |
-        // values | fold carries | their head flags | first heads per tile | next heads per tile]
-        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-        DevWslides sl = sd->sl;
-        const size_t na = (size_t)sl.n;
-        bool folds = false;                                           // does some slide fold (SUM / MIN / MAX)?
-        for (size_t a = 0; a < na; ++a) {
-            // an offset of n or more reaches outside every partition, whichever it is: clamped, the arithmetic stays far inside 64 bits
-            DevWslide& d = sl.a[a];
-            d.lo = std::max<int64_t>(std::min<int64_t>(sd->lo[a], n), -n);
-            d.hi = std::max<int64_t>(std::min<int64_t>(sd->hi[a], n), -n);
-            d.w = (uint32_t)std::min<int64_t>(d.hi - d.lo + 1, n);
-            folds |= d.g.cls != WSL_NONE;
-        }
-        uint8_t *heads = nullptr, *bh = nullptr, *thead = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr;
-        uint64_t *elem = nullptr, *pre = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
-        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
-                heads = c.take<uint8_t>((size_t)n);
-                carry = c.take<WinCarry>(ntiles);
-                rown = c.take<uint32_t>((size_t)n);
-                pend = c.take<uint32_t>((size_t)n);
-                bh = c.take<uint8_t>((size_t)n);
-                elem = c.take<uint64_t>(agg_stride * na);
-                pre = c.take<uint64_t>(folds ? agg_stride * na : 0);
-                fin = c.take<uint64_t>(agg_stride * na);
-                tval = c.take<uint64_t>(folds ? (size_t)ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
-                thead = c.take<uint8_t>(folds ? (size_t)ntiles * 2 * SDQH_WSLIDE_MAX_AGGS : 0);
-                tfirst = c.take<WaggHeads>(ntiles);
-                tnext = c.take<WaggHeads>(ntiles);
-            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, sd->npart, nsort, s.perm, un, heads, carry, ntiles);
-        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-        LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
-        LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
-        LAUNCH(ctx, "k_wsl_blocks", k_wsl_blocks, tgrid, table->stage, sl, s.refs, s.perm, heads, tnext, rown, un, agg_stride, pend, bh, elem, ntiles);
-        if (folds) {
-            LAUNCH(ctx, "k_wsl_tiles", k_wsl_tiles, tgrid, sl, bh, un, agg_stride, elem, tval, thead, ntiles);
-            LAUNCH(ctx, "k_wsl_scan", k_wsl_scan, 2 * SDQH_WSLIDE_MAX_AGGS, sl, thead, tval, ntiles);
-            LAUNCH(ctx, "k_wsl_run", k_wsl_run, tgrid, sl, bh, un, agg_stride, elem, pre, tval, ntiles);
-        }
-        const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-        LAUNCH(ctx, "k_wsl_fold", k_wsl_fold, fgrid, sl, rown, pend, un, (uint32_t)m, agg_stride, elem, pre, fin);
-        agg_out = sd->out; agg_n = sl.n;
-        for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
+    // the step.  Columns nobody gave an array for are not computed (rows only; quantiles may still filter them); ranks are, as they
+    // always were, even where every row is kept and no rank column is asked for
+    int step_rc = SDQH_OK;
+    switch (step.kind) {
+        case STEP_NONE: break;
+        case STEP_RANKS: step_rc = step_ranks(r); break;
+        case STEP_FRAMES: if (step.out) step_rc = step_frames(r); break;
+        case STEP_SLIDES: if (step.out) step_rc = step_slides(r); break;
+        case STEP_RANGES: if (step.out) step_rc = step_ranges(r); break;
+        case STEP_QUANTILES: if (step.out || !all_kept) step_rc = step_quantiles(r); break;
     }
-    if (rr) {
-        // block 3: [heads | tile carries | row numbers | partition ends | dense ranks | kept per tile | VALUE keys | GROUPS keys | raw
-        // elements, an array per FIRST / LAST range | fold trees, one per folded range | values | first heads per tile | next heads per tile]
-        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-        DevWranges rg = rr->rg;
-        const size_t na = (size_t)rg.n;
-        int nfold = 0, nraw = 0; bool groups = false;                   // folded ranges (SUM / MIN / MAX), FIRST / LAST ranges, any GROUPS range
-        for (size_t a = 0; a < na; ++a) {
-            DevWrange& d = rg.a[a];
-            d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
-            groups |= d.unit == SDQH_WRANGE_GROUPS;
-        }
-        uint64_t cap = SORT_TILE;                                      // the trees' leaf count: the power of two at or above n
-        while (cap < (uint64_t)n) cap <<= 1;
-        const size_t tstride = nfold ? (size_t)(2 * cap) : 0;          // a tree: nodes [1, cap), leaves [cap, 2 cap)
-        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
-        uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
-        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
-                heads = c.take<uint8_t>((size_t)n);
-                carry = c.take<WinCarry>(ntiles);
-                rown = c.take<uint32_t>((size_t)n);
-                pend = c.take<uint32_t>((size_t)n);
-                dense = c.take<uint32_t>(groups ? (size_t)n : 0);
-                tile_kept = c.take<uint32_t>(groups ? ntiles : 0);
-                vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
-                gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
-                elem = c.take<uint64_t>(agg_stride * (size_t)nraw);
-                tree = c.take<uint64_t>(tstride * (size_t)nfold);
-                fin = c.take<uint64_t>(agg_stride * na);
-                tfirst = c.take<WaggHeads>(ntiles);
-                tnext = c.take<WaggHeads>(ntiles);
-            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        if (rg.vcol < 0) vkey = nullptr;
-        if (!groups) { dense = nullptr; gkey = nullptr; }
-        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, rr->npart, nsort, s.perm, un, heads, carry, ntiles);
-        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-        LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
-        LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
-        if (groups) LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, ntiles);
-        LAUNCH(ctx, "k_wrg_stage", k_wrg_stage, tgrid, table->stage, rg, s.refs, s.perm, heads, tnext, rg.vcol >= 0 ? s.keys + (size_t)rg.vcol * s.key_stride : nullptr, dense, un,
-               agg_stride, tstride, cap, pend, vkey, gkey, elem, tree, ntiles);
-        if (nfold) {
-            LAUNCH(ctx, "k_wrg_tiles", k_wrg_tiles, tgrid, rg, un, tstride, cap, tree, ntiles);
-            if (cap > (uint64_t)SORT_TILE) LAUNCH(ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, ntiles);
-        }
-        const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-        LAUNCH(ctx, "k_wrg_fold", k_wrg_fold, fgrid, rg, rown, pend, vkey, gkey, un, (uint32_t)m, agg_stride, tstride, cap, elem, tree, fin);
-        agg_out = rr->out; agg_n = rg.n;
-        for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
-    }
-    if (quants && (qv || !all_kept)) {
-        // block 3: [heads | tile carries | row numbers | partition ends | tie-run ends | tie-run ranks | kept per tile of that pass | row
-        // numbers from 1 | kept per tile | kept positions | measure elements, an array per distinct measure | values | first heads per
-        // tile | next heads per tile] — the tie arrays only with a CUME_DIST / PERCENT_RANK column, the three kept arrays only when
-        // per_limit filters, the rest only when values are asked for
-        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-        const DevWquants& q = quants->q;
-        bool need_f = false, need_l = false;                            // does some column read the tie run's first / last position?
-        for (int c = 0; qv && c < q.n; ++c) { need_f |= q.a[c].fn == SDQH_WQ_PERCENT_RANK; need_l |= q.a[c].fn == SDQH_WQ_CUME_DIST; }
-        const size_t nv = qv ? (size_t)n : 0, nt = qv ? ntiles : 0;
-        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t *rown = nullptr, *pend = nullptr, *tend = nullptr, *frank = nullptr, *fkept = nullptr, *tile_kept = nullptr;
-        uint64_t *elem = nullptr, *fin = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
-        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
-                heads = c.take<uint8_t>((size_t)n);
-                carry = c.take<WinCarry>(ntiles);
-                rown = c.take<uint32_t>(nv);
-                pend = c.take<uint32_t>(nv);
-                tend = c.take<uint32_t>(need_l ? (size_t)n : 0);
-                frank = c.take<uint32_t>(need_f ? (size_t)n : 0);
-                fkept = c.take<uint32_t>(need_f ? ntiles : 0);
-                rank = c.take<uint32_t>(all_kept ? 0 : (size_t)n);
-                tile_kept = c.take<uint32_t>(all_kept ? 0 : ntiles);
-                sel = c.take<uint32_t>(all_kept ? 0 : (size_t)n);
-                elem = c.take<uint64_t>(qv ? agg_stride * (size_t)q.nslots : 0);
-                fin = c.take<uint64_t>(qv ? agg_stride * (size_t)q.n : 0);
-                tfirst = c.take<WaggHeads>(nt);
-                tnext = c.take<WaggHeads>(nt);
-            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        if (!need_l) tend = nullptr;
-        if (!need_f) frank = nullptr;
-        if (all_kept) { rank = nullptr; sel = nullptr; }
-        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, quants->npart, nsort, s.perm, un, heads, carry, ntiles);
-        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-        if (!all_kept) {                                              // sdqh_table_window's ROW_NUMBER filter: counted, the ways out again, then placed
-            const uint64_t pl = (uint64_t)quants->per_limit;
-            LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_ROW_NUMBER, pl, rank, tile_kept, ntiles);
-            LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-            if (int rc = sync_stream(ctx)) return rc;
-            unsigned long long kept;
-            std::memcpy(&kept, ctx->result_host, 8);
-            m = std::min<int64_t>(limit, (int64_t)kept);
-            if (count_only || m == 0) return done(m);
-            if (m > capacity) return overflow(m);
-            LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
-        }
-        if (qv) {
-            LAUNCH(ctx, "k_wsl_rows", k_wsl_rows, tgrid, heads, carry, un, rown, tfirst, ntiles);
-            if (need_l) LAUNCH(ctx, "k_wq_ties", k_wq_ties, tgrid, heads, un, tfirst, ntiles);
-            LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
-            if (need_f) LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, (int)SDQH_WIN_RANK, ~0ull, frank, fkept, ntiles);
-            LAUNCH(ctx, "k_wq_stage", k_wq_stage, tgrid, table->stage, q, s.refs, s.perm, heads, tnext, un, agg_stride, pend, tend, elem, ntiles);
-            const unsigned fgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-            LAUNCH(ctx, "k_wq_value", k_wq_value, fgrid, q, sel, rown, pend, tend, frank, un, (uint32_t)m, agg_stride, elem, fin);
-            agg_out = quants->out; agg_n = q.n;
-            for (int a = 0; a < agg_n; ++a) agg_src[a] = fin + (size_t)a * agg_stride;
-        }
-        rank = nullptr;                                               // (no rank column is emitted)
-    }
-    if (win || fr) {
-        // block 3: [heads | tile carries | ranks | kept per tile | kept positions | slack] for a window, [heads | tile carries |
-        // ROWS values | RANGE / PARTITION values | value carries | first heads per tile | next heads per tile] for frames
-        const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
-        const size_t na = fr ? (size_t)fr->aggs.n : 0;
-        bool ends = false;                                            // does some aggregate ask for RANGE or PARTITION?
-        for (size_t a = 0; a < na; ++a) ends |= fr->aggs.a[a].frame != SDQH_FRAME_ROWS;
-        uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t* tile_kept = nullptr;
-        uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
-        if (!carve(ctx, scratch.p[3], [&](Carver& c) {
-                heads = c.take<uint8_t>((size_t)n);
-                carry = c.take<WinCarry>(ntiles);
-                if (win) {
-                    rank = c.take<uint32_t>((size_t)n);
-                    tile_kept = c.take<uint32_t>(ntiles);
-                    sel = all_kept ? nullptr : c.take<uint32_t>((size_t)n);
-                    (void)c.take<char>(256);
-                }
-                if (fr) {
-                    elem = c.take<uint64_t>(agg_stride * na);
-                    fin = c.take<uint64_t>(ends ? agg_stride * na : 0);
-                    tval = c.take<uint64_t>((size_t)ntiles * na);
-                    tfirst = c.take<WaggHeads>(ntiles);
-                    tnext = c.take<WaggHeads>(ends ? ntiles : 0);
-                }
-            })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
-        const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-        LAUNCH(ctx, "k_win_heads", k_win_heads, tgrid, s.keys, s.key_stride, win ? win->npart : fr->npart, nsort, s.perm, un, heads, carry, ntiles);
-        if (fr) {                                                     // every position is kept: row j is sorted position j, the first m values are the output
-            LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, table->stage, fr->aggs, s.refs, s.perm, heads, un, agg_stride, elem, tval, tfirst, ntiles);
-            LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, fr->aggs, tfirst, un, tval, ntiles);
-            LAUNCH(ctx, "k_wagg_run", k_wagg_run, tgrid, fr->aggs, heads, un, agg_stride, elem, tval, ntiles);
-            if (ends) {
-                const uint32_t mtiles = (uint32_t)((m + SORT_TILE - 1) / SORT_TILE);
-                LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, un, tnext, ntiles);
-                LAUNCH(ctx, "k_wagg_ends", k_wagg_ends, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), fr->aggs, heads, tnext, un, (uint32_t)m, agg_stride, elem, fin, mtiles);
-            }
-            agg_out = fr->out; agg_n = fr->aggs.n;                     // each from the array its frame left it in
-            for (int a = 0; a < agg_n; ++a) agg_src[a] = (fr->aggs.a[a].frame == SDQH_FRAME_ROWS ? elem : fin) + (size_t)a * agg_stride;
-        }
-        if (win) {
-            const uint64_t pl = (uint64_t)win->per_limit;
-            LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carry, ntiles);
-            LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, heads, carry, un, win->kind, pl, rank, tile_kept, ntiles);
-            if (!all_kept) {                                          // the kept positions counted, the ways out again, then placed
-                LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_kept, (int)ntiles, s.info);
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, s.info, 8, hipMemcpyDeviceToHost, ctx->stream));
-                if (int rc = sync_stream(ctx)) return rc;
-                unsigned long long kept;
-                std::memcpy(&kept, ctx->result_host, 8);
-                m = std::min<int64_t>(limit, (int64_t)kept);
-                if (count_only || m == 0) return done(m);
-                if (m > capacity) return overflow(m);
-                LAUNCH(ctx, "k_win_place", k_win_place, tgrid, rank, un, pl, tile_kept, ntiles, sel, (uint32_t)m);
-            }
-        }
-    }
+    if (step_rc || r.ended) return step_rc;
+    const int64_t m = r.m;
+    int64_t* out_rank = r.rank ? step.out : nullptr;                  // (step.out is the rank column or, with r.ncols, the columns)
     *out_n = m;
     // emit: m rows (>= 1) of the arrays asked for; none if only columns the table does not have were
-    SortRows r;
-    if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, out_rank != nullptr, scratch, r)) return rc;
-    if (r.narr) {
-        const unsigned egrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-        LAUNCH(ctx, "k_sort_emit", k_sort_emit, egrid, table->stage, s.refs, s.perm, sel, rank, un, (uint32_t)m, r.o, r.extra);
-    }
+    SortRows rows;
+    if (int rc = sort_rows_alloc(ctx, table, me, m, out_keys != nullptr, out_payload != nullptr, out_values != nullptr, out_hits != nullptr, out_rank != nullptr, scratch, rows)) return rc;
+    if (rows.narr) LAUNCH(ctx, "k_sort_emit", k_sort_emit, r.row_grid(), table->stage, s.refs, s.perm, r.sel, r.rank, r.un, (uint32_t)m, rows.o, rows.extra);
     call_end(ctx);                                                    // the call's device time ends here: the fetch is the host's
-    if (agg_n) {                                                      // the aggregates' or slides' first m values
-        for (int a = 0; a < agg_n; ++a)
-            HIP_TRY(ctx, hipMemcpyAsync(agg_out + (size_t)a * (size_t)capacity, agg_src[a], (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (!r.narr) if (int rc = sync_stream(ctx)) return rc;
+    if (r.ncols) {                                                    // the columns' first m values
+        for (int a = 0; a < r.ncols; ++a)
+            HIP_TRY(ctx, hipMemcpyAsync(step.out + (size_t)a * (size_t)capacity, r.col_src[a], (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        if (!rows.narr) if (int rc = sync_stream(ctx)) return rc;
     }
-    if (r.narr) if (int rc = sort_rows_fetch(ctx, r, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
-    if (out_values) for (int v = r.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, r.nb);
+    if (rows.narr) if (int rc = sort_rows_fetch(ctx, rows, capacity, out_keys, out_payload, out_values, out_hits, out_rank)) return rc;
+    if (out_values) for (int v = rows.nval; v < SDQH_TUPLE_MAX_VALUES; ++v) std::memset(out_values + (size_t)v * (size_t)capacity, 0, rows.nb);
     return SDQH_OK;
 }
 
@@ -1741,6 +1773,8 @@ static bool sort_column_ok(const sdqh_table* table, int kind, int index) {
     return (kind == SDQH_SORT_KEY) || (kind == SDQH_SORT_PAYLOAD && index >= 0 && index < table->npay) ||
            (kind == SDQH_SORT_VALUE && index >= 0 && index < nv) || (kind == SDQH_SORT_HITS && table->accumulate);
 }
+// is a column of `kind` read as doubles?  Values are, keys and hit counts are not, a payload column is what the caller says
+static int column_is_f64(int kind, int is_f64) { return kind == SDQH_SORT_VALUE ? 1 : (kind == SDQH_SORT_PAYLOAD ? (is_f64 ? 1 : 0) : 0); }
 
 // the terms of an entry point checked and marshalled; SDQH_OK or the failed call's code.  plain: sdqh_table_sorted's keys (terms
 // with no derivation), named "sort key" in its one message
@@ -1752,7 +1786,7 @@ static int sort_terms_set(sdqh_ctx* ctx, const sdqh_table* table, const std::str
         if (!sort_column_ok(table, t.kind, t.index)) return fail(ctx, SDQH_ERR_INVALID, (plain ? me + ": sort key" : term) + " names a field the table does not have");
         DevSortKey& k = terms[i].sk;
         k.kind = t.kind; k.index = t.index; k.desc = t.descending ? 1 : 0;
-        k.is_f64 = t.kind == SDQH_SORT_VALUE ? 1 : (t.kind == SDQH_SORT_PAYLOAD ? (t.is_f64 ? 1 : 0) : 0);
+        k.is_f64 = column_is_f64(t.kind, t.is_f64);
         if (t.div < 0 || t.mod < 0) return fail(ctx, SDQH_ERR_INVALID, term + " has a negative divisor or modulus");
         if (t.ranks && (t.ranks->dtype != SDQH_I64 || !t.ranks->data)) return fail(ctx, SDQH_ERR_INVALID, term + ": ranks must be an I64 column");
         terms[i].div = (uint64_t)t.div; terms[i].mod = (uint64_t)t.mod; terms[i].add = t.add;
@@ -1763,7 +1797,7 @@ static int sort_terms_set(sdqh_ctx* ctx, const sdqh_table* table, const std::str
     return SDQH_OK;
 }
 
-// what the three entry points check before they look at their terms; ok: the entry point's own conditions on its arguments
+// what every entry point checks before it looks at its terms; ok: the entry point's own conditions on its arguments
 static int sort_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, bool ok) {
     const std::string me(who);
     if (!ctx || !table || !ok) return fail(ctx, SDQH_ERR_INVALID, me + ": bad arguments");
@@ -1775,6 +1809,29 @@ static int sort_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, b
 static bool sort_args_ok(const void* terms, int nterms, int64_t limit, int64_t capacity, const int64_t* out_n) {
     return out_n && terms && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && limit >= 1 && capacity >= 0;
 }
+// ... and what the five window entry points do before they look at their columns: the arguments they share tested with `own` (the
+// entry point's conditions on the rest), sort_enter, the terms marshalled
+static int window_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, int npartition, int nterms, const sdqh_sort_term* in, int64_t limit, int64_t capacity,
+                        const int64_t* out_n, bool own, DevSortTerm* terms) {
+    const bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && own;
+    if (int rc = sort_enter(ctx, table, who, ok)) return rc;
+    return sort_terms_set(ctx, table, who, nterms, in, false, terms);
+}
+
+// the measure of column i of a window entry point (noun: what it calls its columns in messages), checked and stored; desc is unused
+static int measure_set(sdqh_ctx* ctx, const sdqh_table* table, const char* who, const char* noun, int i, int kind, int index, int is_f64, DevSortKey& sk) {
+    const std::string col = std::string(who) + ": " + noun + " " + std::to_string(i);
+    if (!sort_column_ok(table, kind, index)) return fail(ctx, SDQH_ERR_INVALID, col + " names a field the table does not have");
+    if (is_f64 && (kind == SDQH_SORT_KEY || kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, col + ": keys and hit counts are integers");
+    sk.kind = kind; sk.index = index; sk.is_f64 = column_is_f64(kind, is_f64);
+    return SDQH_OK;
+}
+// how an op's elements fold.  folding_ops_only (frames: SUM / COUNT / MIN / MAX, COUNT a sum of ones); else COUNT, FIRST and LAST fold nothing
+static int fold_class(int op, int is_f64, bool folding_ops_only) {
+    if (op == SDQH_WAGG_MIN || op == SDQH_WAGG_MAX) return WAGG_UMAX;
+    if (op != SDQH_WAGG_SUM) return folding_ops_only ? WAGG_ADD_I : WSL_NONE;
+    return is_f64 ? WAGG_ADD_F : WAGG_ADD_I;
+}
 
 int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
                       int64_t capacity, int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_n) {
@@ -1783,7 +1840,7 @@ int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, 
     for (int i = 0; i < nsort; ++i) { in[i].kind = sort[i].kind; in[i].index = sort[i].index; in[i].descending = sort[i].descending; in[i].is_f64 = sort[i].is_f64; }
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted", nsort, in, true, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, nullptr, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted", min_hits, limit, nsort, terms, sort_step(STEP_NONE, 0, nullptr), capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nterms, const sdqh_sort_term* in,
@@ -1791,79 +1848,69 @@ int sdqh_table_sorted_by(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hit
     if (int rc = sort_enter(ctx, table, "table_sorted_by", sort_args_ok(in, nterms, limit, capacity, out_n))) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = sort_terms_set(ctx, table, "table_sorted_by", nterms, in, false, terms)) return rc;
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_sorted_by", min_hits, limit, nterms, terms, sort_step(STEP_NONE, 0, nullptr), capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                       int kind, int64_t per_limit, int64_t limit, int64_t capacity,
                       int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_rank, int64_t* out_n) {
-    const bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && per_limit >= 1 &&
-                    (kind == SDQH_WIN_ROW_NUMBER || kind == SDQH_WIN_RANK || kind == SDQH_WIN_DENSE_RANK);
-    if (int rc = sort_enter(ctx, table, "table_window", ok)) return rc;
+    const char* who = "table_window";
+    const bool ok = per_limit >= 1 && (kind == SDQH_WIN_ROW_NUMBER || kind == SDQH_WIN_RANK || kind == SDQH_WIN_DENSE_RANK);
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
-    if (int rc = sort_terms_set(ctx, table, "table_window", nterms, in, false, terms)) return rc;
-    const SortWindow win = {npartition, kind, per_limit, out_rank};
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window", min_hits, limit, nterms, terms, &win, nullptr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_RANKS, npartition, out_rank);
+    st.filters = true; st.rank_kind = kind; st.per_limit = per_limit;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_agg(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                           int naggs, const sdqh_window_agg* aggs, int64_t limit, int64_t capacity,
                           int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
-    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && aggs && naggs >= 1 && naggs <= SDQH_WAGG_MAX_AGGS;
+    const char* who = "table_window_agg";
+    bool ok = aggs && naggs >= 1 && naggs <= SDQH_WAGG_MAX_AGGS;
     for (int a = 0; ok && a < naggs; ++a)
         ok = aggs[a].op >= SDQH_WAGG_SUM && aggs[a].op <= SDQH_WAGG_MAX && aggs[a].frame >= SDQH_FRAME_ROWS && aggs[a].frame <= SDQH_FRAME_PARTITION;
-    if (int rc = sort_enter(ctx, table, "table_window_agg", ok)) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
-    if (int rc = sort_terms_set(ctx, table, "table_window_agg", nterms, in, false, terms)) return rc;
-    SortFrames fr; std::memset(&fr, 0, sizeof(fr));
-    fr.npart = npartition; fr.out = out_aggs; fr.aggs.n = naggs;
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_FRAMES, npartition, out_aggs);
+    st.aggs.n = naggs;
     for (int a = 0; a < naggs; ++a) {
         const sdqh_window_agg& g = aggs[a];
-        DevWagg& d = fr.aggs.a[a];
+        DevWagg& d = st.aggs.a[a];
         d.op = g.op; d.frame = g.frame;
-        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
-            const std::string agg = "table_window_agg: aggregate " + std::to_string(a);
-            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
-            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
-            d.sk.kind = g.kind; d.sk.index = g.index;
-            d.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
-        }
-        d.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op == SDQH_WAGG_SUM && d.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I);
+        if (g.op != SDQH_WAGG_COUNT)                                  // (COUNT ignores its measure)
+            if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind, g.index, g.is_f64, d.sk)) return rc;
+        d.cls = fold_class(g.op, d.sk.is_f64, true);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_agg", min_hits, limit, nterms, terms, nullptr, &fr, nullptr, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_slide(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                             int nslides, const sdqh_window_slide* slides, int64_t limit, int64_t capacity,
                             int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
-    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && slides && nslides >= 1 && nslides <= SDQH_WSLIDE_MAX_AGGS;
+    const char* who = "table_window_slide";
+    bool ok = slides && nslides >= 1 && nslides <= SDQH_WSLIDE_MAX_AGGS;
     for (int a = 0; ok && a < nslides; ++a) ok = slides[a].op >= SDQH_WAGG_SUM && slides[a].op <= SDQH_WSLIDE_LAST && slides[a].lo <= slides[a].hi;
-    if (int rc = sort_enter(ctx, table, "table_window_slide", ok)) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
-    if (int rc = sort_terms_set(ctx, table, "table_window_slide", nterms, in, false, terms)) return rc;
-    SortSlides sd; std::memset(&sd, 0, sizeof(sd));
-    sd.npart = npartition; sd.out = out_aggs; sd.sl.n = nslides;
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_SLIDES, npartition, out_aggs);
+    st.sl.n = nslides;
     for (int a = 0; a < nslides; ++a) {
         const sdqh_window_slide& g = slides[a];
-        DevWslide& d = sd.sl.a[a];
-        d.g.op = g.op; d.empty = (uint64_t)g.empty; d.w = 1u;
-        sd.lo[a] = g.lo; sd.hi[a] = g.hi;
-        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
-            const std::string agg = "table_window_slide: slide " + std::to_string(a);
-            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
-            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
-            d.g.sk.kind = g.kind; d.g.sk.index = g.index;
-            d.g.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
-        }
-        d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
+        DevWslide& d = st.sl.a[a];
+        d.g.op = g.op; d.empty = (uint64_t)g.empty; d.w = 1u; d.lo = g.lo; d.hi = g.hi;
+        if (g.op != SDQH_WAGG_COUNT)                                  // (COUNT ignores its measure)
+            if (int rc = measure_set(ctx, table, who, "slide", a, g.kind, g.index, g.is_f64, d.g.sk)) return rc;
+        d.g.cls = fold_class(g.op, d.g.sk.is_f64, false);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_slide", min_hits, limit, nterms, terms, nullptr, nullptr, &sd, nullptr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                             int nranges, const sdqh_window_range* ranges, int64_t limit, int64_t capacity,
                             int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
-    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && ranges && nranges >= 1 && nranges <= SDQH_WRANGE_MAX_AGGS;
+    const char* who = "table_window_range";
+    bool ok = ranges && nranges >= 1 && nranges <= SDQH_WRANGE_MAX_AGGS;
     bool value = false;
     for (int a = 0; ok && a < nranges; ++a) {
         const sdqh_window_range& g = ranges[a];
@@ -1872,9 +1919,9 @@ int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
         value |= ok && g.unit == SDQH_WRANGE_VALUE;
     }
     bool vf64 = false;
-    if (ok && value) {                                                // exactly one ORDER BY term, and one with arithmetic
-        ok = nterms == npartition + 1 && in[npartition].ranks == nullptr;
-        if (ok) vf64 = in[npartition].kind == SDQH_SORT_VALUE || (in[npartition].kind == SDQH_SORT_PAYLOAD && in[npartition].is_f64);
+    if (ok && value) {                                                // exactly one ORDER BY term (read here, so: is it there?), and one with arithmetic
+        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
+        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
     }
     for (int a = 0; ok && a < nranges; ++a) {
         const sdqh_window_range& g = ranges[a];
@@ -1885,32 +1932,27 @@ int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
             ok = lo_ok && hi_ok && !(both && lo > hi);
         } else ok = !(both && g.lo > g.hi);
     }
-    if (int rc = sort_enter(ctx, table, "table_window_range", ok)) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
-    if (int rc = sort_terms_set(ctx, table, "table_window_range", nterms, in, false, terms)) return rc;
-    SortRanges sr; std::memset(&sr, 0, sizeof(sr));
-    sr.npart = npartition; sr.out = out_aggs; sr.rg.n = nranges;
-    sr.rg.vcol = value ? npartition : -1; sr.rg.vdesc = value ? terms[npartition].sk.desc : 0; sr.rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_RANGES, npartition, out_aggs);
+    st.rg.n = nranges;
+    st.rg.vcol = value ? npartition : -1; st.rg.vdesc = value ? terms[npartition].sk.desc : 0; st.rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
     for (int a = 0; a < nranges; ++a) {
         const sdqh_window_range& g = ranges[a];
-        DevWrange& d = sr.rg.a[a];
+        DevWrange& d = st.rg.a[a];
         d.g.op = g.op; d.empty = (uint64_t)g.empty; d.unit = g.unit; d.flags = g.flags; d.lo = g.lo; d.hi = g.hi;
-        if (g.op != SDQH_WAGG_COUNT) {                                // (COUNT ignores its measure)
-            const std::string agg = "table_window_range: range " + std::to_string(a);
-            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, agg + " names a field the table does not have");
-            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, agg + ": keys and hit counts are integers");
-            d.g.sk.kind = g.kind; d.g.sk.index = g.index;
-            d.g.sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
-        }
-        d.g.cls = g.op == SDQH_WAGG_MIN || g.op == SDQH_WAGG_MAX ? WAGG_UMAX : (g.op != SDQH_WAGG_SUM ? WSL_NONE : (d.g.sk.is_f64 ? WAGG_ADD_F : WAGG_ADD_I));
+        if (g.op != SDQH_WAGG_COUNT)                                  // (COUNT ignores its measure)
+            if (int rc = measure_set(ctx, table, who, "range", a, g.kind, g.index, g.is_f64, d.g.sk)) return rc;
+        d.g.cls = fold_class(g.op, d.g.sk.is_f64, false);
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_range", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, &sr, nullptr, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
 int sdqh_table_window_quantile(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                                int ncols, const sdqh_window_quantile* cols, int64_t per_limit, int64_t limit, int64_t capacity,
                                int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
-    bool ok = sort_args_ok(in, nterms, limit, capacity, out_n) && npartition >= 0 && npartition <= nterms && per_limit >= 1 && cols && ncols >= 1 && ncols <= SDQH_WQUANT_MAX_COLS;
+    const char* who = "table_window_quantile";
+    bool ok = per_limit >= 1 && cols && ncols >= 1 && ncols <= SDQH_WQUANT_MAX_COLS;
     for (int c = 0; ok && c < ncols; ++c) {
         const sdqh_window_quantile& g = cols[c];
         ok = g.fn >= SDQH_WQ_NTILE && g.fn <= SDQH_WQ_PERCENTILE_CONT;
@@ -1918,61 +1960,43 @@ int sdqh_table_window_quantile(sdqh_ctx* ctx, const sdqh_table* table, int64_t m
         if (g.fn == SDQH_WQ_NTH) ok = ok && g.arg != 0;
         if (g.fn == SDQH_WQ_PERCENTILE_DISC || g.fn == SDQH_WQ_PERCENTILE_CONT) ok = ok && g.p >= 0.0 && g.p <= 1.0;      // (a NaN fails both)
     }
-    if (int rc = sort_enter(ctx, table, "table_window_quantile", ok)) return rc;
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
-    if (int rc = sort_terms_set(ctx, table, "table_window_quantile", nterms, in, false, terms)) return rc;
-    SortQuantiles sq; std::memset(&sq, 0, sizeof(sq));
-    sq.npart = npartition; sq.per_limit = per_limit; sq.out = out_cols; sq.q.n = ncols;
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_QUANTILES, npartition, out_cols);
+    st.filters = true; st.per_limit = per_limit;                      // (on the row number, as sort_step leaves it)
+    DevWquants& q = st.q;
+    q.n = ncols;
     for (int c = 0; c < ncols; ++c) {
         const sdqh_window_quantile& g = cols[c];
-        DevWquant& d = sq.q.a[c];
+        DevWquant& d = q.a[c];
         d.fn = g.fn; d.arg = g.arg; d.p = g.p; d.empty = (uint64_t)g.empty; d.slot = -1;
         if (g.fn >= SDQH_WQ_NTH) {                                    // (the others have no measure)
-            const std::string col = "table_window_quantile: column " + std::to_string(c);
-            if (!sort_column_ok(table, g.kind, g.index)) return fail(ctx, SDQH_ERR_INVALID, col + " names a field the table does not have");
-            if (g.is_f64 && (g.kind == SDQH_SORT_KEY || g.kind == SDQH_SORT_HITS)) return fail(ctx, SDQH_ERR_INVALID, col + ": keys and hit counts are integers");
             DevSortKey sk; std::memset(&sk, 0, sizeof(sk));
-            sk.kind = g.kind; sk.index = g.index;
-            sk.is_f64 = g.kind == SDQH_SORT_VALUE ? 1 : (g.kind == SDQH_SORT_PAYLOAD ? (g.is_f64 ? 1 : 0) : 0);
+            if (int rc = measure_set(ctx, table, who, "column", c, g.kind, g.index, g.is_f64, sk)) return rc;
             d.is_f64 = sk.is_f64;
             int k = 0;                                                // the measure's element array: shared with an earlier column of the same measure
-            while (k < sq.q.nslots && !(sq.q.slot[k].kind == sk.kind && sq.q.slot[k].index == sk.index && sq.q.slot[k].is_f64 == sk.is_f64)) ++k;
-            if (k == sq.q.nslots) sq.q.slot[sq.q.nslots++] = sk;
+            while (k < q.nslots && !(q.slot[k].kind == sk.kind && q.slot[k].index == sk.index && q.slot[k].is_f64 == sk.is_f64)) ++k;
+            if (k == q.nslots) q.slot[q.nslots++] = sk;
             d.slot = k;
         }
     }
-    return ordered_impl(ctx, const_cast<sdqh_table*>(table), "table_window_quantile", min_hits, limit, nterms, terms, nullptr, nullptr, nullptr, nullptr, &sq, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
-int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
-    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_quantile_geometry: bad arguments");
+
+// what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
+// a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
+static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, bool has_narrow, int64_t* narrow_max_width) {
+    if (!ctx || !tile_rows || (has_narrow && !narrow_max_width)) return fail(ctx, SDQH_ERR_INVALID, std::string(who) + ": bad arguments");
     *tile_rows = SORT_TILE;
+    if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
-
-int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {
-    if (!ctx || !tile_rows || !narrow_max_width) return fail(ctx, SDQH_ERR_INVALID, "window_range_geometry: bad arguments");
-    *tile_rows = SORT_TILE; *narrow_max_width = 0;                    // no kernel walks a frame row by row: two searches and a tree query
-    return SDQH_OK;
-}
-
-int sdqh_window_slide_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) {
-    if (!ctx || !tile_rows || !narrow_max_width) return fail(ctx, SDQH_ERR_INVALID, "window_slide_geometry: bad arguments");
-    *tile_rows = SORT_TILE; *narrow_max_width = 0;                    // no kernel walks a frame row by row
-    return SDQH_OK;
-}
-
-int sdqh_window_agg_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
-    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_agg_geometry: bad arguments");
-    *tile_rows = SORT_TILE;
-    return SDQH_OK;
-}
-
-int sdqh_window_geometry(sdqh_ctx* ctx, int64_t* tile_rows) {
-    if (!ctx || !tile_rows) return fail(ctx, SDQH_ERR_INVALID, "window_geometry: bad arguments");
-    *tile_rows = SORT_TILE;
-    return SDQH_OK;
-}
+int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_quantile_geometry", tile_rows, false, nullptr); }
+int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_range_geometry", tile_rows, true, narrow_max_width); }
+int sdqh_window_slide_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_slide_geometry", tile_rows, true, narrow_max_width); }
+int sdqh_window_agg_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_agg_geometry", tile_rows, false, nullptr); }
+int sdqh_window_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_geometry", tile_rows, false, nullptr); }
 
 int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_column** out_ranks, int64_t* out_distinct) {
     if (!ctx || !text || !out_ranks || !out_distinct || nrows < 0) return fail(ctx, SDQH_ERR_INVALID, "text_ranks: bad arguments");

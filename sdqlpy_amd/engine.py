@@ -1729,6 +1729,17 @@ class _FrameSpec(list):
     decoded_order = ()       # the ORDER BY columns of a RangeRequest that are text or decoded on the host (_order_column_decoded)
 
 
+# The requests with partitions, in the order they are told apart: class -> (route, Engine switch, Library flag, the attribute that
+# lists the request's columns — None: ranks only —, the most columns the device takes)
+_WINDOW_ROUTES = (
+    (FrameRequest, "window_agg", "device_window_agg", "has_window_agg", "aggs", abi.WAGG_MAX_AGGS),
+    (SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS),
+    (RangeRequest, "window_range", "device_window_range", "has_window_range", "ranges", abi.WRANGE_MAX_AGGS),
+    (QuantileRequest, "window_quantile", "device_window_quantile", "has_window_quantile", "quants", abi.WQUANT_MAX_COLS),
+    (WindowRequest, "window", "device_window", "has_window", None, 0),
+)
+
+
 def _order_spec(top, spec_of, decoded_of):
     """The device's columns for `top`: spec_of(order, eng_or_None) is _device_sort_spec over the table at hand.  A FrameRequest's
     measures go through the same mapping with no engine to derive anything: whatever needs a decoder or a derivation is None there.
@@ -1740,8 +1751,7 @@ def _order_spec(top, spec_of, decoded_of):
     spec = _FrameSpec(spec)
     if isinstance(top, RangeRequest):
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
-    measured = [a[2] for a in (top.aggs if isinstance(top, FrameRequest) else (top.slides if isinstance(top, SlideRequest) else
-                                                                              (top.ranges if isinstance(top, RangeRequest) else top.quants)))]
+    measured = [a[2] for a in getattr(top, next(items for cls, _, _, _, items, _ in _WINDOW_ROUTES if isinstance(top, cls)))]
     cols = list(dict.fromkeys(col for col in measured if col is not None))
     plain = spec_of([(c, "asc") for c in cols], False) if cols else []      # (a QuantileRequest may measure nothing)
     if plain is not None:
@@ -1753,20 +1763,17 @@ def _order_spec(top, spec_of, decoded_of):
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
             "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile") and _term_text(t) is not None]}
-    if isinstance(top, FrameRequest):                        # "order" / "per" as for a window; the aggregates in the order of their columns
+    if isinstance(top, tuple(cls for cls, *_ in _WINDOW_ROUTES)):      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+    if isinstance(top, FrameRequest):                        # the aggregates in the order of their columns
         note["aggs"] = [list(a) for a in top.aggs]
-    elif isinstance(top, SlideRequest):                      # likewise; lag / lead as the `first` they are, unbounded sides None
-        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+    elif isinstance(top, SlideRequest):                      # lag / lead as the `first` they are, unbounded sides None
         note["slides"] = [list(a) for a in top.slides]
-    elif isinstance(top, RangeRequest):                      # likewise, and the frames' unit
-        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+    elif isinstance(top, RangeRequest):                      # and the frames' unit
         note["unit"], note["ranges"] = top.unit, [list(a) for a in top.ranges]
-    elif isinstance(top, QuantileRequest):                   # likewise, and the per-group limit it filters by
-        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+    elif isinstance(top, QuantileRequest):                   # and the per-group limit it filters by
         note["per_limit"], note["quantiles"] = int(min(top.per_limit, abi.SORT_ALL)), [list(a) for a in top.quants]
-    elif isinstance(top, WindowRequest):                     # "order": the ORDER BY names alone; the PARTITION BY names are "per"
-        note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
+    elif isinstance(top, WindowRequest):
         note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
     eng.order_routes.append(note)
 
@@ -1844,6 +1851,36 @@ def result_columns(plan):
     return None
 
 
+def _columns_fit(top_items, limit, spec):
+    """Can the device take the columns `top_items` of a request with partitions (None: it has none) over the terms `spec`?  At most
+    SORT_MAX_KEYS terms, at most `limit` columns, measures that are underived numeric columns (spec.measures), and — where a column has
+    a default, the sixth member of its tuple; an aggregate over a frame has none — no default beyond 2^53 for a column the table keeps
+    as integer-valued doubles: such a column takes its default as a double and back, and one no double holds stays on the host."""
+    if not 1 <= len(spec) <= abi.SORT_MAX_KEYS:
+        return False
+    if top_items is None:
+        return True
+    if len(top_items) > limit or getattr(spec, "measures", None) is None:
+        return False
+    return not any(len(item) > 5 and item[2] in spec.int_values and item[5] is not None and not isinstance(item[5], (float, np.floating)) and abs(int(item[5])) > 1 << 53
+                   for item in top_items)
+
+
+def _measure_args(col, measure, default, spec, who):
+    """(kind, index, is_f64, empty) of a window call's column over the measure `col` of spec.measures (None: the column has no
+    measure).  empty: the 64 bits of `default` as the device holds the column — a double where the engine keeps integers as
+    integer-valued doubles (converted back with the rest) — or 0 where the column takes no default (who None; else the method's name
+    in slide_empty's messages)."""
+    if col is None:
+        return abi.SORT_KEY, 0, False, 0
+    kind, index, is_f64 = col[0], col[1], col[3]
+    if who is None:
+        return kind, index, is_f64, 0
+    as_f64 = kind == abi.SORT_VALUE or bool(is_f64)
+    fill = slide_empty(default, as_f64 and measure not in spec.int_values, who)
+    return kind, index, is_f64, int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+
+
 def _order_route(eng, top, spec):
     """Who orders `top` = (k, order) or a WindowRequest over the sort columns `spec` (None: no column list the device can take):
     "topk"       sdqh_table_topk: at most MAX_TOPK rows by at most MAX_SORT_KEYS plain columns
@@ -1871,28 +1908,12 @@ def _order_route(eng, top, spec):
     k, n = top[0], len(spec)
     derived = any(_term_derived(t) for t in spec)
     terms_ok = not derived or on("device_sort", "has_sort_terms")
-    if isinstance(top, FrameRequest):
-        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.aggs) <= abi.WAGG_MAX_AGGS and getattr(spec, "measures", None) is not None
-        return "window_agg" if fits and on("device_window_agg", "has_window_agg") and terms_ok else "host"
-    if isinstance(top, SlideRequest):
-        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.slides) <= abi.WSLIDE_MAX_AGGS and getattr(spec, "measures", None) is not None
-        # a column the table keeps as integer-valued doubles takes its default as a double and back: one no double holds stays on the host
-        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
-                                for _, _, col, _, _, default in top.slides)
-        return "window_slide" if fits and on("device_window_slide", "has_window_slide") and terms_ok else "host"
-    if isinstance(top, RangeRequest):
-        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.ranges) <= abi.WRANGE_MAX_AGGS and getattr(spec, "measures", None) is not None
-        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
-                                for _, _, col, _, _, default in top.ranges)
-        fits = fits and _range_offsets(top, spec) is not None
-        return "window_range" if fits and on("device_window_range", "has_window_range") and terms_ok else "host"
-    if isinstance(top, QuantileRequest):
-        fits = 1 <= n <= abi.SORT_MAX_KEYS and len(top.quants) <= abi.WQUANT_MAX_COLS and getattr(spec, "measures", None) is not None
-        fits = fits and not any(col in spec.int_values and default is not None and not isinstance(default, (float, np.floating)) and abs(int(default)) > 1 << 53
-                                for _, _, col, _, _, default in top.quants)
-        return "window_quantile" if fits and on("device_window_quantile", "has_window_quantile") and terms_ok else "host"
-    if isinstance(top, WindowRequest):
-        return "window" if 1 <= n <= abi.SORT_MAX_KEYS and on("device_window", "has_window") and terms_ok else "host"
+    for cls, route, switch, extension, items, limit in _WINDOW_ROUTES:
+        if isinstance(top, cls):
+            fits = _columns_fit(None if items is None else getattr(top, items), limit, spec)
+            if fits and cls is RangeRequest:
+                fits = _range_offsets(top, spec) is not None
+            return route if fits and on(switch, extension) and terms_ok else "host"
     if derived:
         return "sorted_by" if k >= 1 and n <= abi.SORT_MAX_KEYS and terms_ok else "host"
     if 1 <= k <= abi.MAX_TOPK and n <= abi.MAX_SORT_KEYS:
@@ -1952,41 +1973,25 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
     elif route == "sorted_by":
         got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
     elif route == "window_agg":
-        aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + ((abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3]))
-                for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
+        aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
         got = eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
     elif route == "window_slide":
         slides = []
         for (_, op, measure, lo, hi, default), col in zip(top.slides, spec.measures):
-            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
-            empty = 0
-            if col is not None:                                  # the default's 64 bits as the device holds the column: a double where the
-                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)  # engine keeps integers as integer-valued doubles (converted back with the rest)
-                fill = slide_empty(default, as_f64 and measure not in spec.int_values)
-                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "sliding")
             slides.append((SLIDE_OPS.index(op), kind, index, is_f64, abi.SLIDE_UNBOUNDED_PRECEDING if lo is None else lo,
                            abi.SLIDE_UNBOUNDED_FOLLOWING if hi is None else hi, empty))
         got = eng.ctx.table_window_slide(table, min_hits, top.npartition, terms, slides, k, cap, want_hits=want_hits)
     elif route == "window_range":
         ranges = []
         for (_, op, measure, _, _, default), col, (lo, hi) in zip(top.ranges, spec.measures, _range_offsets(top, spec)):
-            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
-            empty = 0
-            if col is not None:                                  # (the default's 64 bits as the device holds the column: see "window_slide")
-                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)
-                fill = slide_empty(default, as_f64 and measure not in spec.int_values, "ranged")
-                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "ranged")
             ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
         got = eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
     elif route == "window_quantile":
         quants = []
         for (_, fn, measure, arg, p, default), col in zip(top.quants, spec.measures):
-            kind, index, is_f64 = (abi.SORT_KEY, 0, False) if col is None else (col[0], col[1], col[3])
-            empty = 0
-            if col is not None and fn == "nth":                  # (the default's 64 bits as the device holds the column: see "window_slide")
-                as_f64 = kind == abi.SORT_VALUE or bool(is_f64)
-                fill = slide_empty(default, as_f64 and measure not in spec.int_values, "quantiles")
-                empty = int(np.array(np.float64(fill) if as_f64 else fill).view(np.int64))
+            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "quantiles" if fn == "nth" else None)      # (NTH alone has a default)
             quants.append((QUANTILE_FNS.index(fn), kind, index, is_f64, 0 if arg is None else arg, 0.0 if p is None else p, empty))
         got = eng.ctx.table_window_quantile(table, min_hits, top.npartition, terms, quants, min(int(top.per_limit), abi.SORT_ALL), k, cap, want_hits=want_hits)
     else:

@@ -496,6 +496,34 @@ def test_the_three_entry_points_agree(hip_engine):
     assert done == 6 * 2 * len(SPECS) * 3
 
 
+def test_window_paths_launch_what_they_launched(hip_engine):
+    """One step type and one partition pass behind the five window entry points: every call of tests/golden/make_window_path_golden.py
+    (ranks, frames, slides, value / group frames, quantiles; with and without a filter, a rank column, fold kernels; count-only and a
+    capacity below the count; at the sizes where the sort and the tile scans change path) returns the code, the *out_n and bit for bit
+    the arrays it returned at the commit before the host paths were merged, and launches exactly the kernels it launched there, in
+    that order (tests/golden/window_path_kernels.json)."""
+    import importlib.util
+    import json
+    golden_dir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    mod = importlib.util.spec_from_file_location("make_window_path_golden", os.path.join(golden_dir, "make_window_path_golden.py"))
+    recorder = importlib.util.module_from_spec(mod)
+    mod.loader.exec_module(recorder)
+    with open(os.path.join(golden_dir, "window_path_kernels.json")) as fh:
+        golden = json.load(fh)
+    ctx = hip_engine.ctx
+    S, tile, _ = ctx.sort_geometry()
+    assert golden["geometry"] == [S, tile] == [1024, 512]
+    ctx.set_profiling(1)
+    try:
+        got = recorder.run_cases(ctx, abi, _probed_table)
+    finally:
+        ctx.set_profiling(0)
+    assert sorted(got["calls"]) == sorted(golden["calls"]) and len(golden["calls"]) == 6 * 2 * 31
+    for case, want in golden["calls"].items():
+        assert got["calls"][case] == want, case
+    assert any("k_wrg_upper" in c["kernels"] for c in golden["calls"].values()) and any("k_win_place" in c["kernels"] for c in golden["calls"].values())
+
+
 # 6. argument errors -----------------------------------------------------------------------------------------------------------------------
 def test_argument_errors_leave_the_context_usable(hip_engine):
     ctx = hip_engine.ctx
