@@ -372,3 +372,18 @@ def test_kernel_headers_carry_no_leftover_ab_switches():
                 offenders.append("%s:%d: %s" % (name, no, line.strip()))
     assert found == allowed, sorted(found ^ allowed)        # (both headers use `#pragma once`: no include guard to allow for)
     assert not offenders, offenders
+
+
+def test_the_tile_scans_geometry_is_what_the_large_window_tests_size_from():
+    """tests/test_window_large_gpu.py sizes its tables from W * T = 131072 sorted positions: W = TPB threads in the one-workgroup scans
+    over the tiles, T = SORT_TILE positions per tile; beyond W * T positions a thread of those scans folds more than one tile.  A change
+    of either constant must come with new sizes there: as they are they would silently stop reaching two tiles per thread."""
+    def constant(name, unit):
+        text = open(os.path.join(ROOT, "sdqlpy_amd", "csrc", unit)).read()
+        found = re.findall(r"^\s*constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, text, flags=re.M)
+        assert len(found) == 1, (name, unit, found)
+        return int(found[0])
+    tpb, tile = constant("TPB", "sdqh_kernels.hpp"), constant("SORT_TILE", "sdqh_sort.hip")
+    assert (tpb, tile) == (256, 512) and tpb * tile == 131072
+    large = open(os.path.join(ROOT, "tests", "test_window_large_gpu.py")).read()
+    assert re.search(r"^W = %d\b" % tpb, large, flags=re.M) and "T == %d" % tile in large
