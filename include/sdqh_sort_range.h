@@ -13,8 +13,8 @@
  * a compile-only context (argument checks first) and the wait for the stream are exactly those of sdqh_table_window_slide, declared
  * in sdqh_sort_slide.h.  Frames look past `limit`, as they do there.  What differs is the frame.
  *
- * These two frame units were the first entries of sdqh_sort_slide.h's "Not here" list.  Not here: EXCLUDE clauses; AVG (divide a SUM
- * by a COUNT of the same frame); text measures; calendar arithmetic — dates are stored as yyyymmdd integers, so a VALUE offset on a
+ * These two frame units were the first entries of sdqh_sort_slide.h's "Not here" list.  EXCLUDE clauses, AVG and frames of different
+ * units in one call are the eighth extension's: sdqh_sort_exclude.h.  Not here: text measures; calendar arithmetic — dates are stored as yyyymmdd integers, so a VALUE offset on a
  * date column counts in those units (GROUPS counts distinct dates); and the multi-GPU runner. */
 #ifndef SDQH_SORT_RANGE_H
 #define SDQH_SORT_RANGE_H

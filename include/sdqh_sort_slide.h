@@ -11,7 +11,7 @@
  * bitmap-only table or a compile-only context (argument checks first) and the wait for the stream are exactly those of
  * sdqh_table_window_agg, declared in sdqh_sort_frames.h.  What differs is the frame.
  *
- * Not here: AVG (divide a SUM by a COUNT of the same frame), text measures, and the multi-GPU runner.  Value-based frames (RANGE BETWEEN x
+ * Not here: text measures and the multi-GPU runner.  AVG, and ROWS frames with an EXCLUDE clause, are the eighth extension's: sdqh_sort_exclude.h.  Value-based frames (RANGE BETWEEN x
  * PRECEDING ...) and GROUPS frames are the sixth extension's: sdqh_sort_range.h.  NTILE, PERCENT_RANK, CUME_DIST, NTH_VALUE and the
  * percentiles are the seventh's: sdqh_sort_quantile.h. */
 #ifndef SDQH_SORT_SLIDE_H

@@ -54,13 +54,21 @@ WRANGE_MAX_AGGS = 4
 WINDOW_QUANTILE_EXPORTS = ["sdqh_table_window_quantile", "sdqh_window_quantile_geometry"]
 WQ_NTILE, WQ_PERCENT_RANK, WQ_CUME_DIST, WQ_NTH, WQ_PERCENTILE_DISC, WQ_PERCENTILE_CONT = 0, 1, 2, 3, 4, 5
 WQUANT_MAX_COLS = 4
-# the five of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
+# ... and its eighth (include/sdqh_sort_exclude.h, Library.has_window_exclude): frames with rows taken out — EXCLUDE CURRENT ROW / GROUP /
+# TIES —, AVG, and ROWS / RANGE / GROUPS frames side by side in one call: the unit is a column's own
+WINDOW_EXCLUDE_EXPORTS = ["sdqh_table_window_exclude", "sdqh_window_exclude_geometry"]
+WEX_ROWS = 2                                     # a unit beside WRANGE_VALUE / WRANGE_GROUPS
+WEX_AVG = 6                                      # an op beside WAGG_SUM .. WSLIDE_LAST
+WEX_NO_OTHERS, WEX_CURRENT_ROW, WEX_GROUP, WEX_TIES = 0, 1, 2, 3
+WEX_MAX_COLS = 4
+# the six of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
     "has_window_agg": (WINDOW_AGG_EXPORTS, "sdqh_sort_frames.h", "window aggregate", "has_window"),
     "has_window_slide": (WINDOW_SLIDE_EXPORTS, "sdqh_sort_slide.h", "window slide", "has_window_agg"),
     "has_window_range": (WINDOW_RANGE_EXPORTS, "sdqh_sort_range.h", "window range", "has_window_slide"),
     "has_window_quantile": (WINDOW_QUANTILE_EXPORTS, "sdqh_sort_quantile.h", "window quantile", "has_window_slide"),
+    "has_window_exclude": (WINDOW_EXCLUDE_EXPORTS, "sdqh_sort_exclude.h", "window exclude", "has_window_range"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -79,14 +87,14 @@ def _measure_is_f64(kind, is_f64):
     return kind == SORT_VALUE or (kind == SORT_PAYLOAD and bool(is_f64))
 
 
-def _range_offset(x):
+def _range_offset(x, who="table_window_range"):
     """A frame offset of sdqh_window_range as its int64: an int as it is, a float as its bits, None (unbounded: ignored) as 0."""
     if x is None:
         return 0
     if isinstance(x, (float, np.floating)):
         return int(np.float64(x).view(np.int64))
     if not INT64_MIN <= int(x) <= INT64_MAX:                 # (ctypes would cut it to 64 bits without a word)
-        raise SdqhError(ERR_INVALID, "table_window_range: the offset %d does not fit int64" % int(x))
+        raise SdqhError(ERR_INVALID, "%s: the offset %d does not fit int64" % (who, int(x)))
     return int(x)
 
 
@@ -157,6 +165,13 @@ class WindowRange(C.Structure):
     (int64, or the bits of doubles for a VALUE frame over a double term) and the 64 bits of an empty frame."""
     _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32),
                 ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
+
+
+class WindowExclude(C.Structure):
+    """sdqh_window_exclude: a WindowRange whose unit may be WEX_ROWS and whose op may be WEX_AVG, and what is taken out of the frame
+    (WEX_NO_OTHERS / WEX_CURRENT_ROW / WEX_GROUP / WEX_TIES)."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32),
+                ("exclude", C.c_int32), ("_pad", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
 
 
 class WindowQuantile(C.Structure):
@@ -1380,6 +1395,30 @@ class Context:
         the tests size their cases from."""
         return self._window_geometry("has_window_range", 2)
 
+    def table_window_exclude(self, table, min_hits, npartition, terms, cols, limit, capacity, want_hits=True):
+        """Values over window frames with rows taken out: terms and npartition as table_window takes them; cols: [(op, kind, index,
+        is_f64, unit, lo, hi, empty, exclude)] — op one of WAGG_SUM .. WSLIDE_LAST or WEX_AVG, the measure as table_window_slide takes it,
+        unit WRANGE_VALUE / WRANGE_GROUPS (the frames of table_window_range) or WEX_ROWS (the rows [j + lo, j + hi]) per column, lo /
+        hi signed along the order (None: unbounded; floats only for a VALUE column over a double term), empty: the 64 bits a column
+        gives where nothing remains, exclude: WEX_NO_OTHERS / WEX_CURRENT_ROW / WEX_GROUP / WEX_TIES.  Every selected row is kept;
+        the first min(limit, n) in sorted order.  Returns (keys, payload, values, hits, cols) — cols one array per column: float64 for
+        an AVG and for a double measure under any op but COUNT, else int64."""
+        self._need("has_window_exclude", "table_window_exclude")
+        arr = (WindowExclude * max(1, len(cols)))()
+        for i, (op, kind, index, is_f64, unit, lo, hi, empty, exclude) in enumerate(cols):
+            if not INT64_MIN <= int(empty) <= INT64_MAX:         # (ctypes would cut it to 64 bits without a word)
+                raise SdqhError(ERR_INVALID, "table_window_exclude: the empty value %d does not fit int64" % int(empty))
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64, arr[i].unit, arr[i].exclude = int(op), int(kind), int(index), 1 if is_f64 else 0, int(unit), int(exclude)
+            arr[i].flags = (WRANGE_LO_UNBOUNDED if lo is None else 0) | (WRANGE_HI_UNBOUNDED if hi is None else 0)
+            arr[i].lo, arr[i].hi, arr[i].empty = _range_offset(lo, "table_window_exclude"), _range_offset(hi, "table_window_exclude"), int(empty)
+        as_f64 = [c[0] == WEX_AVG or (c[0] != WAGG_COUNT and _measure_is_f64(c[1], c[3])) for c in cols]
+        return self._window_columns_call("table_window_exclude", table, min_hits, npartition, terms, arr, len(cols), (), limit, capacity, want_hits, True, as_f64)
+
+    def window_exclude_geometry(self):
+        """(sorted positions per tile of sdqh_table_window_exclude's passes, the largest frame width a kernel walks row by row or 0):
+        what the tests size their cases from."""
+        return self._window_geometry("has_window_exclude", 2)
+
     def table_window_quantile(self, table, min_hits, npartition, terms, cols, per_limit, limit, capacity, want_hits=True, want_cols=True):
         """Functions of the partition's size beside the ordered entries: terms and npartition as table_window takes them; cols: [(fn,
         kind, index, is_f64, arg, p, empty)] — fn one of WQ_NTILE (arg = b >= 1) / WQ_PERCENT_RANK / WQ_CUME_DIST / WQ_NTH (arg = k != 0,
@@ -1658,7 +1697,7 @@ class Library:
             L.sdqh_text_ranks.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
             L.sdqh_table_sorted_by.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p]
-        for flag, (exports, _, _, base) in WINDOW_EXTENSIONS.items():      # ... and the five window extensions, each on the one before it
+        for flag, (exports, _, _, base) in WINDOW_EXTENSIONS.items():      # ... and the window extensions, each on the one it builds on
             setattr(self, flag, bool(getattr(self, base)) and all(hasattr(L, s) for s in exports))
         if self.has_window:
             L.sdqh_table_window.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int64,
@@ -1676,6 +1715,10 @@ class Library:
             L.sdqh_table_window_range.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_range_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        if self.has_window_exclude:
+            L.sdqh_table_window_exclude.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_exclude_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -24,13 +24,14 @@
 //
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
 // (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h), sdqh_table_window_slide
-// (include/sdqh_sort_slide.h), sdqh_table_window_range (include/sdqh_sort_range.h) and sdqh_table_window_quantile
-// (include/sdqh_sort_quantile.h): select -> passes -> step -> emit -> fetch (ordered_impl, the spine).  What differs between them
+// (include/sdqh_sort_slide.h), sdqh_table_window_range (include/sdqh_sort_range.h), sdqh_table_window_quantile
+// (include/sdqh_sort_quantile.h) and sdqh_table_window_exclude (include/sdqh_sort_exclude.h): select -> passes -> step -> emit -> fetch
+// (ordered_impl, the spine).  What differs between them
 // is data, not code: their terms, and ONE step description (SortStep) that the spine hands to one dispatch.  On the host the step
 // is three pieces: the partition pass (Partitions + partition_pass: the arrays every family reads its partitions from, k_win_heads
 // and of k_win_scan / k_wsl_rows / k_wagg_next those the family names), the filter (rank_filter: k_win_rank -> k_sort_scan -> the
 // kept count to the host -> the ways out -> k_win_place; a window filters on its own ranks, quantiles on row numbers) and the family
-// steps (step_ranks / _frames / _slides / _ranges / _quantiles: each lays out scratch block 3, runs the pieces above and its own
+// steps (step_ranks / _frames / _slides / _ranges / _quantiles / _excludes: each lays out scratch block 3, runs the pieces above and its own
 // kernels and says where each output column lies).  In front of them the entry points share window_enter, measure_set and
 // fold_class.  On the device:
 //
@@ -101,6 +102,15 @@
 //   k_win_rank        only with a PERCENT_RANK column: the RANK of every position = its tie run's first offset + 1 (every row kept)
 //   k_wq_stage        backwards: per position its partition's and its tie run's last position, every distinct measure's element once
 //   k_wq_value        per returned row the indices, one or two gathers and the arithmetic — see the section
+//   EXCLUDES          in their place (STEP_EXCLUDES).  sdqh_table_window_exclude (include/sdqh_sort_exclude.h) takes the six ops of the
+//                     slides and AVG over ROWS, VALUE and GROUP frames — the unit a column's own — out of which the row, its tie run
+//                     or its ties are taken.  Behind k_win_heads, k_win_scan, k_wsl_rows and k_wagg_next, and the ranges' k_win_rank
+//                     (a GROUPS column), k_wrg_stage, k_wrg_tiles and k_wrg_upper over the columns' image as ranges:
+//
+//   k_wq_ties / k_win_rank / k_wex_ties
+//                     only with a GROUP / TIES column: the first tie head of every tile for k_wagg_next to scan, the RANK of every
+//                     position (its tie run's first offset + 1) and, backwards, its tie run's last position
+//   k_wex_fold        per row and column the base frame's ends, the cut into at most three pieces, a tree query per piece — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -116,6 +126,7 @@
 #include "sdqh_host.hpp"
 #include "sdqh_sort_range.h"
 #include "sdqh_sort_quantile.h"
+#include "sdqh_sort_exclude.h"
 
 using namespace sdqh_host;
 
@@ -1268,6 +1279,139 @@ __global__ __launch_bounds__(TPB) void k_wq_value(DevWquants q, const uint32_t* 
     }
 }
 
+// ---- frames with rows taken out (sdqh_table_window_exclude) ------------------------------------------------------------------------
+// The base frame of sorted row j is an interval [l, r] of its partition [s, e] in the column's own unit — ROWS: arithmetic on j;
+// VALUE / GROUPS: the two binary searches of k_wrg_fold over the same keys — and what EXCLUDE removes is an interval around j too:
+// {j}, or j's tie run [a, b] (a from k_win_rank's RANK arm, b from k_wex_ties), with or without j itself.  What remains is at most
+// three pieces in position order, [l, min(r, x0 - 1)], {j}, [max(l, x1 + 1), r]: COUNT adds their lengths, FIRST / LAST gather at
+// the first / last remaining position, SUM / MIN / MAX / AVG ask the fold tree of the ranges (k_wrg_stage / _tiles / _upper build
+// it from the columns' DevWranges image, an AVG staged as the SUM it divides) once per piece with k_wrg_fold's iterative query and
+// join the answers left to right: exactly the remaining rows enter, once each, nothing is subtracted, and the association is a
+// function of the pieces' ends and cap alone.  With nothing excluded the one piece is the frame and the bits are k_wrg_fold's.
+struct DevWexs { DevWranges rg; int32_t exclude[SDQH_WEX_MAX_COLS]; int32_t avg[SDQH_WEX_MAX_COLS]; };      // rg: the image (a[c].unit may be SDQH_WEX_ROWS: lo / hi clamped to [-n, n]; an AVG has op SUM there)
+static_assert(SDQH_WEX_MAX_COLS == SDQH_WRANGE_MAX_AGGS, "the columns of an exclude call are the ranges of its image");
+
+// 1. only with a GROUP / TIES column: a tile walked backwards (k_wq_stage's shape), per position the last position of its tie run —
+// the next tie head read off the ballots above the lane, else off the batches and tiles behind (tnext: k_wagg_next's, over the
+// first tie heads k_wq_ties left)
+__global__ __launch_bounds__(TPB) void k_wex_ties(const uint8_t* __restrict__ heads, const WaggHeads* __restrict__ tnext, uint32_t n, uint32_t* __restrict__ tend, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint32_t next = tnext[w].tie;
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(heads, r, live, le);
+        const uint64_t tg = h.mt & ~le;
+        if (live) tend[r] = (tg ? (uint32_t)b + (uint32_t)__builtin_ctzll(tg) : next) - 1u;
+        if (h.mt) next = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mt);
+        if (b == r0) break;
+    }
+}
+// the base frame [l, r1) of row j in [s, e] (false: no row): ROWS by arithmetic, VALUE / GROUPS as k_wrg_fold finds it
+__device__ __forceinline__ bool wex_ends(const DevWrange& d, const DevWranges& rg, const uint64_t* __restrict__ vkey, const uint64_t* __restrict__ gkey,
+                                         uint64_t j, uint32_t s, uint32_t e, uint32_t& l, uint32_t& r1) {
+    if (d.unit == SDQH_WEX_ROWS) {                                       // (|lo|, |hi| <= n < 2^32: no overflow)
+        const int64_t a = (d.flags & SDQH_WRANGE_LO_UNBOUNDED) ? (int64_t)s : max((int64_t)j + d.lo, (int64_t)s);
+        const int64_t b = (d.flags & SDQH_WRANGE_HI_UNBOUNDED) ? (int64_t)e : min((int64_t)j + d.hi, (int64_t)e);
+        if (a > b) return false;
+        l = (uint32_t)a; r1 = (uint32_t)b + 1u;
+        return true;
+    }
+    const bool groups = d.unit == SDQH_WRANGE_GROUPS;
+    const uint64_t* __restrict__ key = groups ? gkey : vkey;
+    const bool desc = !groups && rg.vdesc != 0, f64 = !groups && rg.vf64 != 0;
+    const uint64_t kj = key[j];
+    int sl = (d.flags & SDQH_WRANGE_LO_UNBOUNDED) ? 1 : 0, sr = (d.flags & SDQH_WRANGE_HI_UNBOUNDED) ? 1 : 0;      // k_wrg_fold's sides
+    uint64_t kl = kj, kr = kj;
+    if (!f64) {
+        const int64_t vj = (int64_t)((desc ? ~kj : kj) ^ (1ull << 63));
+        if (sl == 0) sl = wrg_int_bound(vj, d.lo, desc, true, kl);
+        if (sr == 0) sr = wrg_int_bound(vj, d.hi, desc, false, kr);
+    } else {
+        const uint64_t u = desc ? ~kj : kj;
+        const double vj = __longlong_as_double((long long)((u >> 63) ? (u ^ (1ull << 63)) : ~u));
+        if (vj == vj) {
+            const double lo = __longlong_as_double(d.lo), hi = __longlong_as_double(d.hi);
+            const double fa = vj + (desc ? -lo : lo), fb = vj + (desc ? -hi : hi);
+            double x = desc ? fb : fa, y = desc ? fa : fb;
+            if (sl == 0 && sr == 0 && x > y) { const double t = x; x = y; y = t; }
+            if (desc) { kl = wrg_f64_key(y, false, true); kr = wrg_f64_key(x, true, true); }
+            else { kl = wrg_f64_key(x, true, false); kr = wrg_f64_key(y, false, false); }
+        }
+    }
+    l = sl == 1 ? s : wrg_lower(key, s, e + 1u, kl);
+    r1 = sr == 1 ? e + 1u : wrg_upper(key, s, e + 1u, kr);
+    return sl != 2 && sr != 2 && l < r1;
+}
+// the fold of tree t over the positions [a, b] (a <= b < n): k_wrg_fold's iterative query
+__device__ __forceinline__ uint64_t wex_query(int cls, const uint64_t* __restrict__ t, uint64_t cap, int64_t a, int64_t b) {
+    uint64_t left = wagg_identity(cls), right = left;
+    for (uint64_t p = cap + (uint64_t)a, q = cap + (uint64_t)b + 1ull; p < q; p >>= 1, q >>= 1) {
+        if (p & 1ull) left = wagg_join(cls, left, t[p++]);
+        if (q & 1ull) right = wagg_join(cls, t[--q], right);
+    }
+    return wagg_join(cls, left, right);
+}
+// 2. the value of every column at the first m positions: fin[c * stride + j].  rown: k_wsl_rows' (s = j - rown[j]); pend, vkey, gkey,
+// elem, tree: k_wrg_stage's; frank: k_win_rank's RANK (a = s + frank[j] - 1) and tend: k_wex_ties' (b) — both nullptr when no column
+// excludes GROUP or TIES
+__global__ __launch_bounds__(TPB) void k_wex_fold(DevWexs ex, const uint32_t* __restrict__ rown, const uint32_t* __restrict__ pend, const uint32_t* __restrict__ frank,
+                                                 const uint32_t* __restrict__ tend, const uint64_t* __restrict__ vkey, const uint64_t* __restrict__ gkey, uint32_t n, uint32_t m,
+                                                 size_t stride, size_t tstride, uint64_t cap, const uint64_t* __restrict__ elem, const uint64_t* __restrict__ tree,
+                                                 uint64_t* __restrict__ fin) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t rn = rown[j], e = pend[j];
+        if ((uint64_t)rn > j || (uint64_t)e < j || e >= n) continue;       // (s <= j <= e < n: never taken)
+        const uint32_t s = (uint32_t)j - rn;
+        int64_t ta = (int64_t)j, tb = (int64_t)j;                         // the tie run [ta, tb]
+        if (frank) {
+            const int64_t a = (int64_t)s + (int64_t)frank[j] - 1, b = (int64_t)tend[j];
+            if (a >= (int64_t)s && a <= (int64_t)j && b >= (int64_t)j && b <= (int64_t)e) { ta = a; tb = b; }      // (s <= a <= j <= b <= e: always)
+        }
+#pragma unroll
+        for (int c = 0; c < SDQH_WEX_MAX_COLS; ++c) if (c < ex.rg.n) {
+            const DevWrange& d = ex.rg.a[c];
+            const int x = ex.exclude[c];
+            uint32_t l = 0u, r1 = 0u;
+            const bool any = wex_ends(d, ex.rg, vkey, gkey, j, s, e, l, r1);
+            // the pieces [a1, b1], {j} (mid), [a3, b3]; an empty one has its end below its start
+            int64_t a1 = 0, b1 = -1, a3 = 0, b3 = -1;
+            bool mid = false;
+            if (any) {
+                const int64_t fl = (int64_t)l, fr = (int64_t)r1 - 1;
+                const int64_t x0 = x == SDQH_WEX_NO_OTHERS ? fr + 1 : (x == SDQH_WEX_CURRENT_ROW ? (int64_t)j : ta);
+                const int64_t x1 = x == SDQH_WEX_NO_OTHERS ? fr : (x == SDQH_WEX_CURRENT_ROW ? (int64_t)j : tb);
+                a1 = fl; b1 = min(fr, x0 - 1); a3 = max(fl, x1 + 1); b3 = fr;
+                mid = x == SDQH_WEX_TIES && fl <= (int64_t)j && (int64_t)j <= fr;
+            }
+            const bool p1 = a1 <= b1, p3 = a3 <= b3;
+            const uint64_t count = (p1 ? (uint64_t)(b1 - a1 + 1) : 0ull) + (mid ? 1ull : 0ull) + (p3 ? (uint64_t)(b3 - a3 + 1) : 0ull);
+            uint64_t v;
+            if (d.g.op == SDQH_WAGG_COUNT) v = count;
+            else if (count == 0ull) v = d.empty;
+            else if (d.g.op == SDQH_WSLIDE_FIRST) v = elem[(size_t)d.slot * stride + (size_t)(p1 ? a1 : (mid ? (int64_t)j : a3))];
+            else if (d.g.op == SDQH_WSLIDE_LAST) v = elem[(size_t)d.slot * stride + (size_t)(p3 ? b3 : (mid ? (int64_t)j : b1))];
+            else {
+                const int cls = d.g.cls;
+                const uint64_t* __restrict__ t = tree + (size_t)d.slot * tstride;
+                uint64_t acc = 0ull;
+                bool have = false;
+                if (p1) { acc = wex_query(cls, t, cap, a1, b1); have = true; }
+                if (mid) { const uint64_t q = wex_query(cls, t, cap, (int64_t)j, (int64_t)j); acc = have ? wagg_join(cls, acc, q) : q; have = true; }
+                if (p3) { const uint64_t q = wex_query(cls, t, cap, a3, b3); acc = have ? wagg_join(cls, acc, q) : q; }
+                if (ex.avg[c]) {                                         // the column's own SUM as a double, one division
+                    const double sum = d.g.sk.is_f64 ? __longlong_as_double((long long)acc) : (double)(int64_t)acc;
+                    v = (uint64_t)__double_as_longlong(sum / (double)count);
+                } else v = wagg_result(d.g, acc);
+            }
+            fin[(size_t)c * stride + j] = v;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1466,12 +1610,12 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // filter: only the rows whose rank of `rank_kind` is <= per_limit are returned (filters false: the entry point has no such argument).
 // out: the rank column, or out[a * capacity + j] = column a beside returned row j — nullptr: rows only, no column is computed.  Then
 // the family's device arguments (a slide's lo / hi: the caller's).
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES };
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
     int64_t* out;
-    union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; };
+    union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; DevWexs ex; };
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -1718,6 +1862,69 @@ static int step_quantiles(StepRun& r) {
     return SDQH_OK;
 }
 
+// Values over frames with rows taken out (sdqh_table_window_exclude): block 3 = [partition pass | partition ends | dense ranks | kept
+// per tile | tie-run ranks | kept per tile of that pass | tie-run ends | VALUE keys | GROUPS keys | raw elements, an array per FIRST /
+// LAST column | fold trees, one per folded column (SUM / MIN / MAX / AVG) | values] — the dense ranks and the GROUPS keys only with a
+// GROUPS column, the VALUE keys only with a VALUE column, the tie arrays only when some column excludes GROUP or TIES.  The trees and
+// the keys are the ranges': k_wrg_stage / _tiles / _upper over the columns' DevWranges image.
+static int step_excludes(StepRun& r) {
+    const int64_t n = r.n;
+    DevWexs ex = r.step.ex;
+    DevWranges& rg = ex.rg;
+    const size_t na = (size_t)rg.n;
+    int nfold = 0, nraw = 0; bool groups = false, ties = false;      // folded columns, FIRST / LAST columns, any GROUPS column, any GROUP / TIES exclusion
+    for (size_t a = 0; a < na; ++a) {
+        DevWrange& d = rg.a[a];
+        d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
+        groups |= d.unit == SDQH_WRANGE_GROUPS;
+        ties |= ex.exclude[a] == SDQH_WEX_GROUP || ex.exclude[a] == SDQH_WEX_TIES;
+        if (d.unit == SDQH_WEX_ROWS) {                                 // an offset of n or more reaches outside every partition: clamped, as a slide's is
+            d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
+            d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
+        }
+    }
+    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
+    while (cap < (uint64_t)n) cap <<= 1;
+    const size_t tstride = nfold ? (size_t)(2 * cap) : 0;
+    Partitions p;
+    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr, *frank = nullptr, *fkept = nullptr, *tend = nullptr;
+    uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, n, true, true, true);
+            pend = c.take<uint32_t>((size_t)n);
+            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
+            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
+            frank = c.take<uint32_t>(ties ? (size_t)n : 0);
+            fkept = c.take<uint32_t>(ties ? p.ntiles : 0);
+            tend = c.take<uint32_t>(ties ? (size_t)n : 0);
+            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
+            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+            elem = c.take<uint64_t>(r.stride * (size_t)nraw);
+            tree = c.take<uint64_t>(tstride * (size_t)nfold);
+            fin = c.take<uint64_t>(r.stride * na);
+        })) return r.nomem();
+    if (rg.vcol < 0) vkey = nullptr;
+    if (!groups) { dense = nullptr; gkey = nullptr; }
+    if (!ties) { frank = nullptr; tend = nullptr; }
+    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS);
+    if (ties) LAUNCH(r.ctx, "k_wq_ties", k_wq_ties, p.tgrid, p.heads, r.un, p.tfirst, p.ntiles);
+    partition_pass(r, p, PP_NEXT);
+    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
+    if (ties) {
+        LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_RANK, ~0ull, frank, fkept, p.ntiles);
+        LAUNCH(r.ctx, "k_wex_ties", k_wex_ties, p.tgrid, p.heads, p.tnext, r.un, tend, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
+           r.stride, tstride, cap, pend, vkey, gkey, elem, tree, p.ntiles);
+    if (nfold) {
+        LAUNCH(r.ctx, "k_wrg_tiles", k_wrg_tiles, p.tgrid, rg, r.un, tstride, cap, tree, p.ntiles);
+        if (cap > (uint64_t)SORT_TILE) LAUNCH(r.ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wex_fold", k_wex_fold, r.row_grid(), ex, p.rown, pend, frank, tend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, elem, tree, fin);
+    r.columns(fin, rg.n);
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -1747,6 +1954,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_SLIDES: if (step.out) step_rc = step_slides(r); break;
         case STEP_RANGES: if (step.out) step_rc = step_ranges(r); break;
         case STEP_QUANTILES: if (step.out || !all_kept) step_rc = step_quantiles(r); break;
+        case STEP_EXCLUDES: if (step.out) step_rc = step_excludes(r); break;
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -1983,6 +2191,51 @@ int sdqh_table_window_quantile(sdqh_ctx* ctx, const sdqh_table* table, int64_t m
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_window_exclude(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                              int ncols, const sdqh_window_exclude* cols, int64_t limit, int64_t capacity,
+                              int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
+    const char* who = "table_window_exclude";
+    bool ok = cols && ncols >= 1 && ncols <= SDQH_WEX_MAX_COLS;
+    bool value = false;
+    for (int c = 0; ok && c < ncols; ++c) {
+        const sdqh_window_exclude& g = cols[c];
+        ok = g.op >= SDQH_WAGG_SUM && g.op <= SDQH_WEX_AVG && g.unit >= SDQH_WRANGE_VALUE && g.unit <= SDQH_WEX_ROWS &&
+             g.exclude >= SDQH_WEX_NO_OTHERS && g.exclude <= SDQH_WEX_TIES && g._pad == 0 && !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+    }
+    bool vf64 = false;
+    if (ok && value) {                                                // sdqh_table_window_range's demand of a VALUE frame: one ORDER BY term, with arithmetic
+        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
+        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
+    }
+    for (int c = 0; ok && c < ncols; ++c) {
+        const sdqh_window_exclude& g = cols[c];
+        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
+            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
+            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
+            ok = lo_ok && hi_ok && !(both && lo > hi);
+        } else ok = !(both && g.lo > g.hi);
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_EXCLUDES, npartition, out_cols);
+    DevWranges& rg = st.ex.rg;
+    rg.n = ncols;
+    rg.vcol = value ? npartition : -1; rg.vdesc = value ? terms[npartition].sk.desc : 0; rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    for (int c = 0; c < ncols; ++c) {
+        const sdqh_window_exclude& g = cols[c];
+        DevWrange& d = rg.a[c];
+        const int op = g.op == SDQH_WEX_AVG ? SDQH_WAGG_SUM : g.op;      // an AVG is staged and folded as the SUM it divides
+        d.g.op = op; d.empty = (uint64_t)g.empty; d.unit = g.unit; d.flags = g.flags; d.lo = g.lo; d.hi = g.hi;
+        st.ex.exclude[c] = g.exclude; st.ex.avg[c] = g.op == SDQH_WEX_AVG ? 1 : 0;
+        if (op != SDQH_WAGG_COUNT)                                    // (COUNT ignores its measure)
+            if (int rc = measure_set(ctx, table, who, "column", c, g.kind, g.index, g.is_f64, d.g.sk)) return rc;
+        d.g.cls = fold_class(op, d.g.sk.is_f64, false);
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
 
 // what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
 // a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
@@ -1992,6 +2245,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_window_exclude_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_exclude_geometry", tile_rows, true, narrow_max_width); }
 int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_quantile_geometry", tile_rows, false, nullptr); }
 int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_range_geometry", tile_rows, true, narrow_max_width); }
 int sdqh_window_slide_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_slide_geometry", tile_rows, true, narrow_max_width); }

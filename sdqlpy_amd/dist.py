@@ -60,9 +60,11 @@ _COLL_ON_RECORDED_STREAM = os.environ.get("SDQLPY_AMD_DIST_COLL_ON_RECORDED_STRE
 def refuse_window(top):
     """ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest), aggregates over window frames (over:
     result.FrameRequest), values over sliding frames (sliding: result.SlideRequest), over value / group frames (ranged:
-    result.RangeRequest) and functions of the group's size (quantiles: result.QuantileRequest) are single-GPU operations: a partition's rows may lie on several ranks, and ranking or folding them takes an
+    result.RangeRequest), over frames with rows taken out (excluding: result.ExcludeRequest) and functions of the group's size (quantiles: result.QuantileRequest) are single-GPU operations: a partition's rows may lie on several ranks, and ranking or folding them takes an
     exchange by partition key that the runner does not have."""
-    from .result import FrameRequest, QuantileRequest, RangeRequest, SlideRequest, WindowRequest
+    from .result import ExcludeRequest, FrameRequest, QuantileRequest, RangeRequest, SlideRequest, WindowRequest
+    if isinstance(top, ExcludeRequest):
+        raise frontend.UnsupportedQuery("excluding runs on one GPU: the multi-GPU runner has no exchange by partition key")
     if isinstance(top, QuantileRequest):
         raise frontend.UnsupportedQuery("quantiles runs on one GPU: the multi-GPU runner has no exchange by partition key")
     if isinstance(top, RangeRequest):

@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import FRAMES, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
+from .result import EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -173,6 +173,9 @@ class Engine:
         # values over value and group frames (ranged: result.RangeRequest) likewise, where the library has the window range extension
         # (abi.Context.table_window_range) — route "window_range", noted with the extra keys "per", "unit" and "ranges"
         self.device_window_range = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_RANGE", "1") != "0"
+        # values over frames with rows taken out (excluding: result.ExcludeRequest) likewise, where the library has the window exclude
+        # extension (abi.Context.table_window_exclude) — route "window_exclude", noted with the extra keys "per", "exclude" and "frames"
+        self.device_window_exclude = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_EXCLUDE", "1") != "0"
         # functions of the group's size (quantiles: result.QuantileRequest) likewise, where the library has the window quantile extension
         # (abi.Context.table_window_quantile) — route "window_quantile", noted with the extra keys "per", "per_limit" and "quantiles"
         self.device_window_quantile = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_QUANTILE", "1") != "0"
@@ -1736,6 +1739,7 @@ _WINDOW_ROUTES = (
     (SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS),
     (RangeRequest, "window_range", "device_window_range", "has_window_range", "ranges", abi.WRANGE_MAX_AGGS),
     (QuantileRequest, "window_quantile", "device_window_quantile", "has_window_quantile", "quants", abi.WQUANT_MAX_COLS),
+    (ExcludeRequest, "window_exclude", "device_window_exclude", "has_window_exclude", "frames", abi.WEX_MAX_COLS),
     (WindowRequest, "window", "device_window", "has_window", None, 0),
 )
 
@@ -1746,10 +1750,10 @@ def _order_spec(top, spec_of, decoded_of):
     decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
     text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest)):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest)):
         return spec
     spec = _FrameSpec(spec)
-    if isinstance(top, RangeRequest):
+    if isinstance(top, (RangeRequest, ExcludeRequest)):
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
     measured = [a[2] for a in getattr(top, next(items for cls, _, _, _, items, _ in _WINDOW_ROUTES if isinstance(top, cls)))]
     cols = list(dict.fromkeys(col for col in measured if col is not None))
@@ -1762,7 +1766,7 @@ def _order_spec(top, spec_of, decoded_of):
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude") and _term_text(t) is not None]}
     if isinstance(top, tuple(cls for cls, *_ in _WINDOW_ROUTES)):      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
     if isinstance(top, FrameRequest):                        # the aggregates in the order of their columns
@@ -1771,6 +1775,8 @@ def _note_order_route(eng, top, spec, route):
         note["slides"] = [list(a) for a in top.slides]
     elif isinstance(top, RangeRequest):                      # and the frames' unit
         note["unit"], note["ranges"] = top.unit, [list(a) for a in top.ranges]
+    elif isinstance(top, ExcludeRequest):                    # what is taken out, and the frames with their own units
+        note["exclude"], note["frames"] = top.exclude, [list(a) for a in top.frames]
     elif isinstance(top, QuantileRequest):                   # and the per-group limit it filters by
         note["per_limit"], note["quantiles"] = int(min(top.per_limit, abi.SORT_ALL)), [list(a) for a in top.quants]
     elif isinstance(top, WindowRequest):
@@ -1815,6 +1821,11 @@ def _finish_top(rs, ordered, top):
             if name in rs.columns:
                 raise KeyError("ranged: the result already has a column %r" % name)
         return ResultSet(rs.columns + [a[0] for a in top.ranges], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
+    if isinstance(top, ExcludeRequest):                     # the device's frames, a column each
+        for name in (a[0] for a in top.frames):
+            if name in rs.columns:
+                raise KeyError("excluding: the result already has a column %r" % name)
+        return ResultSet(rs.columns + [a[0] for a in top.frames], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
     if isinstance(top, QuantileRequest):                    # the device's columns, one each
         for name in (a[0] for a in top.quants):
             if name in rs.columns:
@@ -1899,6 +1910,9 @@ def _order_route(eng, top, spec):
     "window_quantile" abi.Context.table_window_quantile: a QuantileRequest under "window_slide"'s conditions (at most WQUANT_MAX_COLS
                  columns, underived numeric measures, NTH's default within 2^53 for a column kept as integer-valued doubles; the window
                  quantile extension and Engine.device_window_quantile on; terms as for "window")
+    "window_exclude" abi.Context.table_window_exclude: an ExcludeRequest under "window_range"'s conditions (at most WEX_MAX_COLS columns;
+                 the window exclude extension and Engine.device_window_exclude on): its "value" columns' offsets are taken as a
+                 RangeRequest's are, "groups" and "rows" columns take ints (_exclude_offsets)
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1910,9 +1924,14 @@ def _order_route(eng, top, spec):
     terms_ok = not derived or on("device_sort", "has_sort_terms")
     for cls, route, switch, extension, items, limit in _WINDOW_ROUTES:
         if isinstance(top, cls):
-            fits = _columns_fit(None if items is None else getattr(top, items), limit, spec)
+            cols = None if items is None else getattr(top, items)
+            if cls is ExcludeRequest:                            # (a frame's default is its seventh member: read as a range's, its sixth — an
+                cols = [(name, op, col, lo, hi, None if op == "avg" else default) for name, op, col, _, lo, hi, default in cols]      # average's is a plain double, never written back as an integer)
+            fits = _columns_fit(cols, limit, spec)
             if fits and cls is RangeRequest:
                 fits = _range_offsets(top, spec) is not None
+            if fits and cls is ExcludeRequest:
+                fits = _exclude_offsets(top, spec) is not None
             return route if fits and on(switch, extension) and terms_ok else "host"
     if derived:
         return "sorted_by" if k >= 1 and n <= abi.SORT_MAX_KEYS and terms_ok else "host"
@@ -1960,10 +1979,36 @@ def _range_offsets(top, spec):
     return out
 
 
+def _exclude_offsets(top, spec):
+    """The offsets [(lo, hi)] of an ExcludeRequest's frames as the device takes them, or None where it cannot: every column's through
+    _range_offsets, as a RangeRequest of its unit — "rows" offsets are ints, as "groups" offsets are."""
+    out = []
+    for name, op, col, unit, lo, hi, default in top.frames:
+        one = _range_offsets(RangeRequest(top[0], top[1], top.npartition, "value" if unit == "value" else "groups", [(name, "count" if op == "avg" else op, col, lo, hi, default)]), spec)
+        if one is None:
+            return None
+        out += one
+    return out
+
+
+def _exclude_columns(top, spec):
+    """The columns of an ExcludeRequest as abi.Context.table_window_exclude takes them.  An average is a double whatever it measures:
+    its default is one too — never put through the measure's own dtype, which refuses a float for an int64 column."""
+    cols = []
+    for (_, op, measure, unit, _, _, default), col, (lo, hi) in zip(top.frames, spec.measures, _exclude_offsets(top, spec)):
+        if op == "avg":
+            kind, index, is_f64, _ = _measure_args(col, measure, None, spec, None)
+            empty = int(np.array(slide_empty(default, True, "excluding")).view(np.int64))
+        else:
+            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "excluding")
+        cols.append((EXCLUDE_OPS.index(op), kind, index, is_f64, EXCLUDE_UNITS.index(unit), lo, hi, empty, EXCLUDES.index(top.exclude)))
+    return cols
+
+
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
-    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range" and "window_quantile" of _order_route: one waited-for call whose arrays are sized from the previous run
+    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile" and "window_exclude" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -1988,6 +2033,8 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
             kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "ranged")
             ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
         got = eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
+    elif route == "window_exclude":
+        got = eng.ctx.table_window_exclude(table, min_hits, top.npartition, terms, _exclude_columns(top, spec), k, cap, want_hits=want_hits)
     elif route == "window_quantile":
         quants = []
         for (_, fn, measure, arg, p, default), col in zip(top.quants, spec.measures):
@@ -2092,6 +2139,8 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         if isinstance(ordered, _Ranked) and isinstance(top, QuantileRequest):   # likewise for what is copied (nth, percentile_disc); a percentile_cont of such a
             ordered.rank = [np.rint(a).astype(np.int64) if fn in ("nth", "percentile_disc") and col in bt.int_values else a     # column read its doubles as they are
                             for a, (_, fn, col, _, _, _) in zip(ordered.rank, top.quants)]
+        if isinstance(ordered, _Ranked) and isinstance(top, ExcludeRequest):    # likewise; an average stays the double it is
+            ordered.rank = [np.rint(a).astype(np.int64) if op not in ("count", "avg") and col in bt.int_values else a for a, (_, op, col, _, _, _, _) in zip(ordered.rank, top.frames)]
         if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
@@ -2229,7 +2278,7 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
@@ -2244,6 +2293,8 @@ def _finalize(eng, op, env, top=None):
             route["slides"] = [list(a) for a in top.slides]
         if isinstance(top, RangeRequest):
             route["ranges"] = [list(a) for a in top.ranges]
+        if isinstance(top, ExcludeRequest):
+            route["frames"] = [list(a) for a in top.frames]
         if isinstance(top, QuantileRequest):
             route["quantiles"] = [list(a) for a in top.quants]
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected

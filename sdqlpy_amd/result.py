@@ -140,6 +140,11 @@ def check_window_columns(req, columns):
             raise KeyError("ranged: the result has no column %r" % col)
         if name in columns:
             raise KeyError("ranged: the result already has a column %r" % name)
+    for name, _, col, _, _, _, _ in getattr(req, "frames", ()):
+        if col is not None and col not in columns:
+            raise KeyError("excluding: the result has no column %r" % col)
+        if name in columns:
+            raise KeyError("excluding: the result already has a column %r" % name)
     for name, _, col, _, _, _ in getattr(req, "quants", ()):
         if col is not None and col not in columns:
             raise KeyError("quantiles: the result has no column %r" % col)
@@ -303,13 +308,13 @@ class RangeRequest(WindowRequest):
         return RangeRequest(self[0], terms, self.npartition, self.unit, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.ranges])
 
 
-def _range_offset(x, unit):
-    """A frame offset of `ranged`: an int, or — unit "value" only — a finite float."""
+def _range_offset(x, unit, who="ranged"):
+    """A frame offset of `ranged` (or `excluding`): an int, or — unit "value" only — a finite float."""
     if not isinstance(x, bool) and isinstance(x, (int, np.integer)):
         return int(x)
     if unit == "value" and isinstance(x, (float, np.floating)) and np.isfinite(x):
         return float(x)
-    raise ValueError("ranged: a bound is %s, not %r" % ("an integer or a finite float" if unit == "value" else "an integer", x))
+    raise ValueError("%s: a bound is %s, not %r" % (who, "an integer or a finite float" if unit == "value" else "an integer", x))
 
 
 def range_request(columns, by, order, aggs, unit="value", k=WINDOW_ALL):
@@ -358,6 +363,80 @@ def _range_int_offset(x):
     if float(x) != int(x):
         raise ValueError("ranged: the offset %r over an integer column is not an integer" % (x,))
     return int(x)
+
+
+EXCLUDES = ("no others", "current row", "group", "ties")      # their positions are abi.WEX_NO_OTHERS .. WEX_TIES
+EXCLUDE_UNITS = ("value", "groups", "rows")                   # ... abi.WRANGE_VALUE / WRANGE_GROUPS / WEX_ROWS
+EXCLUDE_OPS = SLIDE_OPS + ("avg",)                            # ... abi.WAGG_SUM .. WSLIDE_LAST, WEX_AVG
+
+
+class ExcludeRequest(WindowRequest):
+    """Values over window frames with rows taken out, travelling where a RangeRequest travels (every row is kept): [0] = the limit on
+    the whole result, [1] = the PARTITION BY terms followed by the ORDER BY terms, npartition, exclude (a name of EXCLUDES: what is cut
+    out of every frame) and frames = [(name of the new column, op: a name of EXCLUDE_OPS, measure column or None for a count, unit: a
+    name of EXCLUDE_UNITS — the column's own —, lo, hi: the frame's offsets in that unit, negative = preceding, None = unbounded,
+    default: what a column gives where nothing remains, None = 0 for an int64 column and NaN for a float64 one)] in the order the
+    columns are appended."""
+
+    def __new__(cls, k, terms, npartition, exclude, frames):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.exclude = str(exclude)
+        self.frames = [(str(n), str(op), None if col is None else str(col), str(unit), lo, hi, default) for n, op, col, unit, lo, hi, default in frames]
+        if self.exclude not in EXCLUDES or not self.frames or any(op not in EXCLUDE_OPS or unit not in EXCLUDE_UNITS or (col is None and op != "count") or
+                                                                   (lo is not None and hi is not None and lo > hi) for _, op, col, unit, lo, hi, _ in self.frames):
+            raise ValueError("excluding: bad aggregate")
+        if any(unit == "value" for _, _, _, unit, _, _, _ in self.frames) and len(terms) != npartition + 1:
+            raise ValueError("excluding: a value frame is ordered by exactly one column")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
+        names = names or {}
+        return ExcludeRequest(self[0], terms, self.npartition, self.exclude, [(n, op, names.get(col, col), unit, lo, hi, d) for n, op, col, unit, lo, hi, d in self.frames])
+
+
+def exclude_request(columns, by, order, aggs, exclude="current row", unit="rows", k=WINDOW_ALL):
+    """The checked ExcludeRequest of `excluding`: by / order as window_request takes them; exclude a name of EXCLUDES; unit a name of
+    EXCLUDE_UNITS, the unit of every column that names none; aggs = {new column: (op, measure column or None, lo, hi[, default]) or
+    (op, measure, lo, hi, default, unit)} with op a name of EXCLUDE_OPS and lo / hi offsets in the column's unit (negative =
+    preceding, None = unbounded): ints, or floats as well for unit "value".  columns: the result's column names when they are known
+    (None: checked when the result is).  The checks and their errors are range_request's: KeyError for a column the result lacks or
+    a new column it has already, ValueError for everything else."""
+    req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    if exclude not in EXCLUDES:
+        raise ValueError("excluding: exclude is one of %s, not %r" % (", ".join(EXCLUDES), exclude))
+    if unit not in EXCLUDE_UNITS:
+        raise ValueError("excluding: unit is one of %s, not %r" % (", ".join(EXCLUDE_UNITS), unit))
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("excluding: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default[, unit]])}")
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5, 6):
+            raise ValueError("excluding: an aggregate is name: (op, measure, lo, hi[, default[, unit]])")
+        op, col = spec[0], spec[1]
+        own = spec[5] if len(spec) == 6 else unit
+        if op not in EXCLUDE_OPS:
+            raise ValueError("excluding: op is one of %s, not %r" % (", ".join(EXCLUDE_OPS), op))
+        if own not in EXCLUDE_UNITS:
+            raise ValueError("excluding: a column's unit is one of %s, not %r" % (", ".join(EXCLUDE_UNITS), own))
+        if own == "value" and len(req[1]) != req.npartition + 1:
+            raise ValueError("excluding: a value frame is ordered by exactly one column, not %d" % (len(req[1]) - req.npartition))
+        lo = None if spec[2] is None else _range_offset(spec[2], own, "excluding")
+        hi = None if spec[3] is None else _range_offset(spec[3], own, "excluding")
+        default = spec[4] if len(spec) >= 5 else None
+        if lo is not None and hi is not None and lo > hi:
+            raise ValueError("excluding: the frame (%r, %r) ends before it starts" % (lo, hi))
+        if col is None and op != "count":
+            raise ValueError("excluding: %s needs a measure column" % op)
+        if col is not None and not isinstance(col, str):
+            raise ValueError("excluding: a measure is a column name")
+        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
+            raise ValueError("excluding: a default is a number, not %r" % (default,))
+        out.append((name, op, col, own, lo, hi, default))
+    req = ExcludeRequest(req[0], req[1], req.npartition, exclude, out)
+    if columns is not None:
+        check_window_columns(req, columns)
+    return req
 
 
 QUANTILE_FNS = ("ntile", "percent_rank", "cume_dist", "nth", "percentile_disc", "percentile_cont")     # their positions are abi.WQ_NTILE .. WQ_PERCENTILE_CONT
@@ -719,19 +798,7 @@ class ResultSet:
         stops = np.append(heads[1:], n)
         end = (stops - 1)[np.cumsum(part_head) - 1] if n else pos
         top = np.uint64(1) << np.uint64(63)
-        desc, is_fv = False, False
-        if req.unit == "groups":
-            g = np.cumsum(tie_head).astype(np.int64)
-            key = (g - g[start] + 1 if n else g).view(np.uint64) ^ top
-            v = key
-        else:
-            (name, direction), = req.order
-            col = self.column(name)
-            if col.dtype.kind not in "iubf":
-                raise ValueError("ranged: a value frame over column %r: the order column is not numeric" % name)
-            desc, is_fv = direction == "desc", col.dtype.kind == "f"
-            v = np.ascontiguousarray(col[idx], np.float64 if is_fv else np.int64)
-            key = order_image(v, desc)
+        keys = self._range_keys(req.unit, req.order, idx, start, tie_head, "ranged")
         new = []
         for name, op, col, lo, hi, default in req.ranges:
             x = None if op == "count" else self.column(col)[idx]
@@ -739,19 +806,7 @@ class ResultSet:
                 raise ValueError("ranged: %s of column %r: the measure is not numeric" % (op, col))
             is_f = x is not None and x.dtype.kind == "f"
             fill = None if op == "count" else slide_empty(default, is_f, "ranged")
-            # per side: the key searched for, and where no search is needed whether every row of the partition lies inside (all) or none
-            if is_fv:
-                sides = _range_f64_bounds(v, key, None if lo is None else float(lo), None if hi is None else float(hi), desc)
-            else:
-                vj = (key ^ top).view(np.int64) if req.unit == "groups" else v
-                sides = (_range_int_bound(vj, _range_int_offset(lo), desc, True), _range_int_bound(vj, _range_int_offset(hi), desc, False))
-            (kl, all_l, none_l), (kr, all_r, none_r) = sides
-            left, right = np.empty(n, np.int64), np.empty(n, np.int64)
-            for a, b in zip(heads, stops):                              # the ends of every row's frame inside its partition [a, b)
-                left[a:b] = a + np.searchsorted(key[a:b], kl[a:b], "left")
-                right[a:b] = a + np.searchsorted(key[a:b], kr[a:b], "right") - 1
-            left, right = np.where(all_l, start, left), np.where(all_r, end, right)
-            empty = none_l | none_r | (left > right)
+            left, right, empty = _range_ends(req.unit, keys, lo, hi, heads, stops, start, end)
             a, b = np.where(empty, pos, left), np.where(empty, pos, right)       # (an empty frame reads its own row, then takes the default)
             if op == "count":
                 new.append((name, np.where(empty, 0, right - left + 1).astype(np.int64)))
@@ -778,6 +833,127 @@ class ResultSet:
         k = max(0, min(int(req[0]), n))
         cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
         return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:k] for _, c in new])
+
+    def _range_keys(self, unit, order, idx, start, tie_head, who):
+        """What the ends of a value or group frame are searched in: (one ordered uint64 key per sorted position — the order_image of
+        the one ORDER BY column (unit "value"), the image of the tie run's number inside the partition (unit "groups") —, the order
+        values themselves, is the order descending, are the values doubles)."""
+        n = self._n
+        top = np.uint64(1) << np.uint64(63)
+        if unit == "groups":
+            g = np.cumsum(tie_head).astype(np.int64)
+            key = (g - g[start] + 1 if n else g).view(np.uint64) ^ top
+            return key, key, False, False
+        (name, direction), = order
+        col = self.column(name)
+        if col.dtype.kind not in "iubf":
+            raise ValueError("%s: a value frame over column %r: the order column is not numeric" % (who, name))
+        desc, is_fv = direction == "desc", col.dtype.kind == "f"
+        v = np.ascontiguousarray(col[idx], np.float64 if is_fv else np.int64)
+        return order_image(v, desc), v, desc, is_fv
+
+    def excluded(self, req):
+        """Every row in an ExcludeRequest's order (the first req[0] of them) with its columns appended: what sdqh_table_window_exclude
+        does on the device (include/sdqh_sort_exclude.h), on the host.  The base frame's ends as slid (unit "rows") or ranged_by
+        ("value", "groups") find them; then the excluded interval around the row — the row itself, or its tie run with or without
+        it — cuts the frame into at most three pieces in position order.  COUNT adds their lengths, FIRST / LAST gather at the first
+        / last remaining position, an integer SUM adds the pieces' differences of wrapping prefix sums (exact mod 2^64); a double
+        SUM and MIN / MAX fold every piece through ranged_by's fold tree and join the pieces left to right: nothing is subtracted.
+        AVG is that SUM as a float64 divided by the count as a float64, one division."""
+        self._wait()
+        check_window_columns(req, self.columns)
+        idx, part_head, tie_head = self._window_heads(req.by, req.order)
+        n = self._n
+        pos = np.arange(n, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(part_head, pos, 0)) if n else pos
+        heads = np.nonzero(part_head)[0]
+        stops = np.append(heads[1:], n)
+        end = (stops - 1)[np.cumsum(part_head) - 1] if n else pos
+        tie_a = np.maximum.accumulate(np.where(tie_head, pos, 0)) if n else pos         # the tie run [tie_a, tie_b] of every position
+        ties = np.nonzero(tie_head)[0]
+        tie_b = (np.append(ties[1:], n) - 1)[np.cumsum(tie_head) - 1] if n else pos
+        top = np.uint64(1) << np.uint64(63)
+        keys = {}
+        new = []
+        for name, op, col, unit, lo, hi, default in req.frames:
+            x = None if op == "count" else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("excluding: %s of column %r: the measure is not numeric" % (op, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            fill = None if op == "count" else slide_empty(default, is_f or op == "avg", "excluding")
+            if unit == "rows":
+                lo_c = -n if lo is None else max(-n, min(n, lo))         # an offset of n or more leaves every partition
+                hi_c = n if hi is None else max(-n, min(n, hi))
+                left, right = np.maximum(pos + lo_c, start), np.minimum(pos + hi_c, end)
+                empty = left > right
+            else:
+                if unit not in keys:
+                    keys[unit] = self._range_keys(unit, req.order, idx, start, tie_head, "excluding")
+                left, right, empty = _range_ends(unit, keys[unit], lo, hi, heads, stops, start, end)
+            # the hull [x0, x1] of what is taken out, and the pieces [a1, b1], {pos} (mid), [a3, b3] that remain
+            if req.exclude == "no others":
+                x0, x1 = right + 1, right
+            elif req.exclude == "current row":
+                x0, x1 = pos, pos
+            else:
+                x0, x1 = tie_a, tie_b
+            a1, b1, a3, b3 = left, np.minimum(right, x0 - 1), np.maximum(left, x1 + 1), right
+            p1, p3 = ~empty & (a1 <= b1), ~empty & (a3 <= b3)
+            mid = ~empty & (left <= pos) & (pos <= right) if req.exclude == "ties" else np.zeros(n, bool)
+            count = (np.where(p1, b1 - a1 + 1, 0) + mid + np.where(p3, b3 - a3 + 1, 0)).astype(np.int64)
+            if op == "count":
+                new.append((name, count))
+                continue
+            none = count == 0
+            x = np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+            pieces = [(p1, np.where(p1, a1, pos), np.where(p1, b1, pos)), (mid, pos, pos), (p3, np.where(p3, a3, pos), np.where(p3, b3, pos))]      # (an empty piece reads its own row and is left out)
+            if op in ("first", "last"):
+                at = np.where(p1, a1, np.where(mid, pos, a3)) if op == "first" else np.where(p3, b3, np.where(mid, pos, b1))
+                val = x[np.where(none, pos, at)]
+            else:
+                if op in ("sum", "avg") and not is_f:
+                    c = np.concatenate((np.zeros(1, np.uint64), np.cumsum(x.view(np.uint64), dtype=np.uint64)))
+                    val = np.zeros(n, np.uint64)
+                    for has, a, b in pieces:
+                        val = val + np.where(has, c[b + 1] - c[a], np.uint64(0))
+                    val = val.view(np.int64)
+                else:
+                    if op in ("sum", "avg"):
+                        e, fold, identity = x, np.add, np.float64(-0.0)
+                    else:                                                # unsigned maximum of the images, reversed for MIN, NaN = 0
+                        e, fold, identity = order_image(x, op == "min"), np.maximum, np.uint64(0)
+                        e = np.where(np.isnan(x), np.uint64(0), e) if is_f else e
+                    val, have = np.full(n, identity, e.dtype), np.zeros(n, bool)
+                    with np.errstate(invalid="ignore", over="ignore"):
+                        for has, a, b in pieces:
+                            if has.any():
+                                q = _tree_fold(e, fold, identity, a, b)
+                                val = np.where(has, np.where(have, fold(val, q), q), val)
+                                have = have | has
+                    if op in ("min", "max"):
+                        u = ~val if op == "min" else val
+                        if is_f:
+                            val = np.where(val == 0, np.uint64(0x7FF8000000000000), np.where(u >> np.uint64(63) != 0, u ^ top, ~u)).view(np.float64)
+                        else:
+                            val = (u ^ top).view(np.int64)
+                if op == "avg":
+                    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+                        val = val.astype(np.float64) / np.where(none, 1, count).astype(np.float64)
+            out_f = is_f or op == "avg"
+            bits = np.where(none, np.array(fill).view(np.uint64), np.ascontiguousarray(val).view(np.uint64))      # (by bits: a NaN default keeps its payload)
+            new.append((name, bits.view(np.float64 if out_f else np.int64)))
+        k = max(0, min(int(req[0]), n))
+        cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:k] for _, c in new])
+
+    def excluding(self, by, order, aggs, exclude="current row", unit="rows"):
+        """Every row, ordered by `by` then `order`, plus one column per aggregate over a frame inside the row's group of `by` with rows
+        taken out of it: aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in EXCLUDE_OPS ("avg" among them),
+        the frame in `unit` — "rows" (the rows [row + lo, row + hi]), "value" or "groups" (ranged's frames) — or a 6-tuple (op,
+        measure, lo, hi, default, unit) for a column with a unit of its own.  exclude: "current row", "group" (the row and the rows
+        tied with it), "ties" (those rows but not the row itself) or "no others".  Nothing left gives `default` (0 / NaN), a count 0;
+        an avg is float64."""
+        return self.excluded(exclude_request(self.columns, by, order, aggs, exclude, unit))
 
     def ranged(self, by, order, aggs, unit="value"):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a value or group frame inside the row's group of
@@ -871,6 +1047,8 @@ class ResultSet:
             return self.slid(req)
         if isinstance(req, RangeRequest):
             return self.ranged_by(req)
+        if isinstance(req, ExcludeRequest):
+            return self.excluded(req)
         if isinstance(req, QuantileRequest):
             return self.quantiled(req)
         self._wait()
@@ -1012,6 +1190,28 @@ def _range_int_bound(v, off, desc, lo_side):
     out = over | under
     every = (over != desc) != lo_side
     return key, out & every, out & ~every
+
+
+def _range_ends(unit, keys, lo, hi, heads, stops, start, end):
+    """(first position, last position, is it empty) of every row's value or group frame [lo, hi] inside its partition — heads / stops:
+    the partitions [a, b); start / end: per position — by two np.searchsorted over the partition's keys (keys: ResultSet._range_keys')
+    against bounds made without a wrapping add."""
+    key, v, desc, is_fv = keys
+    n = len(key)
+    top = np.uint64(1) << np.uint64(63)
+    # per side: the key searched for, and where no search is needed whether every row of the partition lies inside (all) or none
+    if is_fv:
+        sides = _range_f64_bounds(v, key, None if lo is None else float(lo), None if hi is None else float(hi), desc)
+    else:
+        vj = (key ^ top).view(np.int64) if unit == "groups" else v
+        sides = (_range_int_bound(vj, _range_int_offset(lo), desc, True), _range_int_bound(vj, _range_int_offset(hi), desc, False))
+    (kl, all_l, none_l), (kr, all_r, none_r) = sides
+    left, right = np.empty(n, np.int64), np.empty(n, np.int64)
+    for a, b in zip(heads, stops):                              # the ends of every row's frame inside its partition [a, b)
+        left[a:b] = a + np.searchsorted(key[a:b], kl[a:b], "left")
+        right[a:b] = a + np.searchsorted(key[a:b], kr[a:b], "right") - 1
+    left, right = np.where(all_l, start, left), np.where(all_r, end, right)
+    return left, right, none_l | none_r | (left > right)
 
 
 def _range_f64_bounds(v, key, lo, hi, desc):

@@ -457,6 +457,24 @@ def sdql_compile(in_type):
             req = range_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, unit)     # checked before anything is launched
             return lambda *args: run(args, req)
 
+        def excluding(by, order, aggs, exclude="current row", unit="rows"):
+            """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a frame inside the row's group of
+            `by` with rows TAKEN OUT of it (EXCLUDE): aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in
+            "sum" / "count" / "min" / "max" / "first" / "last" / "avg", the frame in `unit` — "rows" (sliding's frames), "value" or
+            "groups" (ranged's) — or (op, measure, lo, hi, default, unit) for a column with a unit of its own: frames of different
+            units share one sort.  exclude: "current row", "group" (the row and the rows tied with it), "ties" (those rows, but
+            not the row itself) or "no others", e.g. ``q3.excluding(["o_orderdate"], [("revenue", "desc")], {"others": ("avg",
+            "revenue", None, None)})(li, cu, ord)`` — the average revenue of the day's other orders.  Where nothing remains a column
+            gives `default` (0 for an int64 column, NaN for a float64 one), a count 0; an avg is float64.  Names, ops, units and
+            bounds are checked here, before anything is launched; what depends on a column's dtype can only be told once the query
+            has run: that ValueError comes from the call."""
+            from . import engine, frontend
+            from .result import exclude_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = exclude_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, exclude, unit)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         def quantiles(by, order, cols, per=None):
             """The same query finished with ORDER BY `by`, `order` and one column per function of the size of the row's group of `by`:
             cols = {new column: ("ntile", b) | ("percent_rank",) | ("cume_dist",) | ("nth", measure, k[, default]) |
@@ -482,6 +500,7 @@ def sdql_compile(in_type):
         wrapper.over = over
         wrapper.sliding = sliding
         wrapper.ranged = ranged
+        wrapper.excluding = excluding
         wrapper.quantiles = quantiles
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
