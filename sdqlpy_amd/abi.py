@@ -61,7 +61,11 @@ WEX_ROWS = 2                                     # a unit beside WRANGE_VALUE / 
 WEX_AVG = 6                                      # an op beside WAGG_SUM .. WSLIDE_LAST
 WEX_NO_OTHERS, WEX_CURRENT_ROW, WEX_GROUP, WEX_TIES = 0, 1, 2, 3
 WEX_MAX_COLS = 4
-# the six of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
+# ... and its ninth (include/sdqh_sort_groups.h, Library.has_grouping_sets): the ordered entries re-grouped — GROUP BY ROLLUP / CUBE /
+# GROUPING SETS: one row per group at several nested levels of one key list, SUM / COUNT / MIN / MAX / AVG per group
+GROUPING_SETS_EXPORTS = ["sdqh_table_grouping_sets", "sdqh_grouping_sets_geometry"]
+GS_MAX_AGGS = 4
+# all of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
     "has_window_agg": (WINDOW_AGG_EXPORTS, "sdqh_sort_frames.h", "window aggregate", "has_window"),
@@ -69,6 +73,7 @@ WINDOW_EXTENSIONS = {
     "has_window_range": (WINDOW_RANGE_EXPORTS, "sdqh_sort_range.h", "window range", "has_window_slide"),
     "has_window_quantile": (WINDOW_QUANTILE_EXPORTS, "sdqh_sort_quantile.h", "window quantile", "has_window_slide"),
     "has_window_exclude": (WINDOW_EXCLUDE_EXPORTS, "sdqh_sort_exclude.h", "window exclude", "has_window_range"),
+    "has_grouping_sets": (GROUPING_SETS_EXPORTS, "sdqh_sort_groups.h", "grouping sets", "has_window_agg"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -172,6 +177,11 @@ class WindowExclude(C.Structure):
     (WEX_NO_OTHERS / WEX_CURRENT_ROW / WEX_GROUP / WEX_TIES)."""
     _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32),
                 ("exclude", C.c_int32), ("_pad", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64), ("empty", C.c_int64)]
+
+
+class GroupAgg(C.Structure):
+    """sdqh_group_agg: an op (WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX / WEX_AVG) and its measure, named as a SortKey names a column."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32)]
 
 
 class WindowQuantile(C.Structure):
@@ -1238,12 +1248,13 @@ class Context:
         n = n.value
         return (keys[:n], None if payload is None else payload[:, :n], None if values is None else values[:, :n], None if hits is None else hits[:n])
 
-    def _sorted_call(self, name, table, lead, limit, capacity_hint, want_hits, want_rank=None, naggs=0):
+    def _sorted_call(self, name, table, lead, limit, capacity_hint, want_hits, want_rank=None, naggs=0, trail=()):
         """What sdqh_table_sorted, sdqh_table_sorted_by, sdqh_table_window and sdqh_table_window_agg share: arrays sized from
         capacity_hint, one retry with the exact size after SDQH_ERR_OVERFLOW, the rows sliced to what was written.  lead: the call's
         arguments between the table and the capacity (the marshalled sort columns / terms among them).  want_rank None: the call has
         no rank array and a 4-tuple is returned; else a 5-tuple whose last member is the ranks, or None without want_rank.  naggs:
-        the last array is naggs x capacity (the aggregates of sdqh_table_window_agg) and the last member its rows, (naggs, n)."""
+        the last array is naggs x capacity (the aggregates of sdqh_table_window_agg) and the last member its rows, (naggs, n).  trail:
+        the call's arguments between that array and the count (the level counts of sdqh_table_grouping_sets)."""
         fn = getattr(self.lib, "sdqh_" + name)
         cap = max(1, min(int(capacity_hint), int(limit)))
         for attempt in (0, 1):
@@ -1254,7 +1265,7 @@ class Context:
             rank = np.empty((naggs, cap) if naggs else cap, np.int64) if want_rank else None
             n = C.c_int64()
             outs = (_np_ptr(keys), _np_ptr(payload), _np_ptr(values), _np_ptr(hits)) + (() if want_rank is None else (_np_ptr(rank),))
-            rc = fn(self.handle, table.handle, *lead, C.c_int64(cap), *outs, C.byref(n))
+            rc = fn(self.handle, table.handle, *lead, C.c_int64(cap), *outs, *trail, C.byref(n))
             if rc == ERR_OVERFLOW and attempt == 0:
                 cap = max(1, n.value)
                 continue
@@ -1442,6 +1453,38 @@ class Context:
     def window_quantile_geometry(self):
         """Sorted positions per tile of sdqh_table_window_quantile's passes: what the tests size their cases from."""
         return self._window_geometry("has_window_quantile", 1)
+
+    def table_grouping_sets(self, table, min_hits, terms, levels, aggs, limit, capacity, want_hits=True):
+        """The ordered entries re-grouped at nested levels: terms as table_sorted_by takes them, all of them grouping terms; levels: bit
+        L asks for the groups whose first L terms are equal (0: the whole selection, len(terms): the distinct combinations); aggs:
+        [(op, kind, index, is_f64)] — op in WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX / WEX_AVG, the measure as a sort column is named
+        (COUNT ignores it), at most GS_MAX_AGGS.  One row per group — its first sorted row —, the levels from the highest down, sorted
+        inside a level; the first min(limit, groups).  The arrays are sized from `capacity`; a result that does not fit is fetched
+        again with the exact size.  Returns (keys, payload, values, hits, aggs, level_rows) — aggs one array per aggregate: float64
+        for an AVG and for a double measure under any op but COUNT, else int64; level_rows[L]: the groups of level L before limit."""
+        self._need("has_grouping_sets", "table_grouping_sets")
+        arr = (GroupAgg * max(1, len(aggs)))()
+        for i, (op, kind, index, is_f64) in enumerate(aggs):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
+        as_f64 = [op == WEX_AVG or (op != WAGG_COUNT and _measure_is_f64(kind, is_f64)) for op, kind, _, is_f64 in aggs]
+        level_rows = np.zeros(SORT_MAX_KEYS + 1, np.int64)
+        lead = (C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_uint32(levels), C.c_int(len(aggs)), arr, C.c_int64(limit))
+        got = self._sorted_call("table_grouping_sets", table, lead, limit, capacity, want_hits, bool(aggs), naggs=max(1, len(aggs)), trail=(_np_ptr(level_rows),))
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)], level_rows)
+
+    def table_grouping_sets_count(self, table, min_hits, terms, levels, limit=SORT_ALL):
+        """The count-only call of table_grouping_sets: (min(limit, groups), level_rows) — the sort and the level pass run, no row is fetched."""
+        self._need("has_grouping_sets", "table_grouping_sets")
+        level_rows = np.zeros(SORT_MAX_KEYS + 1, np.int64)
+        n = C.c_int64()
+        self._check(self.lib.sdqh_table_grouping_sets(self.handle, table.handle, C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_uint32(levels),
+                                                      C.c_int(0), None, C.c_int64(limit), C.c_int64(0), None, None, None, None, None, _np_ptr(level_rows), C.byref(n)))
+        self._after_call("table_grouping_sets")
+        return n.value, level_rows
+
+    def grouping_sets_geometry(self):
+        """Sorted positions (and, at a lower level, groups) per tile of sdqh_table_grouping_sets' passes: what the tests size their cases from."""
+        return self._window_geometry("has_grouping_sets", 1)
 
     def _need_extrema(self, what):
         if not self.library.has_extrema:
@@ -1719,6 +1762,10 @@ class Library:
             L.sdqh_table_window_exclude.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_window_exclude_geometry.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        if self.has_grouping_sets:
+            L.sdqh_table_grouping_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_grouping_sets_geometry.argtypes = [C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

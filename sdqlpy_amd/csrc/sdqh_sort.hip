@@ -111,6 +111,15 @@
 //                     only with a GROUP / TIES column: the first tie head of every tile for k_wagg_next to scan, the RANK of every
 //                     position (its tie run's first offset + 1) and, backwards, its tie run's last position
 //   k_wex_fold        per row and column the base frame's ends, the cut into at most three pieces, a tree query per piece — see the section
+//   GROUPS            in their place (STEP_GROUPS).  sdqh_table_grouping_sets (include/sdqh_sort_groups.h) returns one row per GROUP at
+//                     several nested levels of the terms — GROUP BY ROLLUP / CUBE / GROUPING SETS — with SUM / COUNT / MIN / MAX / AVG:
+//
+//   k_gs_depth        per position the number of leading terms equal to its predecessor's (the heads of every level in one byte), per
+//                     tile and level the heads; k_sort_bins scans them, the level counts go to the host (the count is known only now)
+//   k_wagg_tiles / k_wagg_scan / k_gs_run
+//                     the highest level over the rows: the frames' tile scan, the value at a group's last row kept in the group's slot
+//   k_gs_tiles / k_wagg_scan / k_sort_bins / k_gs_run
+//                     every lower level over the groups of the level above it; k_gs_avg divides the sums of an AVG — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -127,6 +136,7 @@
 #include "sdqh_sort_range.h"
 #include "sdqh_sort_quantile.h"
 #include "sdqh_sort_exclude.h"
+#include "sdqh_sort_groups.h"
 
 using namespace sdqh_host;
 
@@ -1412,6 +1422,157 @@ __global__ __launch_bounds__(TPB) void k_wex_fold(DevWexs ex, const uint32_t* __
     }
 }
 
+// ---- groups at nested levels (sdqh_table_grouping_sets) ---------------------------------------------------------------------------
+// The DEPTH of sorted position r is the number of leading terms whose keys equal those of r - 1 (position 0: 0).  r opens a level-L
+// group iff r == 0 or depth[r] < L, so one byte per position holds the heads of every level.  The levels asked for are folded from
+// the highest down: the highest over the rows (k_wagg_tiles' elements and tile carries, k_wagg_scan, then k_gs_run in the place of
+// k_wagg_run: the value at a group's last row goes to the group's slot), every lower one over the GROUPS of the level above it, which
+// carry their first row's depth and sorted position along — the same three passes (k_gs_tiles / k_wagg_scan / k_gs_run) over an
+// array as long as that level's group count, not n.  All levels write into one set of arrays, highest level first: the positions
+// are the emit's `sel`, the values the call's columns.  COUNT is a sum of ones, an AVG is folded as its SUM and divided at the end
+// by the count read off the positions (k_gs_avg).  No atomics: a group's slot is its head's rank among the heads.
+struct DevGsLevels { uint32_t off[SDQH_SORT_MAX_KEYS + 2]; int32_t n, _pad; };      // level k's groups are rows [off[k], off[k + 1]) of the output
+struct DevGsAvg { int32_t avg[SDQH_GS_MAX_AGGS], is_f64[SDQH_GS_MAX_AGGS]; };
+static_assert(SDQH_GS_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "the groups' folds are the frames'");
+
+// a group's value as k_gs_run left it (wagg_result) back as an element of its class
+__device__ __forceinline__ uint64_t gs_element(const DevWagg& g, uint64_t v) {
+    if (g.cls != WAGG_UMAX) return v;
+    if (g.sk.is_f64) { const double d = __longlong_as_double((long long)v); if (d != d) return 0ull; }
+    return sort_bits((int64_t)v, g.sk.is_f64, g.op == SDQH_WAGG_MIN);
+}
+// the heads of level L among 64 items at [b, ..): item j is one iff j == 0 or depth[j] < L
+struct GsBatch { uint64_t mh, hl; uint32_t first, d; bool head, last; };
+__device__ __forceinline__ GsBatch gs_batch(const uint8_t* __restrict__ depth, int L, uint64_t j, uint64_t r1, uint32_t n, uint64_t le) {
+    GsBatch h;
+    const bool live = j < r1;
+    h.d = live ? depth[j] : 255u;
+    h.head = live && (j == 0 || (int)h.d < L);
+    h.last = live && (j + 1 >= n || (int)depth[j + 1] < L);              // the item closes its group
+    h.mh = __ballot(h.head);
+    h.hl = h.mh & le;
+    h.first = h.hl ? 63u - (uint32_t)__clzll((long long)h.hl) : 0u;
+    return h;
+}
+
+// 1. the depth of every position, the head flags of level `top` as k_wagg_tiles reads them, and per tile and level 0 .. nterms the
+// number of heads: tcount[L * ntiles + tile]
+__global__ __launch_bounds__(TPB) void k_gs_depth(const uint64_t* __restrict__ keys, size_t key_stride, int nterms, int top, const uint32_t* __restrict__ perm, uint32_t n,
+                                                 uint8_t* __restrict__ depth, uint8_t* __restrict__ heads, uint32_t* __restrict__ tcount, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    uint32_t cnt[SDQH_SORT_MAX_KEYS + 1];
+#pragma unroll
+    for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) cnt[L] = 0u;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        const bool live = r < r1;
+        int d = 0;
+        if (live && r > 0) {
+            const uint32_t g = perm ? perm[r] : (uint32_t)r, h = perm ? perm[r - 1] : (uint32_t)(r - 1);
+            if (g < n && h < n)                                          // (a permutation of [0, n): always)
+                while (d < nterms && keys[(size_t)d * key_stride + g] == keys[(size_t)d * key_stride + h]) ++d;
+        }
+        if (live) {
+            depth[r] = (uint8_t)d;
+            heads[r] = (uint8_t)((r == 0 || d < top) ? (WIN_PART | WIN_TIE) : 0u);
+        }
+#pragma unroll
+        for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) cnt[L] += (uint32_t)__popcll(__ballot(live && (r == 0 || d < L)));
+    }
+    if (lane_id() == 0) {
+#pragma unroll
+        for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) if (L <= nterms) tcount[(size_t)L * ntiles + w] = cnt[L];
+    }
+}
+// 2. a lower level over the n groups of the level above it (depth / val: theirs): per tile and aggregate the carry — the elements
+// folded since the tile's last head of level L, or over the whole tile — the tile's first head (what k_wagg_scan reads) and its
+// number of heads
+__global__ __launch_bounds__(TPB) void k_gs_tiles(DevWaggs ag, int L, const uint8_t* __restrict__ depth, const uint64_t* __restrict__ val, size_t stride, uint32_t n,
+                                                 uint64_t* __restrict__ tval, WaggHeads* __restrict__ tfirst, uint32_t* __restrict__ tcnt, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint64_t run[SDQH_WAGG_MAX_AGGS];
+#pragma unroll
+    for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) run[a] = wagg_identity(ag.a[a].cls);
+    WaggHeads fh = {n, n};
+    uint32_t cnt = 0u;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t j = b + lane;
+        const GsBatch h = gs_batch(depth, L, j, r1, n, le);
+        if (h.mh && fh.part == n) fh.part = fh.tie = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mh);
+        cnt += (uint32_t)__popcll(h.mh);
+        const int last = (int)min((uint64_t)WAVE, r1 - b) - 1;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) {
+            const int cls = ag.a[a].cls;
+            const uint64_t e = j < r1 ? gs_element(ag.a[a], val[(size_t)a * stride + j]) : wagg_identity(cls);
+            const uint64_t s = wagg_wave_scan(cls, e, lane, h.first);
+            const uint64_t tail = (uint64_t)__shfl((long long)s, last, WAVE);
+            run[a] = h.mh ? tail : wagg_join(cls, run[a], tail);
+        }
+    }
+    if (lane == 0) {
+        tfirst[w] = fh; tcnt[w] = cnt;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) tval[(size_t)a * ntiles + w] = run[a];
+    }
+}
+// 3. the tile again with its carry-in (tval: k_wagg_scan's) and the number of heads before it (toff): k_wagg_run's scan, but only
+// the value at a group's last item is kept — in slot toff + heads up to the item - 1 of the level's part of the output, where the
+// group's head leaves its depth and sorted position.  elems: val holds elements (the rows', k_wagg_tiles'), not group values;
+// pos == nullptr: item j is sorted position j.  A slot at or past `ng` is not written.
+__global__ __launch_bounds__(TPB) void k_gs_run(DevWaggs ag, int L, int elems, const uint8_t* __restrict__ depth, const uint32_t* __restrict__ pos, const uint64_t* __restrict__ val, size_t stride,
+                                               uint32_t n, const uint64_t* __restrict__ tval, const uint32_t* __restrict__ toff, uint32_t ntiles,
+                                               uint64_t* __restrict__ oval, size_t ostride, uint8_t* __restrict__ odepth, uint32_t* __restrict__ opos, uint32_t ng) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint64_t run[SDQH_WAGG_MAX_AGGS];
+#pragma unroll
+    for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) run[a] = a < ag.n ? tval[(size_t)a * ntiles + w] : 0ull;
+    uint32_t at0 = toff[w];
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t j = b + lane;
+        const bool live = j < r1;
+        const GsBatch h = gs_batch(depth, L, j, r1, n, le);
+        const uint32_t slot = at0 + (uint32_t)__popcll(h.hl) - 1u;       // (position 0 is a head: at least one lies at or below every item)
+        const bool ok = slot < ng;
+        if (h.head && ok) { odepth[slot] = (uint8_t)(j == 0 ? 0u : h.d); opos[slot] = pos ? pos[j] : (uint32_t)j; }
+        const int last = (int)min((uint64_t)WAVE, r1 - b) - 1;
+#pragma unroll
+        for (int a = 0; a < SDQH_WAGG_MAX_AGGS; ++a) if (a < ag.n) {
+            const int cls = ag.a[a].cls;
+            uint64_t e = wagg_identity(cls);
+            if (live) { e = val[(size_t)a * stride + j]; if (!elems) e = gs_element(ag.a[a], e); }
+            const uint64_t s = wagg_wave_scan(cls, e, lane, h.first);
+            const uint64_t v = h.hl ? s : wagg_join(cls, run[a], s);
+            if (h.last && ok) oval[(size_t)a * ostride + slot] = wagg_result(ag.a[a], v);
+            run[a] = (uint64_t)__shfl((long long)v, last, WAVE);
+        }
+        at0 += (uint32_t)__popcll(h.mh);
+    }
+}
+// 4. the averages of the first m output rows, in place: the SUM in the slot converted to double and divided by the group's size —
+// the distance to the next representative of its level, or to n
+__global__ __launch_bounds__(TPB) void k_gs_avg(DevGsAvg av, DevGsLevels lv, const uint32_t* __restrict__ pos, uint32_t n, uint32_t m, size_t stride, uint64_t* __restrict__ val) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        int k = 0;
+        while (k + 1 < lv.n && j >= lv.off[k + 1]) ++k;
+        const uint32_t next = j + 1 < lv.off[k + 1] ? pos[j + 1] : n;
+        const double cnt = (double)(next - pos[j]);
+#pragma unroll
+        for (int a = 0; a < SDQH_GS_MAX_AGGS; ++a) if (av.avg[a]) {
+            const uint64_t s = val[(size_t)a * stride + j];
+            const double sum = av.is_f64[a] ? __longlong_as_double((long long)s) : (double)(int64_t)s;
+            val[(size_t)a * stride + j] = (uint64_t)__double_as_longlong(sum / cnt);
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1434,7 +1595,7 @@ __global__ __launch_bounds__(TPB) void k_sort_emit(DevStage st, const uint32_t* 
 }
 
 struct Scratch {                                     // pool blocks of one call, returned on every way out
-    sdqh_ctx* ctx; void* p[4] = {nullptr, nullptr, nullptr, nullptr};
+    sdqh_ctx* ctx; void* p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     explicit Scratch(sdqh_ctx* c) : ctx(c) {}
     ~Scratch() { for (void* q : p) if (q) pool_free(ctx, q); }
 };
@@ -1610,12 +1771,15 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // filter: only the rows whose rank of `rank_kind` is <= per_limit are returned (filters false: the entry point has no such argument).
 // out: the rank column, or out[a * capacity + j] = column a beside returned row j — nullptr: rows only, no column is computed.  Then
 // the family's device arguments (a slide's lo / hi: the caller's).
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES };
+// STEP_GROUPS (sdqh_table_grouping_sets) returns one row per group: `levels` of the nsort terms, their counts to level_rows; its
+// aggregates are `aggs` (an AVG as the SUM it divides: avg), and like a filter it knows its count only behind the sort.
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
     int64_t* out;
     union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; DevWexs ex; };
+    uint32_t levels; int64_t* level_rows; DevGsAvg avg;
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -1925,6 +2089,81 @@ static int step_excludes(StepRun& r) {
     return SDQH_OK;
 }
 
+// Groups at nested levels (sdqh_table_grouping_sets).  Block 3 = [depths | head flags of the highest level | heads per tile and level
+// | level counts]: what the level pass needs.  The counts go to the host — the call's second wait, as a filter's — and the ways out
+// are taken; only then is the output's size known: block 4 = [representatives' positions | their depths | group values | the rows'
+// elements | value carries | first heads | heads per tile | their total], the first three over all g groups, highest level first.
+static int step_groups(StepRun& r) {
+    sdqh_ctx* ctx = r.ctx;
+    const int nl = r.nsort + 1;
+    const uint32_t levels = r.step.levels;
+    int top = r.nsort;
+    while (!((levels >> top) & 1u)) --top;                            // (levels != 0 and no bit above nsort: the entry point's check)
+    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
+    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
+            depth = c.take<uint8_t>((size_t)r.n);
+            heads = c.take<uint8_t>((size_t)r.n);
+            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
+            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
+        })) return r.nomem();
+    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);      // per level: the tiles' offsets in place, the level's count
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
+    std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
+    DevGsLevels lv; std::memset(&lv, 0, sizeof(lv));
+    int lvl[SDQH_SORT_MAX_KEYS + 1];
+    int64_t g = 0;
+    for (int L = top; L >= 0; --L) if ((levels >> L) & 1u) { lvl[lv.n] = L; g += (int64_t)tot[L]; lv.off[++lv.n] = (uint32_t)g; }
+    if (g > 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 groups over the levels asked for");
+    if (r.step.level_rows) for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) r.step.level_rows[L] = (L < nl && ((levels >> L) & 1u)) ? (int64_t)tot[L] : 0;
+    r.m = std::min<int64_t>(r.limit, g);
+    if (r.count_only) return r.done(r.m);
+    if (r.m > r.capacity) return r.overflow(r.m);
+    DevWaggs ag = r.step.aggs;
+    if (!r.step.out) ag.n = 0;                                        // rows only: nothing is folded
+    const size_t na = (size_t)ag.n, gstride = round_up((size_t)g * 8) / 8;
+    uint32_t *sel = nullptr, *tcnt = nullptr, *tot1 = nullptr; uint8_t* gdepth = nullptr;
+    uint64_t *fin = nullptr, *elem = nullptr, *tval = nullptr; WaggHeads* tfirst = nullptr;
+    if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
+            sel = c.take<uint32_t>((size_t)g);
+            gdepth = c.take<uint8_t>((size_t)g);
+            fin = c.take<uint64_t>(gstride * na);
+            elem = c.take<uint64_t>(r.stride * na);
+            tval = c.take<uint64_t>((size_t)ntiles * na);
+            tfirst = c.take<WaggHeads>(ntiles);
+            tcnt = c.take<uint32_t>(ntiles);
+            tot1 = c.take<uint32_t>(1);
+        })) return r.nomem();
+    // the highest level, over the rows
+    if (na) {
+        LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, heads, r.un, r.stride, elem, tval, tfirst, ntiles);
+        LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, r.un, tval, ntiles);
+    }
+    LAUNCH(ctx, "k_gs_run", k_gs_run, tgrid, ag, top, 1, depth, (const uint32_t*)nullptr, elem, r.stride, r.un, tval, tcount + (size_t)top * ntiles, ntiles,
+           fin, gstride, gdepth, sel, tot[top]);
+    // every lower level, over the groups of the one above it
+    for (int k = 1; k < lv.n; ++k) {
+        const uint32_t nf = tot[lvl[k - 1]], nt = (nf + SORT_TILE - 1) / SORT_TILE;
+        const unsigned fgrid = (nt + TPB / WAVE - 1) / (TPB / WAVE);
+        const uint32_t from = lv.off[k - 1], to = lv.off[k];
+        LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, fgrid, ag, lvl[k], gdepth + from, fin + from, gstride, nf, tval, tfirst, tcnt, nt);
+        if (na) LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, nf, tval, nt);
+        LAUNCH(ctx, "k_sort_bins", k_sort_bins, 1, tcnt, nt, tot1);
+        LAUNCH(ctx, "k_gs_run", k_gs_run, fgrid, ag, lvl[k], 0, gdepth + from, sel + from, fin + from, gstride, nf, tval, tcnt, nt,
+               fin + to, gstride, gdepth + to, sel + to, tot[lvl[k]]);
+    }
+    bool avg = false;
+    for (size_t a = 0; a < na; ++a) avg |= r.step.avg.avg[a] != 0;
+    if (avg) LAUNCH(ctx, "k_gs_avg", k_gs_avg, r.row_grid(), r.step.avg, lv, sel, r.un, (uint32_t)r.m, gstride, fin);
+    r.sel = sel;
+    for (r.ncols = 0; r.ncols < ag.n; ++r.ncols) r.col_src[r.ncols] = fin + (size_t)r.ncols * gstride;
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -1939,6 +2178,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     StepRun r{ctx, table, me, step, s, scratch, nsort, n, limit, capacity, count_only, all_kept, out_n, (uint32_t)n, round_up((size_t)n * 8) / 8, std::min<int64_t>(limit, n)};
     // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering call knows its count
     // only after the ranks, so of these it takes the first alone (and leaves *out_n untouched if a later step fails).
+    if (n == 0 && step.kind == STEP_GROUPS && step.level_rows) std::memset(step.level_rows, 0, sizeof(int64_t) * (SDQH_SORT_MAX_KEYS + 1));
     if (n == 0) return r.done(0);                                     // nothing selected (limit >= 1: m = 0 means n = 0)
     if (all_kept && count_only) return r.done(r.m);                   // count-only call
     if (all_kept && r.m > capacity) return r.overflow(r.m);           // the needed count, nothing written
@@ -1955,6 +2195,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_RANGES: if (step.out) step_rc = step_ranges(r); break;
         case STEP_QUANTILES: if (step.out || !all_kept) step_rc = step_quantiles(r); break;
         case STEP_EXCLUDES: if (step.out) step_rc = step_excludes(r); break;
+        case STEP_GROUPS: step_rc = step_groups(r); break;            // (the rows themselves are the step's: always)
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -2236,6 +2477,32 @@ int sdqh_table_window_exclude(sdqh_ctx* ctx, const sdqh_table* table, int64_t mi
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_grouping_sets(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int nterms, const sdqh_sort_term* in, uint32_t levels,
+                             int naggs, const sdqh_group_agg* aggs, int64_t limit, int64_t capacity,
+                             int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_level_rows, int64_t* out_n) {
+    const char* who = "table_grouping_sets";
+    bool ok = naggs >= 0 && naggs <= SDQH_GS_MAX_AGGS && (aggs || naggs == 0) && levels != 0u && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && !(levels >> (nterms + 1));
+    for (int a = 0; ok && a < naggs; ++a) ok = (aggs[a].op >= SDQH_WAGG_SUM && aggs[a].op <= SDQH_WAGG_MAX) || aggs[a].op == SDQH_WEX_AVG;
+    SortStep st = sort_step(STEP_GROUPS, 0, naggs ? out_aggs : nullptr);
+    st.filters = true; st.per_limit = 0;                              // no row is kept for its rank: the count is the groups', known behind the level pass
+    st.levels = levels; st.level_rows = out_level_rows;
+    st.aggs.n = ok ? naggs : 0;
+    // the measures are checked in front of window_enter: a measure the table lacks is SDQH_ERR_INVALID on a bitmap-only table and in a
+    // compile-only context too (the header: every argument error comes before SDQH_ERR_UNSUPPORTED)
+    for (int a = 0; ctx && table && ok && a < naggs; ++a) {
+        const sdqh_group_agg& g = aggs[a];
+        DevWagg& d = st.aggs.a[a];
+        d.op = g.op == SDQH_WEX_AVG ? SDQH_WAGG_SUM : g.op;             // an AVG is folded as the SUM it divides
+        d.frame = SDQH_FRAME_ROWS;
+        if (d.op != SDQH_WAGG_COUNT)                                  // (COUNT ignores its measure)
+            if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind, g.index, g.is_f64, d.sk)) return rc;
+        d.cls = fold_class(d.op, d.sk.is_f64, true);
+        st.avg.avg[a] = g.op == SDQH_WEX_AVG ? 1 : 0; st.avg.is_f64[a] = d.sk.is_f64;
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, 0, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
 
 // what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
 // a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
@@ -2245,6 +2512,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_grouping_sets_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "grouping_sets_geometry", tile_rows, false, nullptr); }
 int sdqh_window_exclude_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_exclude_geometry", tile_rows, true, narrow_max_width); }
 int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_quantile_geometry", tile_rows, false, nullptr); }
 int sdqh_window_range_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_range_geometry", tile_rows, true, narrow_max_width); }

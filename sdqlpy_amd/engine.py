@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
+from .result import EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -179,6 +179,9 @@ class Engine:
         # functions of the group's size (quantiles: result.QuantileRequest) likewise, where the library has the window quantile extension
         # (abi.Context.table_window_quantile) — route "window_quantile", noted with the extra keys "per", "per_limit" and "quantiles"
         self.device_window_quantile = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_QUANTILE", "1") != "0"
+        # GROUP BY ROLLUP / CUBE / GROUPING SETS over a result (result.GroupingRequest) likewise, where the library has the grouping sets
+        # extension (abi.Context.table_grouping_sets) — route "grouping_sets", one call per chain of sets, noted with "sets", "aggs", "calls"
+        self.device_grouping_sets = os.environ.get("SDQLPY_AMD_DEVICE_GROUPING_SETS", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1735,6 +1738,7 @@ class _FrameSpec(list):
 # The requests with partitions, in the order they are told apart: class -> (route, Engine switch, Library flag, the attribute that
 # lists the request's columns — None: ranks only —, the most columns the device takes)
 _WINDOW_ROUTES = (
+    (GroupingRequest, "grouping_sets", "device_grouping_sets", "has_grouping_sets", "aggs", abi.GS_MAX_AGGS),
     (FrameRequest, "window_agg", "device_window_agg", "has_window_agg", "aggs", abi.WAGG_MAX_AGGS),
     (SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS),
     (RangeRequest, "window_range", "device_window_range", "has_window_range", "ranges", abi.WRANGE_MAX_AGGS),
@@ -1750,7 +1754,7 @@ def _order_spec(top, spec_of, decoded_of):
     decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
     text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest)):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest)):
         return spec
     spec = _FrameSpec(spec)
     if isinstance(top, (RangeRequest, ExcludeRequest)):
@@ -1766,10 +1770,12 @@ def _order_spec(top, spec_of, decoded_of):
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets") and _term_text(t) is not None]}
     if isinstance(top, tuple(cls for cls, *_ in _WINDOW_ROUTES)):      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
-    if isinstance(top, FrameRequest):                        # the aggregates in the order of their columns
+    if isinstance(top, GroupingRequest):                     # the sets as listed, the aggregates, and how many device calls serve them
+        note["sets"], note["aggs"], note["calls"] = [list(s) for s in top.sets], [list(a) for a in top.aggs], len(top.chains()) if route == "grouping_sets" else 0
+    elif isinstance(top, FrameRequest):                      # the aggregates in the order of their columns
         note["aggs"] = [list(a) for a in top.aggs]
     elif isinstance(top, SlideRequest):                      # lag / lead as the `first` they are, unbounded sides None
         note["slides"] = [list(a) for a in top.slides]
@@ -1806,6 +1812,12 @@ def _finish_top(rs, ordered, top):
         return rs
     if not ordered:
         return _host_top(rs, top)
+    if isinstance(top, GroupingRequest):                    # the device's groups, every chain's rows behind one another: the sets in listed order
+        pieces = []
+        for s, cols in enumerate(top.sets):
+            rows = np.nonzero(ordered.rank.set_of == s)[0]
+            pieces.append(({c: rs.column(c)[rows] for c in cols}, [np.asarray(a)[rows] for a in ordered.rank], len(rows)))
+        return grouped_result(top, rs.column, pieces)
     if isinstance(top, FrameRequest):                       # the device's aggregates, a column each
         for name, _, _, _ in top.aggs:
             if name in rs.columns:
@@ -1913,6 +1925,9 @@ def _order_route(eng, top, spec):
     "window_exclude" abi.Context.table_window_exclude: an ExcludeRequest under "window_range"'s conditions (at most WEX_MAX_COLS columns;
                  the window exclude extension and Engine.device_window_exclude on): its "value" columns' offsets are taken as a
                  RangeRequest's are, "groups" and "rows" columns take ints (_exclude_offsets)
+    "grouping_sets" abi.Context.table_grouping_sets, once per chain of sets (_grouping_calls): a GroupingRequest of at most GS_MAX_AGGS
+                 aggregates whose measures are underived numeric columns, over at most SORT_MAX_KEYS grouping columns (the grouping
+                 sets extension and Engine.device_grouping_sets on; terms as for "window")
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -2005,10 +2020,37 @@ def _exclude_columns(top, spec):
     return cols
 
 
+class _GroupColumns(list):
+    """The aggregate columns of the rows a "grouping_sets" route fetched, and set_of: per row the index of the set it belongs to."""
+    set_of = None
+
+
+def _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits):
+    """The route "grouping_sets": one abi.Context.table_grouping_sets call per chain of top's sets — terms = the chain's longest set,
+    levels = its members' lengths — and the calls' rows behind one another: (keys, payload, values, hits, _GroupColumns)."""
+    names = [nm for nm, _ in top[1]]
+    aggs = [(abi.WEX_AVG if op == "avg" else GROUP_OPS.index(op),) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _), col in zip(top.aggs, spec.measures)]
+    parts, set_of = [], []
+    for head, members in top.chains():
+        levels = 0
+        for length in members:
+            levels |= 1 << length
+        got = eng.ctx.table_grouping_sets(table, min_hits, [terms[names.index(c)] for c in head], levels, aggs, abi.SORT_ALL, cap, want_hits=want_hits)
+        parts.append(got)
+        for length in sorted(members, reverse=True):                 # the levels come from the highest down
+            set_of.append(np.full(int(got[5][length]), members[length], np.int64))
+
+    def joined(i, axis):
+        return None if parts[0][i] is None else np.concatenate([g[i] for g in parts], axis=axis)
+    cols = _GroupColumns(np.concatenate([g[4][a] for g in parts]) for a in range(len(aggs)))
+    cols.set_of = np.concatenate(set_of)
+    return joined(0, 0), joined(1, 1), joined(2, 1), joined(3, 0), cols
+
+
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
     """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile" and "window_exclude" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -2017,6 +2059,8 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
         got = eng.ctx.table_sorted(table, min_hits, k, spec, cap, want_hits=want_hits)
     elif route == "sorted_by":
         got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
+    elif route == "grouping_sets":
+        got = _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits)
     elif route == "window_agg":
         aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
         got = eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
@@ -2141,6 +2185,10 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
                             for a, (_, fn, col, _, _, _) in zip(ordered.rank, top.quants)]
         if isinstance(ordered, _Ranked) and isinstance(top, ExcludeRequest):    # likewise; an average stays the double it is
             ordered.rank = [np.rint(a).astype(np.int64) if op not in ("count", "avg") and col in bt.int_values else a for a, (_, op, col, _, _, _, _) in zip(ordered.rank, top.frames)]
+        if isinstance(ordered, _Ranked) and isinstance(top, GroupingRequest):   # likewise, in place (the columns carry set_of); an average stays the double it is
+            for i, (_, op, col) in enumerate(top.aggs):
+                if op not in ("count", "avg") and col in bt.int_values:
+                    ordered.rank[i] = np.rint(ordered.rank[i]).astype(np.int64)
         if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
@@ -2278,7 +2326,7 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
@@ -2287,8 +2335,10 @@ def _finalize(eng, op, env, top=None):
         route["order"], route["ranked"] = [nm for nm, _ in top[1]], [nm for i, (nm, _) in enumerate(top[1]) if i in ranked]
         if isinstance(top, WindowRequest):
             route["order"], route["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
-        if isinstance(top, FrameRequest):
+        if isinstance(top, (FrameRequest, GroupingRequest)):
             route["aggs"] = [list(a) for a in top.aggs]
+        if isinstance(top, GroupingRequest):
+            route["sets"] = [list(s) for s in top.sets]
         if isinstance(top, SlideRequest):
             route["slides"] = [list(a) for a in top.slides]
         if isinstance(top, RangeRequest):

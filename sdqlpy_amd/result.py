@@ -513,6 +513,148 @@ def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
     return req
 
 
+GROUP_OPS = ("sum", "count", "min", "max", "avg")          # abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX, and abi.WEX_AVG
+
+
+class GroupingRequest(WindowRequest):
+    """GROUP BY GROUPING SETS over a result, travelling where a WindowRequest travels (it reads as an ORDER BY of every grouping
+    column): [1] = `by`, the union of the sets' columns in order of first appearance with their directions; sets = the column tuples
+    in the order listed; aggs = [(name of the new column, op: a name of GROUP_OPS, measure column or None for a count)].  The result
+    holds `by`, the aggregates and an int64 column "grouping" (SQL's GROUPING(by...): bit len(by) - 1 - i set where by[i] is rolled
+    up in the row; such a column holds 0 / NaN / ""); every other column of the query's result is dropped.  The sets come in the
+    order listed, inside a set the rows are ordered by the set's columns as the set lists them."""
+
+    def __new__(cls, terms, sets, aggs):
+        self = WindowRequest.__new__(cls, WINDOW_ALL, terms, len(terms), 0, WINDOW_ALL, None)
+        self.sets = [tuple(str(c) for c in s) for s in sets]
+        self.aggs = [(str(n), str(op), None if col is None else str(col)) for n, op, col in aggs]
+        names = [nm for nm, _ in self[1]]
+        if not self.sets or len(set(self.sets)) != len(self.sets) or any(len(set(s)) != len(s) or any(c not in names for c in s) for s in self.sets):
+            raise ValueError("grouping_sets: bad sets")
+        if any(op not in GROUP_OPS or (col is None and op != "count") for _, op, col in self.aggs):
+            raise ValueError("grouping_sets: bad aggregate")
+        return self
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: `by` term for term (and the sets with it), the measures through `names`."""
+        names = names or {}
+        to = {old: new for (old, _), (new, _) in zip(self[1], terms)}
+        return GroupingRequest(terms, [tuple(to[c] for c in s) for s in self.sets], [(n, op, names.get(col, col)) for n, op, col in self.aggs])
+
+    def chains(self):
+        """The sets as the device serves them: [(the chain's column tuple, {level: index of the set it serves})].  A set rides in
+        another set's chain iff its tuple is a prefix of that set's; a chain is one call over its longest tuple, `levels` = the
+        members' lengths.  Every set is served exactly once."""
+        out = []
+        for i in sorted(range(len(self.sets)), key=lambda i: -len(self.sets[i])):      # (stable: longest first, then as listed)
+            s = self.sets[i]
+            for head, members in out:
+                if head[:len(s)] == s and len(s) not in members:
+                    members[len(s)] = i
+                    break
+            else:
+                out.append((s, {len(s): i}))
+        return out
+
+    def masks(self):
+        """the `grouping` value of every set's rows"""
+        names = [nm for nm, _ in self[1]]
+        return [sum(1 << (len(names) - 1 - i) for i, nm in enumerate(names) if nm not in s) for s in self.sets]
+
+
+def grouping_request(columns, sets, aggs):
+    """The checked GroupingRequest of rollup / cube / grouping_sets: sets = a list of column tuples, a column `name` or (name, "asc" |
+    "desc"); aggs = {new column: (op, measure column or None)} with op a name of GROUP_OPS (an empty dict: the distinct combinations
+    alone).  columns: the result's column names when they are known (None: checked when the result is).  KeyError for a column the
+    result lacks or a new column it has already, ValueError for everything else."""
+    if not isinstance(sets, (list, tuple)) or not sets:
+        raise ValueError("grouping_sets: sets is a non-empty list of column tuples")
+    direction, listed = {}, []
+    for s in sets:
+        if isinstance(s, str) or not isinstance(s, (list, tuple)):
+            raise ValueError("grouping_sets: a set is a tuple of columns")
+        cols = []
+        for c in s:
+            name, d = (c, None) if isinstance(c, str) else (c[0], c[1]) if isinstance(c, (list, tuple)) and len(c) == 2 else (None, None)
+            if not isinstance(name, str) or d not in (None, "asc", "desc"):
+                raise ValueError("grouping_sets: a column is a name or (name, 'asc' | 'desc')")
+            if name in cols:
+                raise ValueError("grouping_sets: column %r comes twice in one set" % name)
+            if d is not None and direction.get(name, d) != d:
+                raise ValueError("grouping_sets: column %r has two directions" % name)
+            if d is not None or name not in direction:
+                direction[name] = d
+            cols.append(name)
+        if tuple(cols) in listed:
+            raise ValueError("grouping_sets: the set %r comes twice" % (tuple(cols),))
+        listed.append(tuple(cols))
+    if not isinstance(aggs, dict):
+        raise ValueError("grouping_sets: aggs is a dict {new column: (op, measure)}")
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) != 2:
+            raise ValueError("grouping_sets: an aggregate is name: (op, measure)")
+        op, col = spec
+        if op not in GROUP_OPS:
+            raise ValueError("grouping_sets: op is one of %s, not %r" % (", ".join(GROUP_OPS), op))
+        if col is None and op != "count":
+            raise ValueError("grouping_sets: %s needs a measure column" % op)
+        if col is not None and not isinstance(col, str):
+            raise ValueError("grouping_sets: a measure is a column name")
+        out.append((name, op, col))
+    req = GroupingRequest([(nm, d or "asc") for nm, d in direction.items()], listed, out)
+    if columns is not None:
+        check_grouping_columns(req, columns)
+    return req
+
+
+def check_grouping_columns(req, columns):
+    for nm, _ in req[1]:
+        if nm not in columns:
+            raise KeyError("grouping_sets: the result has no column %r" % nm)
+    for name, _, col in req.aggs:
+        if col is not None and col not in columns:
+            raise KeyError("grouping_sets: the result has no column %r" % col)
+        if name in columns or name == "grouping":
+            raise KeyError("grouping_sets: the result already has a column %r" % name)
+
+
+def rollup_sets(by):
+    """by[:d], by[:d - 1], ..., ()"""
+    by = list(by)
+    return [tuple(by[:d]) for d in range(len(by), -1, -1)]
+
+
+def cube_sets(by):
+    """every subset of `by`, in by's order, by ascending `grouping` mask (bit len(by) - 1 - i: by[i] is rolled up)"""
+    by = list(by)
+    return [tuple(c for i, c in enumerate(by) if not (mask >> (len(by) - 1 - i)) & 1) for mask in range(1 << len(by))]
+
+
+def _rolled_up(a, n):
+    """n values of what a rolled-up column of a's dtype holds: 0, NaN or the empty text"""
+    a = np.asarray(a)
+    return np.full(n, np.nan, a.dtype) if a.dtype.kind == "f" else np.zeros(n, a.dtype if a.dtype.kind in "iubU" else object)
+
+
+def grouped_result(req, column_of, pieces):
+    """The ResultSet of a GroupingRequest out of its sets' rows, whoever grouped them: pieces[s] = ({column of set s: its groups'
+    values}, [one array per aggregate], the number of groups) for every set; column_of(name): the source column (for the dtype of what a rolled-up column
+    holds).  The sets in the order listed, rolled-up columns filled, the `grouping` column last."""
+    names = [nm for nm, _ in req[1]]
+    masks = req.masks()
+    sizes = [m for _, _, m in pieces]
+    cols = []
+    for nm in names:
+        src = column_of(nm)
+        parts = [np.asarray(by[nm]) if nm in by else _rolled_up(src, m) for (by, _, _), m in zip(pieces, sizes)]
+        cols.append(np.concatenate(parts) if parts else np.asarray(src)[:0])
+    for a in range(len(req.aggs)):
+        cols.append(np.concatenate([np.asarray(aggs[a]) for _, aggs, _ in pieces]))
+    cols.append(np.concatenate([np.full(m, mask, np.int64) for m, mask in zip(sizes, masks)]))
+    return ResultSet(names + [n for n, _, _ in req.aggs] + ["grouping"], cols)
+
+
 def slide_empty(default, is_f64, what="sliding"):
     """What an empty frame gives for a measure of dtype float64 (is_f64) or int64: `default`, or with None NaN / 0.  ValueError for a
     default that does not fit the dtype: a float for an int64 column, an int outside int64."""
@@ -1027,6 +1169,76 @@ class ResultSet:
         ("median", measure)}.  Every function sees its whole group, whatever `per` keeps."""
         return self.quantiled(quantile_request(self.columns, by, order, cols, per))
 
+    def grouped(self, req):
+        """The groups of a GroupingRequest, what sdqh_table_grouping_sets does on the device (include/sdqh_sort_groups.h), on the host:
+        per set a stable lexsort by the set's columns (order_image: the device's total order), a group wherever a neighbour differs
+        in one of them, and np.ufunc.reduceat over the groups — SUM of integers wraps, MIN / MAX are the unsigned maximum of the
+        order-preserving images (NaNs skipped, -0.0 below +0.0, nothing but NaNs: NaN), AVG the SUM as a double over the count.
+        sum / min / max take the measure's dtype (int64 or float64), count is int64, avg float64.  An empty result has no groups, not
+        even the grand total."""
+        self._wait()
+        check_grouping_columns(req, self.columns)
+        n = self._n
+        direction = dict(req[1])
+        top = np.uint64(1) << np.uint64(63)
+        measures = {}
+        for name, op, col in req.aggs:
+            if col is not None and col not in measures:
+                x = self.column(col)
+                if x.dtype.kind not in "iubf":
+                    raise ValueError("grouping_sets: %s of column %r: the measure is not numeric" % (op, col))
+                measures[col] = np.ascontiguousarray(x, np.float64 if x.dtype.kind == "f" else np.int64)
+        pieces = []
+        for s in req.sets:
+            images = [order_image(self.column(c), direction[c] == "desc") for c in s]
+            idx = np.lexsort(images[::-1]) if images else np.arange(n)    # stable: ties keep the stored order
+            head = np.zeros(n, bool)
+            if n:
+                head[0] = True
+            for u in images:
+                head[1:] |= u[idx][1:] != u[idx][:-1]
+            starts = np.nonzero(head)[0]
+            m = len(starts)
+            count = np.diff(np.append(starts, n)).astype(np.int64)
+            aggs = []
+            for name, op, col in req.aggs:
+                if op == "count":
+                    aggs.append(count)
+                    continue
+                x = measures[col][idx]
+                is_f = x.dtype.kind == "f"
+                if not m:
+                    aggs.append(np.zeros(0, np.float64 if is_f or op == "avg" else np.int64))
+                elif op in ("sum", "avg"):
+                    v = np.add.reduceat(x, starts) if is_f else np.add.reduceat(x.view(np.uint64), starts).view(np.int64)
+                    aggs.append(v if op == "sum" else v.astype(np.float64) / count.astype(np.float64))
+                else:                                                # the images of sdqh_extrema.h: unsigned maximum, reversed for MIN, NaN = 0
+                    v = order_image(x, op == "min")
+                    if is_f:
+                        v = np.where(np.isnan(x), np.uint64(0), v)
+                    e = np.maximum.reduceat(v, starts)
+                    u = ~e if op == "min" else e
+                    if is_f:
+                        aggs.append(np.where(e == 0, np.uint64(0x7FF8000000000000), np.where(u >> np.uint64(63) != 0, u ^ top, ~u)).view(np.float64))
+                    else:
+                        aggs.append((u ^ top).view(np.int64))
+            pieces.append(({c: self.column(c)[idx[starts]] for c in s}, aggs, m))
+        return grouped_result(req, self.column, pieces)
+
+    def grouping_sets(self, sets, aggs):
+        """GROUP BY GROUPING SETS over the rows: one row per group of every set in `sets` (column tuples; a column is a name or (name,
+        "asc" | "desc")), aggs = {new column: (op, measure column or None)}, op in GROUP_OPS.  The result holds the sets' columns, the
+        aggregates and `grouping` (see GroupingRequest)."""
+        return self.grouped(grouping_request(self.columns, sets, aggs))
+
+    def rollup(self, by, aggs):
+        """GROUP BY ROLLUP(by): the sets by[:d], by[:d - 1], ..., () — every prefix's subtotals down to the grand total."""
+        return self.grouping_sets(rollup_sets(by), aggs)
+
+    def cube(self, by, aggs):
+        """GROUP BY CUBE(by): every subset of `by`, by ascending `grouping` mask."""
+        return self.grouping_sets(cube_sets(by), aggs)
+
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:
         aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS, the frame rows [row + lo, row + hi] of
@@ -1041,6 +1253,8 @@ class ResultSet:
 
     def windowed(self, req):
         """The rows a WindowRequest keeps, in its order, with its rank column when it names one (a FrameRequest: framed)."""
+        if isinstance(req, GroupingRequest):
+            return self.grouped(req)
         if isinstance(req, FrameRequest):
             return self.framed(req)
         if isinstance(req, SlideRequest):

@@ -493,6 +493,35 @@ def sdql_compile(in_type):
             req = quantile_request(engine.result_columns(cache["plan"]), list(by), list(order), cols, per)     # checked before anything is launched
             return lambda *args: run(args, req)
 
+        def grouping_sets(sets, aggs):
+            """The same query finished with GROUP BY GROUPING SETS over its result: one row per group of every set in `sets` — column
+            tuples, a column a name or (name, "asc" | "desc") —, aggs = {new column: (op, measure column or None)}, op in "sum" /
+            "count" / "min" / "max" / "avg", e.g. ``q3.grouping_sets([("o_orderdate", "o_shippriority"), ("o_shippriority",), ()],
+            {"revenue_sum": ("sum", "revenue"), "n": ("count", None)})(li, cu, ord)``.  The result holds the sets' columns, the
+            aggregates and an int64 column `grouping` — SQL's GROUPING(): bit len(by) - 1 - i is set where column i is rolled up in
+            the row, and such a column holds 0 / NaN / "" — and none of the query's other columns; the sets come in the order
+            listed, inside a set the rows are ordered by the set's columns.  sum / min / max take the measure's dtype, count is
+            int64, avg float64.  Names and ops are checked here, before anything is launched."""
+            from . import engine, frontend
+            from .result import grouping_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = grouping_request(engine.result_columns(cache["plan"]), list(sets), aggs)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
+        def rollup(by, aggs):
+            """The same query finished with GROUP BY ROLLUP(by): the grouping sets by[:d], by[:d - 1], ..., () — subtotals for every
+            prefix of `by` down to the grand total, behind one sort, e.g. ``q3.rollup(["o_orderdate", "o_shippriority"],
+            {"revenue_sum": ("sum", "revenue")})(li, cu, ord)``.  See grouping_sets."""
+            from .result import rollup_sets
+            return grouping_sets(rollup_sets(by), aggs)
+
+        def cube(by, aggs):
+            """The same query finished with GROUP BY CUBE(by): the grouping sets of every subset of `by`, by ascending `grouping`
+            mask.  See grouping_sets."""
+            from .result import cube_sets
+            return grouping_sets(cube_sets(by), aggs)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -502,6 +531,9 @@ def sdql_compile(in_type):
         wrapper.ranged = ranged
         wrapper.excluding = excluding
         wrapper.quantiles = quantiles
+        wrapper.rollup = rollup
+        wrapper.cube = cube
+        wrapper.grouping_sets = grouping_sets
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
