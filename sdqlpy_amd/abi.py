@@ -65,6 +65,11 @@ WEX_MAX_COLS = 4
 # GROUPING SETS: one row per group at several nested levels of one key list, SUM / COUNT / MIN / MAX / AVG per group
 GROUPING_SETS_EXPORTS = ["sdqh_table_grouping_sets", "sdqh_grouping_sets_geometry"]
 GS_MAX_AGGS = 4
+# ... and its tenth (include/sdqh_sort_distinct.h, Library.has_group_distinct): aggregates over the distinct values of a group — COUNT /
+# SUM / AVG (DISTINCT x), MODE and its count, and the plain COUNT beside them, one row per group
+GROUP_DISTINCT_EXPORTS = ["sdqh_table_group_distinct", "sdqh_group_distinct_geometry"]
+GD_COUNT_DISTINCT, GD_SUM_DISTINCT, GD_AVG_DISTINCT, GD_MODE, GD_MODE_COUNT, GD_COUNT = 0, 1, 2, 3, 4, 5
+GD_MAX_AGGS = 4
 # all of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
@@ -74,6 +79,7 @@ WINDOW_EXTENSIONS = {
     "has_window_quantile": (WINDOW_QUANTILE_EXPORTS, "sdqh_sort_quantile.h", "window quantile", "has_window_slide"),
     "has_window_exclude": (WINDOW_EXCLUDE_EXPORTS, "sdqh_sort_exclude.h", "window exclude", "has_window_range"),
     "has_grouping_sets": (GROUPING_SETS_EXPORTS, "sdqh_sort_groups.h", "grouping sets", "has_window_agg"),
+    "has_group_distinct": (GROUP_DISTINCT_EXPORTS, "sdqh_sort_distinct.h", "group distinct", "has_grouping_sets"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -1486,6 +1492,39 @@ class Context:
         """Sorted positions (and, at a lower level, groups) per tile of sdqh_table_grouping_sets' passes: what the tests size their cases from."""
         return self._window_geometry("has_grouping_sets", 1)
 
+    def table_group_distinct(self, table, min_hits, terms, ngroup, aggs, limit, capacity, want_hits=True, want_aggs=True):
+        """Aggregates over the distinct values of a group: terms as table_sorted_by takes them — the first ngroup (0 .. len(terms) - 1)
+        group, the others are the value —; aggs: [(op, kind, index, is_f64)] — op one of GD_COUNT_DISTINCT / GD_SUM_DISTINCT /
+        GD_AVG_DISTINCT / GD_MODE / GD_MODE_COUNT / GD_COUNT, the measure as a sort column is named (COUNT_DISTINCT, MODE_COUNT and COUNT
+        ignore it), 1 .. GD_MAX_AGGS of them.  One row per group — its first sorted row —, in sorted order; the first min(limit,
+        groups).  The arrays are sized from `capacity`; a result that does not fit is fetched again with the exact size.  Returns
+        (keys, payload, values, hits, aggs) — aggs one array per aggregate: float64 for an AVG_DISTINCT and for a double measure under
+        SUM_DISTINCT / MODE, else int64; None without want_aggs (rows only)."""
+        self._need("has_group_distinct", "table_group_distinct")
+        arr = (GroupAgg * max(1, len(aggs)))()
+        for i, (op, kind, index, is_f64) in enumerate(aggs):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
+        as_f64 = [op == GD_AVG_DISTINCT or (op in (GD_SUM_DISTINCT, GD_MODE) and _measure_is_f64(kind, is_f64)) for op, kind, _, is_f64 in aggs]
+        lead = (C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(ngroup), C.c_int(len(aggs)), arr, C.c_int64(limit))
+        got = self._sorted_call("table_group_distinct", table, lead, limit, capacity, want_hits, bool(want_aggs), naggs=max(1, len(aggs)))
+        return got[:4] + (None if got[4] is None else [got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def table_group_distinct_count(self, table, min_hits, terms, ngroup, aggs, limit=SORT_ALL):
+        """The count-only call of table_group_distinct: min(limit, groups) — the sort and the depth pass run, no row is fetched."""
+        self._need("has_group_distinct", "table_group_distinct")
+        arr = (GroupAgg * max(1, len(aggs)))()
+        for i, (op, kind, index, is_f64) in enumerate(aggs):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
+        n = C.c_int64()
+        self._check(self.lib.sdqh_table_group_distinct(self.handle, table.handle, C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_int(ngroup),
+                                                       C.c_int(len(aggs)), arr, C.c_int64(limit), C.c_int64(0), None, None, None, None, None, C.byref(n)))
+        self._after_call("table_group_distinct")
+        return n.value
+
+    def group_distinct_geometry(self):
+        """Sorted positions (and, at the upper stage, value runs) per tile of sdqh_table_group_distinct's passes: what the tests size their cases from."""
+        return self._window_geometry("has_group_distinct", 1)
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1766,6 +1805,10 @@ class Library:
             L.sdqh_table_grouping_sets.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_grouping_sets_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        if self.has_group_distinct:
+            L.sdqh_table_group_distinct.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_group_distinct_geometry.argtypes = [C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

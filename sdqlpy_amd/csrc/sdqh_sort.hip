@@ -120,6 +120,15 @@
 //                     the highest level over the rows: the frames' tile scan, the value at a group's last row kept in the group's slot
 //   k_gs_tiles / k_wagg_scan / k_sort_bins / k_gs_run
 //                     every lower level over the groups of the level above it; k_gs_avg divides the sums of an AVG — see the section
+//   DISTINCTS         in their place (STEP_DISTINCTS).  sdqh_table_group_distinct (include/sdqh_sort_distinct.h) returns one row per group of
+//                     the first ngroup terms with COUNT / SUM / AVG over the DISTINCT values of the other terms, MODE and COUNT:
+//
+//   k_gs_depth / k_sort_bins
+//                     as for GROUPS: a head of level nterms opens a value run, one of level ngroup a group; both counts go to the host
+//   k_gd_heads / k_gd_elems
+//                     the rows to value runs: a run's sorted position, depth and length, per aggregate the element the groups fold
+//   k_gs_tiles / k_wagg_scan / k_sort_bins / k_gs_run
+//                     the runs folded into groups, as a lower level of GROUPS; k_gd_finish unpacks MODE and divides an AVG — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -137,6 +146,7 @@
 #include "sdqh_sort_quantile.h"
 #include "sdqh_sort_exclude.h"
 #include "sdqh_sort_groups.h"
+#include "sdqh_sort_distinct.h"
 
 using namespace sdqh_host;
 
@@ -1573,6 +1583,94 @@ __global__ __launch_bounds__(TPB) void k_gs_avg(DevGsAvg av, DevGsLevels lv, con
     }
 }
 
+// ---- aggregates over the distinct values of a group (sdqh_table_group_distinct) ----------------------------------------------------
+// The first ngroup terms group, all nterms terms make the value: a VALUE RUN is a level-nterms group, a GROUP a level-ngroup one, and
+// k_gs_depth's byte holds the heads of both.  Two stages.  The lower one turns the rows into runs: a run's slot is its head's rank
+// among the run heads (k_gd_heads), its length the distance to the next run's head, and per aggregate it leaves the element the upper
+// stage folds (k_gd_elems) — 1 for COUNT_DISTINCT, the length for COUNT, the measure's bits at the run's first row for SUM / AVG, and
+// for MODE / MODE_COUNT one word, (length << 32) | (0xFFFFFFFF - sorted position), whose unsigned maximum is the longest and then the
+// earliest run.  The upper one is the grouping sets' "a lower level over the groups of the level above it", unchanged: k_gs_tiles /
+// k_wagg_scan / k_sort_bins / k_gs_run at level ngroup over an array as long as the number of runs.  The MODE word is folded by
+// WAGG_UMAX as it stands — as the signed image of a MAX over int64, which those passes encode to the word and decode again — so no
+// new fold class is needed.  k_gd_finish then gives every group its sorted position, unpacks the MODE word (the measure gathered
+// through the permutation at the winning position) and divides an AVG by the group's own number of runs.  No atomics.
+struct DevGdAggs { DevSortKey sk[SDQH_GD_MAX_AGGS]; int32_t op[SDQH_GD_MAX_AGGS]; int32_t n, _pad; };      // sk: the measure (desc unused)
+static_assert(SDQH_GD_MAX_AGGS == SDQH_WAGG_MAX_AGGS, "the distinct folds are the frames'");
+constexpr unsigned long long GD_SIGN = 1ull << 63;
+
+// the 64 bits of measure sk at sorted position p (p < n)
+__device__ __forceinline__ uint64_t gd_measure(const DevSortKey& sk, const DevStage& st, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, uint32_t p, uint32_t n) {
+    const uint32_t g = perm ? perm[p] : p;
+    if (g >= n) return 0ull;                                             // (a permutation of [0, n): never taken)
+    const int64_t idx = (int64_t)refs[g];
+    const uint32_t hits = st.shits ? st.shits[idx] : 0u;
+    return (uint64_t)sort_raw(sk, st, idx, hits);
+}
+
+// 1. a wave per tile of sorted positions: the head of value run s (its rank among the level-`top` heads: toff — k_sort_bins' — plus
+// the heads up to it in the tile) leaves its sorted position and its depth in slot s.  A slot at or past nr is not written.
+__global__ __launch_bounds__(TPB) void k_gd_heads(int top, const uint8_t* __restrict__ depth, uint32_t n, const uint32_t* __restrict__ toff, uint32_t ntiles,
+                                                 uint32_t* __restrict__ rpos, uint8_t* __restrict__ rdepth, uint32_t nr) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint64_t le = lanemask_lt() | (1ull << (uint32_t)lane_id());
+    uint32_t at0 = toff[w];
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t j = b + (uint32_t)lane_id();
+        const GsBatch h = gs_batch(depth, top, j, r1, n, le);
+        const uint32_t slot = at0 + (uint32_t)__popcll(h.hl) - 1u;
+        if (h.head && slot < nr) { rpos[slot] = (uint32_t)j; rdepth[slot] = (uint8_t)(j == 0 ? 0u : h.d); }
+        at0 += (uint32_t)__popcll(h.mh);
+    }
+}
+// 2. a thread per value run: its length and every aggregate's element, as a group value of the aggregate's fold class (what
+// k_gs_tiles and k_gs_run read with elems == 0)
+__global__ __launch_bounds__(TPB) void k_gd_elems(DevStage st, DevGdAggs gd, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ rpos,
+                                                 uint32_t n, uint32_t nr, size_t stride, uint64_t* __restrict__ elem) {
+    for (uint64_t s = (uint64_t)blockIdx.x * TPB + threadIdx.x; s < nr; s += (uint64_t)gridDim.x * TPB) {
+        const uint32_t p = rpos[s];
+        const uint32_t next = s + 1 < nr ? rpos[s + 1] : n;
+        const uint64_t len = (uint64_t)(next - p);
+#pragma unroll
+        for (int a = 0; a < SDQH_GD_MAX_AGGS; ++a) if (a < gd.n) {
+            const int op = gd.op[a];
+            uint64_t e;
+            if (op == SDQH_GD_COUNT_DISTINCT) e = 1ull;
+            else if (op == SDQH_GD_COUNT) e = len;
+            else if (op == SDQH_GD_MODE || op == SDQH_GD_MODE_COUNT) e = ((len << 32) | (uint64_t)(0xFFFFFFFFu - p)) ^ GD_SIGN;
+            else e = p < n ? gd_measure(gd.sk[a], st, refs, perm, p, n) : 0ull;
+            elem[(size_t)a * stride + s] = e;
+        }
+    }
+}
+// 3. a thread per returned group: gfirst[j] (k_gs_run's positions over the runs) is the group's first run — its sorted position
+// goes to sel, the distance to the next group's first run (or to nr) is its number of runs; MODE / MODE_COUNT are unpacked and an
+// AVG divided, in place
+__global__ __launch_bounds__(TPB) void k_gd_finish(DevStage st, DevGdAggs gd, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ rpos,
+                                                  const uint32_t* __restrict__ gfirst, uint32_t n, uint32_t nr, uint32_t ng, uint32_t m, size_t stride,
+                                                  uint64_t* __restrict__ val, uint32_t* __restrict__ sel) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t f = gfirst[j];
+        const uint32_t next = j + 1 < ng ? gfirst[j + 1] : nr;
+        if (f >= nr) continue;                                           // (a run index: never taken)
+        sel[j] = rpos[f];
+        const double runs = (double)(next - f);
+#pragma unroll
+        for (int a = 0; a < SDQH_GD_MAX_AGGS; ++a) if (a < gd.n) {
+            const int op = gd.op[a];
+            const uint64_t v = val[(size_t)a * stride + j];
+            if (op == SDQH_GD_MODE_COUNT) val[(size_t)a * stride + j] = (v ^ GD_SIGN) >> 32;
+            else if (op == SDQH_GD_MODE) {
+                const uint32_t p = 0xFFFFFFFFu - (uint32_t)((v ^ GD_SIGN) & 0xFFFFFFFFull);
+                val[(size_t)a * stride + j] = p < n ? gd_measure(gd.sk[a], st, refs, perm, p, n) : 0ull;
+            } else if (op == SDQH_GD_AVG_DISTINCT) {
+                const double sum = gd.sk[a].is_f64 ? __longlong_as_double((long long)v) : (double)(int64_t)v;
+                val[(size_t)a * stride + j] = (uint64_t)__double_as_longlong(sum / runs);
+            }
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1773,13 +1871,16 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // the family's device arguments (a slide's lo / hi: the caller's).
 // STEP_GROUPS (sdqh_table_grouping_sets) returns one row per group: `levels` of the nsort terms, their counts to level_rows; its
 // aggregates are `aggs` (an AVG as the SUM it divides: avg), and like a filter it knows its count only behind the sort.
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS };
+// STEP_DISTINCTS (sdqh_table_group_distinct) returns one row per group of the first `ngroup` terms; `aggs` are the folds of the upper
+// stage, `gd` the ops and measures as the caller named them.
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
     int64_t* out;
     union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; DevWexs ex; };
     uint32_t levels; int64_t* level_rows; DevGsAvg avg;
+    int ngroup; DevGdAggs gd;
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -2164,6 +2265,68 @@ static int step_groups(StepRun& r) {
     return SDQH_OK;
 }
 
+// Aggregates over the distinct values of a group (sdqh_table_group_distinct).  Block 3 = step_groups' [depths | head flags of level
+// nsort | heads per tile and level | level counts].  The counts of runs (level nsort) and groups (level ngroup) go to the host — the
+// call's second wait — and the ways out are taken.  Block 4 = [runs: positions | depths | elements] [groups: first runs | depths |
+// values | positions] [the upper stage's value carries | first heads | heads per tile | their total].
+static int step_distincts(StepRun& r) {
+    sdqh_ctx* ctx = r.ctx;
+    const int nl = r.nsort + 1, top = r.nsort, L = r.step.ngroup;
+    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
+    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
+            depth = c.take<uint8_t>((size_t)r.n);
+            heads = c.take<uint8_t>((size_t)r.n);
+            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
+            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
+        })) return r.nomem();
+    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
+    std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
+    const uint32_t nr = tot[top], ng = tot[L];                        // value runs, groups: 1 <= ng <= nr <= n
+    r.m = std::min<int64_t>(r.limit, (int64_t)ng);
+    if (r.count_only) return r.done(r.m);
+    if (r.m > r.capacity) return r.overflow(r.m);
+    DevWaggs ag = r.step.aggs;
+    DevGdAggs gd = r.step.gd;
+    if (!r.step.out) ag.n = gd.n = 0;                                 // rows only: nothing is folded
+    const size_t na = (size_t)ag.n, rstride = round_up((size_t)nr * 8) / 8, gstride = round_up((size_t)ng * 8) / 8;
+    const uint32_t nt = (nr + SORT_TILE - 1) / SORT_TILE;             // the upper stage's tiles: SORT_TILE runs each
+    const unsigned fgrid = (nt + TPB / WAVE - 1) / (TPB / WAVE);
+    uint32_t *rpos = nullptr, *gfirst = nullptr, *sel = nullptr, *tcnt = nullptr, *tot1 = nullptr; uint8_t *rdepth = nullptr, *gdepth = nullptr;
+    uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads* tfirst = nullptr;
+    if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
+            rpos = c.take<uint32_t>((size_t)nr);
+            rdepth = c.take<uint8_t>((size_t)nr);
+            elem = c.take<uint64_t>(rstride * na);
+            gfirst = c.take<uint32_t>((size_t)ng);
+            gdepth = c.take<uint8_t>((size_t)ng);
+            fin = c.take<uint64_t>(gstride * na);
+            sel = c.take<uint32_t>((size_t)ng);
+            tval = c.take<uint64_t>((size_t)nt * na);
+            tfirst = c.take<WaggHeads>(nt);
+            tcnt = c.take<uint32_t>(nt);
+            tot1 = c.take<uint32_t>(1);
+        })) return r.nomem();
+    // the lower stage: rows -> value runs
+    const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nr + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
+    LAUNCH(ctx, "k_gd_heads", k_gd_heads, tgrid, top, depth, r.un, tcount + (size_t)top * ntiles, ntiles, rpos, rdepth, nr);
+    if (na) LAUNCH(ctx, "k_gd_elems", k_gd_elems, rgrid, r.table->stage, gd, r.s.refs, r.s.perm, rpos, r.un, nr, rstride, elem);
+    // the upper stage: value runs -> groups, a lower level of the grouping sets over the runs (positions: run indices)
+    LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, fgrid, ag, L, rdepth, elem, rstride, nr, tval, tfirst, tcnt, nt);
+    if (na) LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, nr, tval, nt);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 1, tcnt, nt, tot1);
+    LAUNCH(ctx, "k_gs_run", k_gs_run, fgrid, ag, L, 0, rdepth, (const uint32_t*)nullptr, elem, rstride, nr, tval, tcnt, nt, fin, gstride, gdepth, gfirst, ng);
+    LAUNCH(ctx, "k_gd_finish", k_gd_finish, r.row_grid(), r.table->stage, gd, r.s.refs, r.s.perm, rpos, gfirst, r.un, nr, ng, (uint32_t)r.m, gstride, fin, sel);
+    r.sel = sel;
+    for (r.ncols = 0; r.ncols < ag.n; ++r.ncols) r.col_src[r.ncols] = fin + (size_t)r.ncols * gstride;
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -2196,6 +2359,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_QUANTILES: if (step.out || !all_kept) step_rc = step_quantiles(r); break;
         case STEP_EXCLUDES: if (step.out) step_rc = step_excludes(r); break;
         case STEP_GROUPS: step_rc = step_groups(r); break;            // (the rows themselves are the step's: always)
+        case STEP_DISTINCTS: step_rc = step_distincts(r); break;      // (likewise)
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -2504,6 +2668,38 @@ int sdqh_table_grouping_sets(sdqh_ctx* ctx, const sdqh_table* table, int64_t min
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_group_distinct(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int nterms, const sdqh_sort_term* in, int ngroup,
+                              int naggs, const sdqh_distinct_agg* aggs, int64_t limit, int64_t capacity,
+                              int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
+    const char* who = "table_group_distinct";
+    bool ok = naggs >= 1 && naggs <= SDQH_GD_MAX_AGGS && aggs && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && ngroup >= 0 && ngroup < nterms;
+    for (int a = 0; ok && a < naggs; ++a) ok = aggs[a].op >= SDQH_GD_COUNT_DISTINCT && aggs[a].op <= SDQH_GD_COUNT;
+    SortStep st = sort_step(STEP_DISTINCTS, 0, out_aggs);
+    st.filters = true; st.per_limit = 0;                              // no row is kept for its rank: the count is the groups', known behind the depth pass
+    st.ngroup = ngroup;
+    st.aggs.n = st.gd.n = ok ? naggs : 0;
+    // the measures in front of window_enter, as sdqh_table_grouping_sets checks them: every argument error comes before SDQH_ERR_UNSUPPORTED
+    for (int a = 0; ctx && table && ok && a < naggs; ++a) {
+        const sdqh_distinct_agg& g = aggs[a];
+        DevWagg& d = st.aggs.a[a];
+        st.gd.op[a] = g.op;
+        const bool measured = g.op == SDQH_GD_SUM_DISTINCT || g.op == SDQH_GD_AVG_DISTINCT || g.op == SDQH_GD_MODE;      // (the others ignore their measure)
+        if (measured)
+            if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind, g.index, g.is_f64, st.gd.sk[a])) return rc;
+        // the upper stage's fold: sums of ones, lengths and measures; the MODE word under WAGG_UMAX as a MAX over int64
+        const bool mode = g.op == SDQH_GD_MODE || g.op == SDQH_GD_MODE_COUNT;
+        const bool sums = g.op == SDQH_GD_SUM_DISTINCT || g.op == SDQH_GD_AVG_DISTINCT;
+        d.op = mode ? SDQH_WAGG_MAX : (sums ? SDQH_WAGG_SUM : SDQH_WAGG_COUNT);
+        d.frame = SDQH_FRAME_ROWS;
+        d.sk = st.gd.sk[a];
+        if (!sums) d.sk.is_f64 = 0;
+        d.cls = fold_class(d.op, d.sk.is_f64, true);
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, 0, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
 // what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
 // a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
 static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, bool has_narrow, int64_t* narrow_max_width) {
@@ -2512,6 +2708,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_group_distinct_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_distinct_geometry", tile_rows, false, nullptr); }
 int sdqh_grouping_sets_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "grouping_sets_geometry", tile_rows, false, nullptr); }
 int sdqh_window_exclude_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_exclude_geometry", tile_rows, true, narrow_max_width); }
 int sdqh_window_quantile_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_quantile_geometry", tile_rows, false, nullptr); }

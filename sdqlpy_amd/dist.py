@@ -62,7 +62,9 @@ def refuse_window(top):
     result.FrameRequest), values over sliding frames (sliding: result.SlideRequest), over value / group frames (ranged:
     result.RangeRequest), over frames with rows taken out (excluding: result.ExcludeRequest) and functions of the group's size (quantiles: result.QuantileRequest) are single-GPU operations: a partition's rows may lie on several ranks, and ranking or folding them takes an
     exchange by partition key that the runner does not have."""
-    from .result import ExcludeRequest, FrameRequest, GroupingRequest, QuantileRequest, RangeRequest, SlideRequest, WindowRequest
+    from .result import DistinctRequest, ExcludeRequest, FrameRequest, GroupingRequest, QuantileRequest, RangeRequest, SlideRequest, WindowRequest
+    if isinstance(top, DistinctRequest):
+        raise frontend.UnsupportedQuery("distincts runs on one GPU: the multi-GPU runner has no exchange by partition key")
     if isinstance(top, GroupingRequest):
         raise frontend.UnsupportedQuery("grouping_sets runs on one GPU: the multi-GPU runner has no exchange by partition key")
     if isinstance(top, ExcludeRequest):

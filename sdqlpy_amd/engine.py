@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
+from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -182,6 +182,10 @@ class Engine:
         # GROUP BY ROLLUP / CUBE / GROUPING SETS over a result (result.GroupingRequest) likewise, where the library has the grouping sets
         # extension (abi.Context.table_grouping_sets) — route "grouping_sets", one call per chain of sets, noted with "sets", "aggs", "calls"
         self.device_grouping_sets = os.environ.get("SDQLPY_AMD_DEVICE_GROUPING_SETS", "1") != "0"
+        # aggregates over the distinct values of a group (distincts: result.DistinctRequest) likewise, where the library has the group
+        # distinct extension (abi.Context.table_group_distinct) — route "group_distinct", one call per value column, noted with "per",
+        # "aggs" and "calls"
+        self.device_group_distinct = os.environ.get("SDQLPY_AMD_DEVICE_GROUP_DISTINCT", "1") != "0"
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1738,6 +1742,7 @@ class _FrameSpec(list):
 # The requests with partitions, in the order they are told apart: class -> (route, Engine switch, Library flag, the attribute that
 # lists the request's columns — None: ranks only —, the most columns the device takes)
 _WINDOW_ROUTES = (
+    (DistinctRequest, "group_distinct", "device_group_distinct", "has_group_distinct", "aggs", abi.GD_MAX_AGGS),
     (GroupingRequest, "grouping_sets", "device_grouping_sets", "has_grouping_sets", "aggs", abi.GS_MAX_AGGS),
     (FrameRequest, "window_agg", "device_window_agg", "has_window_agg", "aggs", abi.WAGG_MAX_AGGS),
     (SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS),
@@ -1754,27 +1759,38 @@ def _order_spec(top, spec_of, decoded_of):
     decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
     text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest)):
+    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest, DistinctRequest)):
         return spec
     spec = _FrameSpec(spec)
     if isinstance(top, (RangeRequest, ExcludeRequest)):
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
     measured = [a[2] for a in getattr(top, next(items for cls, _, _, _, items, _ in _WINDOW_ROUTES if isinstance(top, cls)))]
+    if isinstance(top, DistinctRequest):                     # only a sum or an average reads the column's numbers; a count needs its runs alone, and a
+        measured = [col if op in ("sum_distinct", "avg_distinct") else None for _, op, col in top.aggs]      # mode copies 64 bits, whatever they stand for
     cols = list(dict.fromkeys(col for col in measured if col is not None))
     plain = spec_of([(c, "asc") for c in cols], False) if cols else []      # (a QuantileRequest may measure nothing)
     if plain is not None:
         by_name = dict(zip(cols, plain))
         spec.measures = [by_name.get(col) for col in measured]
+        if isinstance(top, DistinctRequest):                 # a mode: the stored column behind the value's term, underived — text comes back as the reference
+            for i, (_, op, col) in enumerate(top.aggs):      # the table stores, a packed field as the key that holds it: decoded as the column itself is
+                if op == "mode":
+                    t = spec[top.npartition + top.values.index(col)]
+                    spec.measures[i] = (t[0], t[1], False, bool(t[3]))
     return spec
 
 
 def _note_order_route(eng, top, spec, route):
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets") and _term_text(t) is not None]}
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets", "group_distinct") and _term_text(t) is not None]}
     if isinstance(top, tuple(cls for cls, *_ in _WINDOW_ROUTES)):      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
     if isinstance(top, GroupingRequest):                     # the sets as listed, the aggregates, and how many device calls serve them
         note["sets"], note["aggs"], note["calls"] = [list(s) for s in top.sets], [list(a) for a in top.aggs], len(top.chains()) if route == "grouping_sets" else 0
+    elif isinstance(top, DistinctRequest):                   # "per": the grouping columns, "order": the value columns; "host_measures": a sum or an
+        calls = top.calls()                                  # average over a column the device cannot read as numbers (text, packed, decoded)
+        note["aggs"], note["calls"] = [list(a) for a in top.aggs], len(calls or ()) if route == "group_distinct" else 0
+        note["host_measures"] = spec is not None and getattr(spec, "measures", None) is None
     elif isinstance(top, FrameRequest):                      # the aggregates in the order of their columns
         note["aggs"] = [list(a) for a in top.aggs]
     elif isinstance(top, SlideRequest):                      # lag / lead as the `first` they are, unbounded sides None
@@ -1818,6 +1834,9 @@ def _finish_top(rs, ordered, top):
             rows = np.nonzero(ordered.rank.set_of == s)[0]
             pieces.append(({c: rs.column(c)[rows] for c in cols}, [np.asarray(a)[rows] for a in ordered.rank], len(rows)))
         return grouped_result(top, rs.column, pieces)
+    if isinstance(top, DistinctRequest):                    # the device's groups: `by` of their first rows and an aggregate a column
+        names = [nm for nm, _ in top.by]
+        return ResultSet(names + [name for name, _, _ in top.aggs], [rs.column(nm) for nm in names] + [np.asarray(a) for a in ordered.rank])
     if isinstance(top, FrameRequest):                       # the device's aggregates, a column each
         for name, _, _, _ in top.aggs:
             if name in rs.columns:
@@ -1928,6 +1947,10 @@ def _order_route(eng, top, spec):
     "grouping_sets" abi.Context.table_grouping_sets, once per chain of sets (_grouping_calls): a GroupingRequest of at most GS_MAX_AGGS
                  aggregates whose measures are underived numeric columns, over at most SORT_MAX_KEYS grouping columns (the grouping
                  sets extension and Engine.device_grouping_sets on; terms as for "window")
+    "group_distinct" abi.Context.table_group_distinct, once per value column (_distinct_calls): a DistinctRequest of at most GD_MAX_AGGS
+                 aggregates per value column (DistinctRequest.calls) whose sum / avg / mode read underived numeric columns, its
+                 grouping and value columns together at most SORT_MAX_KEYS (the group distinct extension and
+                 Engine.device_group_distinct on; terms as for "window")
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1942,6 +1965,11 @@ def _order_route(eng, top, spec):
             cols = None if items is None else getattr(top, items)
             if cls is ExcludeRequest:                            # (a frame's default is its seventh member: read as a range's, its sixth — an
                 cols = [(name, op, col, lo, hi, None if op == "avg" else default) for name, op, col, _, lo, hi, default in cols]      # average's is a plain double, never written back as an integer)
+            if cls is DistinctRequest:                           # (the limit is per call: DistinctRequest.calls)
+                cols = cols if top.calls() is not None else None
+                limit = len(top.aggs)
+                fits = cols is not None and _columns_fit(cols, limit, spec)
+                return route if fits and on(switch, extension) and terms_ok else "host"
             fits = _columns_fit(cols, limit, spec)
             if fits and cls is RangeRequest:
                 fits = _range_offsets(top, spec) is not None
@@ -2047,10 +2075,41 @@ def _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits):
     return joined(0, 0), joined(1, 1), joined(2, 1), joined(3, 0), cols
 
 
+def _mode_decoded(raw, measure, col, keys, payload, key_fields_of):
+    """The column `col` of a "group_distinct" route's mode: raw = the 64 bits of the stored column `measure` names at the winning rows
+    — put in that column's place among the rows' own arrays and decoded by key_fields_of(keys, payload), the result's own decoding."""
+    bits = np.ascontiguousarray(raw).view(np.int64)
+    if measure[0] == abi.SORT_KEY:
+        keys = bits
+    else:
+        payload = {src: (bits if src == measure[1] else np.asarray(payload[src])) for src in range(len(payload))}
+    return np.asarray(dict(key_fields_of(keys, payload))[col])
+
+
+def _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits):
+    """The route "group_distinct": one abi.Context.table_group_distinct call per value column of top (DistinctRequest.calls) — terms =
+    the grouping terms and that column's — and the rows of the first call beside every call's aggregates, in the order of top.aggs:
+    (keys, payload, values, hits, columns).  Every call returns the same groups in the same order: they are ordered by `by` alone."""
+    nby = top.npartition
+    values = top.values
+    cols, rows = [None] * len(top.aggs), None
+    for value, members in top.calls():
+        aggs = []
+        for i in members:
+            _, op, _ = top.aggs[i]
+            aggs.append((DISTINCT_OPS.index(op),) + _measure_args(spec.measures[i], None, None, spec, None)[:3])
+        got = eng.ctx.table_group_distinct(table, min_hits, terms[:nby] + [terms[nby + values.index(value)]], nby, aggs, abi.SORT_ALL, cap, want_hits=want_hits)
+        rows = got if rows is None else rows
+        cap = max(cap, len(got[0]))
+        for i, a in zip(members, got[4]):
+            cols[i] = a
+    return rows[0], rows[1], rows[2], rows[3], cols
+
+
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
     """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile" and "window_exclude" of _order_route: one waited-for call whose arrays are sized from the previous run
     of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets") else "sorted", hint_key)
+    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets", "group_distinct") else "sorted", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
@@ -2061,6 +2120,8 @@ def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
         got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
     elif route == "grouping_sets":
         got = _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits)
+    elif route == "group_distinct":
+        got = _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits)
     elif route == "window_agg":
         aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
         got = eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
@@ -2189,6 +2250,21 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             for i, (_, op, col) in enumerate(top.aggs):
                 if op not in ("count", "avg") and col in bt.int_values:
                     ordered.rank[i] = np.rint(ordered.rank[i]).astype(np.int64)
+        if isinstance(ordered, _Ranked) and isinstance(top, DistinctRequest):   # likewise for what is summed or copied; an average stays the double it is
+            ordered.rank = [np.rint(a).astype(np.int64) if op in ("sum_distinct", "mode") and col in bt.int_values else a for a, (_, op, col) in zip(ordered.rank, top.aggs)]
+
+            def key_fields_of(keys, payload):                # the key fields of rows, as the three ways below decode them
+                if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:
+                    from . import xplan
+                    return xplan._decode_radix(keys, bt.key_radix[0], bt.key_radix[1])
+                if bt.key_parts is not None and out_key_fields == [(bt.key_name, "key")]:
+                    decs = getattr(bt, "key_part_decoders", None) or [None, None]
+                    return [(bt.key_parts[0], _decode_column(keys >> 32, decs[0], np.int64)), (bt.key_parts[1], _decode_column(keys & 0xFFFFFFFF, decs[1], np.int64))]
+                return [(f, keys if src == "key" and bt.key_decoder is None else _decode_column(keys, bt.key_decoder, np.int64) if src == "key"
+                         else _decode_column(payload[src], bt.decoder_of(fields_of.get(f), src), bt.payload_dtypes[src])) for f, src in out_key_fields]
+            for i, (_, op, col) in enumerate(top.aggs):      # a mode of a key field: the 64 bits the table stores, decoded in the field's own place
+                if op == "mode" and col not in vnames:
+                    ordered.rank[i] = _mode_decoded(ordered.rank[i], spec.measures[i], col, keys, payload, key_fields_of)
         if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
             ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
@@ -2288,6 +2364,18 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         if got is not None:
             keys, payload = got[0], got[1]
             ordered = _Ranked(got[4]) if len(got) > 4 else True
+            if isinstance(top, DistinctRequest):             # a mode: the stored 64 bits, decoded in the field's own place
+                def key_fields_of(keys, payload):
+                    if value.key_parts is not None:
+                        decs = getattr(value, "key_part_decoders", None) or [None, None]
+                        own = [(value.key_parts[0], _decode_column(keys >> 32, decs[0], np.int64)), (value.key_parts[1], _decode_column(keys & 0xFFFFFFFF, decs[1], np.int64))]
+                    else:
+                        own = [(value.key_name, _decode_column(keys, value.key_decoder, np.int64))]
+                    return own + [(fname, keys if src == "key" else _decode_column(payload[src], value.decoder_of(fname, src), value.payload_dtypes[src]))
+                                  for fname, src in value.val_fields]
+                for i, (_, op, col) in enumerate(top.aggs):
+                    if op == "mode":
+                        ordered.rank[i] = _mode_decoded(ordered.rank[i], spec.measures[i], col, keys, payload, key_fields_of)
         else:
             keys, payload, _, _ = _compact(eng, value.table, 0, hint_key, want_values=False, want_hits=False)
             ordered = False

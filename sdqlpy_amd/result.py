@@ -655,6 +655,99 @@ def grouped_result(req, column_of, pieces):
     return ResultSet(names + [n for n, _, _ in req.aggs] + ["grouping"], cols)
 
 
+DISTINCT_OPS = ("count_distinct", "sum_distinct", "avg_distinct", "mode", "mode_count", "count")      # their positions are abi.GD_COUNT_DISTINCT .. GD_COUNT
+DISTINCT_MEASURED = ("sum_distinct", "avg_distinct", "mode")      # the ops that read their value column's values, not only its runs
+DISTINCT_MAX_AGGS = 4                                      # abi.GD_MAX_AGGS: the aggregates of one device call
+
+
+class DistinctRequest(WindowRequest):
+    """Aggregates over the distinct values of a group, travelling where a WindowRequest travels: [1] = the grouping columns `by` with
+    their directions (npartition of them) followed by the value columns, ascending, in order of first appearance; aggs = [(name of
+    the new column, op: a name of DISTINCT_OPS, value column or None for a count)].  The result holds `by` and the aggregates, one row
+    per group, ordered by `by`; every other column of the query's result is dropped."""
+
+    def __new__(cls, by, aggs):
+        aggs = [(str(n), str(op), None if col is None else str(col)) for n, op, col in aggs]
+        values = list(dict.fromkeys(col for _, _, col in aggs if col is not None))
+        self = WindowRequest.__new__(cls, WINDOW_ALL, list(by) + [(v, "asc") for v in values], len(by), 0, WINDOW_ALL, None)
+        self.aggs = aggs
+        names = [nm for nm, _ in self.by]
+        if not aggs or len(set(names)) != len(names) or any(v in names for v in values):
+            raise ValueError("distincts: bad columns")
+        if any(op not in DISTINCT_OPS or (col is None) != (op == "count") for _, op, col in aggs):
+            raise ValueError("distincts: bad aggregate")
+        return self
+
+    values = property(lambda self: [nm for nm, _ in self.order])
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms one for one, the value columns with them."""
+        to = {old: new for (old, _), (new, _) in zip(self[1], terms)}
+        return DistinctRequest(terms[:self.npartition], [(n, op, to.get(col, col)) for n, op, col in self.aggs])
+
+    def calls(self):
+        """The aggregates as the device serves them: [(value column, [indices into aggs])], one call per value column in order of
+        first appearance, a `count` riding in the first call that has room — or None where the device cannot: no value column at
+        all, or more than DISTINCT_MAX_AGGS aggregates in one call."""
+        out = [(v, [i for i, (_, _, col) in enumerate(self.aggs) if col == v]) for v in self.values]
+        for i, (_, _, col) in enumerate(self.aggs):
+            if col is None:
+                room = [idx for _, idx in out if len(idx) < DISTINCT_MAX_AGGS]
+                if not room:
+                    return None
+                room[0].append(i)
+        return out if out and all(len(idx) <= DISTINCT_MAX_AGGS for _, idx in out) else None
+
+
+def distinct_request(columns, by, aggs):
+    """The checked DistinctRequest of distincts: by = a list of columns, a column `name` or (name, "asc" | "desc") (an empty list: the
+    whole result is one group); aggs = {new column: (op, value column)} with op a name of DISTINCT_OPS — "count" takes None, every
+    other op a column name.  columns: the result's column names when they are known (None: checked when the result is).  KeyError for
+    a column the result lacks or a new column it has already, ValueError for everything else."""
+    if isinstance(by, str) or not isinstance(by, (list, tuple)):
+        raise ValueError("distincts: by is a list of columns")
+    terms = []
+    for c in by:
+        name, d = (c, "asc") if isinstance(c, str) else (c[0], c[1]) if isinstance(c, (list, tuple)) and len(c) == 2 else (None, None)
+        if not isinstance(name, str) or d not in ("asc", "desc"):
+            raise ValueError("distincts: a column is a name or (name, 'asc' | 'desc')")
+        if name in [nm for nm, _ in terms]:
+            raise ValueError("distincts: column %r comes twice in by" % name)
+        terms.append((name, d))
+    if not isinstance(aggs, dict) or not aggs:
+        raise ValueError("distincts: aggs is a non-empty dict {new column: (op, value column)}")
+    out = []
+    for name, spec in aggs.items():
+        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) != 2:
+            raise ValueError("distincts: an aggregate is name: (op, value column)")
+        op, col = spec
+        if op not in DISTINCT_OPS:
+            raise ValueError("distincts: op is one of %s, not %r" % (", ".join(DISTINCT_OPS), op))
+        if op == "count":
+            if col is not None:
+                raise ValueError("distincts: count takes no value column (None)")
+        elif not isinstance(col, str):
+            raise ValueError("distincts: %s needs a value column, a column name" % op)
+        elif col in [nm for nm, _ in terms]:
+            raise ValueError("distincts: the value column %r is a grouping column" % col)
+        out.append((name, op, col))
+    if len(set(n for n, _, _ in out) | set(nm for nm, _ in terms)) != len(out) + len(terms):
+        raise ValueError("distincts: a new column has the name of a grouping column")
+    req = DistinctRequest(terms, out)
+    if columns is not None:
+        check_distinct_columns(req, columns)
+    return req
+
+
+def check_distinct_columns(req, columns):
+    for nm, _ in req[1]:
+        if nm not in columns:
+            raise KeyError("distincts: the result has no column %r" % nm)
+    for name, _, _ in req.aggs:
+        if name in columns:
+            raise KeyError("distincts: the result already has a column %r" % name)
+
+
 def slide_empty(default, is_f64, what="sliding"):
     """What an empty frame gives for a measure of dtype float64 (is_f64) or int64: `default`, or with None NaN / 0.  ValueError for a
     default that does not fit the dtype: a float for an int64 column, an int outside int64."""
@@ -1239,6 +1332,74 @@ class ResultSet:
         """GROUP BY CUBE(by): every subset of `by`, by ascending `grouping` mask."""
         return self.grouping_sets(cube_sets(by), aggs)
 
+    def distincted(self, req):
+        """The groups of a DistinctRequest, what sdqh_table_group_distinct does on the device (include/sdqh_sort_distinct.h), on the
+        host: per value column a stable lexsort by `by` and the column (order_image: the device's total order, so -0.0 and +0.0 are two
+        values and NaNs are equal only bit for bit), a group wherever a neighbour differs in `by`, a value run wherever it differs at
+        all, and np.ufunc.reduceat of the runs over the groups.  count_distinct / mode_count / count are int64, sum_distinct and mode
+        take the column's dtype (a sum of integers wraps; mode may be text), avg_distinct is float64: the sum as a double over the
+        number of runs.  Among runs of equal length the mode is the first in order.  An empty result has no groups."""
+        self._wait()
+        check_distinct_columns(req, self.columns)
+        n = self._n
+        by = [(nm, d == "desc") for nm, d in req.by]
+        by_images = [order_image(self.column(nm), desc) for nm, desc in by]
+        out, first_rows = {}, None
+        for v in req.values or [None]:
+            images = by_images + ([order_image(self.column(v), False)] if v is not None else [])
+            idx = np.lexsort(images[::-1]) if images else np.arange(n)    # stable: ties keep the stored order
+            ghead, rhead = np.zeros(n, bool), np.zeros(n, bool)
+            if n:
+                ghead[0] = rhead[0] = True
+            for i, u in enumerate(images):
+                diff = u[idx][1:] != u[idx][:-1]
+                rhead[1:] |= diff
+                if i < len(by_images):
+                    ghead[1:] |= diff
+            rstart = np.nonzero(rhead)[0]                                 # the runs' first sorted positions
+            rlen = np.diff(np.append(rstart, n)).astype(np.int64)
+            gfirst = np.nonzero(ghead[rstart])[0]                         # per group its first run
+            g = len(gfirst)
+            runs = np.diff(np.append(gfirst, len(rstart))).astype(np.int64)
+            if first_rows is None:
+                first_rows = idx[rstart[gfirst]] if g else np.zeros(0, np.int64)
+            for name, op, col in req.aggs:
+                if col != v and not (col is None and name not in out):
+                    continue
+                if op == "count":
+                    out[name] = np.add.reduceat(rlen, gfirst) if g else np.zeros(0, np.int64)
+                    continue
+                x = self.column(col)
+                if op == "count_distinct":
+                    out[name] = runs
+                elif op in ("mode", "mode_count"):
+                    if not g:
+                        out[name] = np.zeros(0, np.int64) if op == "mode_count" else x[:0]
+                        continue
+                    longest = np.maximum.reduceat(rlen, gfirst)
+                    group_of = np.repeat(np.arange(g), runs)
+                    winner = np.minimum.reduceat(np.where(rlen == longest[group_of], np.arange(len(rstart)), len(rstart)), gfirst)
+                    out[name] = longest if op == "mode_count" else x[idx[rstart[winner]]]
+                else:
+                    if x.dtype.kind not in "iubf":
+                        raise ValueError("distincts: %s of column %r: the column is not numeric" % (op, col))
+                    is_f = x.dtype.kind == "f"
+                    r = np.ascontiguousarray(x, np.float64 if is_f else np.int64)[idx[rstart]]
+                    if not g:
+                        out[name] = np.zeros(0, np.float64 if is_f or op == "avg_distinct" else np.int64)
+                        continue
+                    total = np.add.reduceat(r, gfirst) if is_f else np.add.reduceat(r.view(np.uint64), gfirst).view(np.int64)
+                    out[name] = total if op == "sum_distinct" else total.astype(np.float64) / runs.astype(np.float64)
+        names = [nm for nm, _ in req.by]
+        return ResultSet(names + [nm for nm, _, _ in req.aggs], [self.column(nm)[first_rows] for nm in names] + [out[nm] for nm, _, _ in req.aggs])
+
+    def distincts(self, by, aggs):
+        """Aggregates over the distinct values of every group of `by` (a list of columns, a column a name or (name, "asc" | "desc")):
+        aggs = {new column: (op, value column)}, op in DISTINCT_OPS — COUNT(DISTINCT x), SUM / AVG(DISTINCT x), the most frequent x
+        and how often it comes, and ("count", None), the group's rows.  The result holds `by` and the aggregates, one row per group,
+        ordered by `by` (see DistinctRequest)."""
+        return self.distincted(distinct_request(self.columns, by, aggs))
+
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:
         aggs = {new column: (op, measure column or None, lo, hi[, default])}, op in SLIDE_OPS, the frame rows [row + lo, row + hi] of
@@ -1255,6 +1416,8 @@ class ResultSet:
         """The rows a WindowRequest keeps, in its order, with its rank column when it names one (a FrameRequest: framed)."""
         if isinstance(req, GroupingRequest):
             return self.grouped(req)
+        if isinstance(req, DistinctRequest):
+            return self.distincted(req)
         if isinstance(req, FrameRequest):
             return self.framed(req)
         if isinstance(req, SlideRequest):

@@ -522,6 +522,22 @@ def sdql_compile(in_type):
             from .result import cube_sets
             return grouping_sets(cube_sets(by), aggs)
 
+        def distincts(by, aggs):
+            """The same query finished with aggregates over the DISTINCT values of every group of `by` — a list of columns, a column a
+            name or (name, "asc" | "desc"); an empty list: the whole result is one group —, aggs = {new column: (op, value column)}, op
+            in "count_distinct" / "sum_distinct" / "avg_distinct" / "mode" / "mode_count" / "count" (count takes None), e.g.
+            ``q16.distincts(["p_brand"], {"types": ("count_distinct", "p_type"), "usual_size": ("mode", "p_size"), "rows": ("count",
+            None)})(ps, pa, su)``.  The result holds `by` and the aggregates and none of the query's other columns, one row per
+            group, ordered by `by`.  count_distinct, mode_count and count are int64, sum_distinct and mode take the value column's
+            dtype (mode may be text; among equally frequent values the first in ascending order), avg_distinct is float64.  Names
+            and ops are checked here, before anything is launched."""
+            from . import engine, frontend
+            from .result import distinct_request
+            if "plan" not in cache:
+                cache["plan"] = frontend.lower_function(func, in_type)
+            req = distinct_request(engine.result_columns(cache["plan"]), list(by) if isinstance(by, (list, tuple)) else by, aggs)     # checked before anything is launched
+            return lambda *args: run(args, req)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -534,6 +550,7 @@ def sdql_compile(in_type):
         wrapper.rollup = rollup
         wrapper.cube = cube
         wrapper.grouping_sets = grouping_sets
+        wrapper.distincts = distincts
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
