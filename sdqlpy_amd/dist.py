@@ -58,27 +58,13 @@ _COLL_ON_RECORDED_STREAM = os.environ.get("SDQLPY_AMD_DIST_COLL_ON_RECORDED_STRE
 
 
 def refuse_window(top):
-    """ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest), aggregates over window frames (over:
-    result.FrameRequest), values over sliding frames (sliding: result.SlideRequest), over value / group frames (ranged:
-    result.RangeRequest), over frames with rows taken out (excluding: result.ExcludeRequest) and functions of the group's size (quantiles: result.QuantileRequest) are single-GPU operations: a partition's rows may lie on several ranks, and ranking or folding them takes an
-    exchange by partition key that the runner does not have."""
-    from .result import DistinctRequest, ExcludeRequest, FrameRequest, GroupingRequest, QuantileRequest, RangeRequest, SlideRequest, WindowRequest
-    if isinstance(top, DistinctRequest):
-        raise frontend.UnsupportedQuery("distincts runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, GroupingRequest):
-        raise frontend.UnsupportedQuery("grouping_sets runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, ExcludeRequest):
-        raise frontend.UnsupportedQuery("excluding runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, QuantileRequest):
-        raise frontend.UnsupportedQuery("quantiles runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, RangeRequest):
-        raise frontend.UnsupportedQuery("ranged runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, SlideRequest):
-        raise frontend.UnsupportedQuery("sliding runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, FrameRequest):
-        raise frontend.UnsupportedQuery("over runs on one GPU: the multi-GPU runner has no exchange by partition key")
-    if isinstance(top, WindowRequest):
-        raise frontend.UnsupportedQuery("top_per / numbered run on one GPU: the multi-GPU runner has no exchange by partition key")
+    """ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest) and every request that travels as one (over, sliding,
+    ranged, excluding, quantiles, grouping_sets, distincts: its subclasses) are single-GPU operations: a partition's rows may lie on
+    several ranks, and ranking or folding them takes an exchange by partition key that the runner does not have."""
+    from .result import WindowRequest
+    if isinstance(top, WindowRequest):                           # (a plain window is known to the user by two methods)
+        raise frontend.UnsupportedQuery("%s on one GPU: the multi-GPU runner has no exchange by partition key"
+                                        % ("top_per / numbered run" if top.method == "window" else top.method + " runs"))
 
 
 class DistributedRunner:

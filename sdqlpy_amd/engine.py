@@ -161,31 +161,11 @@ class Engine:
         # order_routes: per result finalised with an ORDER BY where it was ordered — {"route": "topk" | "sorted" | "sorted_by" | "host",
         # "ranked": the order columns that went through a rank table} (the last 256)
         self.order_routes = collections.deque(maxlen=256)
-        # ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest) ranks on the device where the library has the window
-        # extension (abi.Context.table_window) — route "window", noted with the extra keys "per", "kind", "per_limit"
-        self.device_window = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW", "1") != "0"
-        # aggregates over window frames (over: result.FrameRequest) fold on the device where the library has the window aggregate
-        # extension (abi.Context.table_window_agg) — route "window_agg", noted with the extra keys "per" and "aggs"
-        self.device_window_agg = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_AGG", "1") != "0"
-        # values over sliding frames (sliding: result.SlideRequest) likewise, where the library has the window slide extension
-        # (abi.Context.table_window_slide) — route "window_slide", noted with the extra keys "per" and "slides"
-        self.device_window_slide = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_SLIDE", "1") != "0"
-        # values over value and group frames (ranged: result.RangeRequest) likewise, where the library has the window range extension
-        # (abi.Context.table_window_range) — route "window_range", noted with the extra keys "per", "unit" and "ranges"
-        self.device_window_range = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_RANGE", "1") != "0"
-        # values over frames with rows taken out (excluding: result.ExcludeRequest) likewise, where the library has the window exclude
-        # extension (abi.Context.table_window_exclude) — route "window_exclude", noted with the extra keys "per", "exclude" and "frames"
-        self.device_window_exclude = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_EXCLUDE", "1") != "0"
-        # functions of the group's size (quantiles: result.QuantileRequest) likewise, where the library has the window quantile extension
-        # (abi.Context.table_window_quantile) — route "window_quantile", noted with the extra keys "per", "per_limit" and "quantiles"
-        self.device_window_quantile = os.environ.get("SDQLPY_AMD_DEVICE_WINDOW_QUANTILE", "1") != "0"
-        # GROUP BY ROLLUP / CUBE / GROUPING SETS over a result (result.GroupingRequest) likewise, where the library has the grouping sets
-        # extension (abi.Context.table_grouping_sets) — route "grouping_sets", one call per chain of sets, noted with "sets", "aggs", "calls"
-        self.device_grouping_sets = os.environ.get("SDQLPY_AMD_DEVICE_GROUPING_SETS", "1") != "0"
-        # aggregates over the distinct values of a group (distincts: result.DistinctRequest) likewise, where the library has the group
-        # distinct extension (abi.Context.table_group_distinct) — route "group_distinct", one call per value column, noted with "per",
-        # "aggs" and "calls"
-        self.device_group_distinct = os.environ.get("SDQLPY_AMD_DEVICE_GROUP_DISTINCT", "1") != "0"
+        # the requests with partitions (result.WindowRequest and its subclasses) are served on the device where the library has their
+        # extension and their switch is on — one switch per kind, device_window .. device_group_distinct, set from its environment
+        # variable SDQLPY_AMD_DEVICE_...; 0 forces the host route (A/B measurements, tests).  _WINDOW_ROUTES says which is whose.
+        for rec in _WINDOW_ROUTES:
+            setattr(self, rec.switch, os.environ.get(rec.env, "1") != "0")
         self.plan_graphs_always = os.environ.get("SDQLPY_AMD_PLAN_GRAPHS_ALWAYS", "0") == "1"      # (default: only while no other result is in flight, see PreparedPlan.run)
         self.graph_stats = {"recorded": 0, "launched": 0, "refused": 0, "dropped": 0}
         lanes = os.environ.get("SDQLPY_AMD_LANES", "")
@@ -1739,70 +1719,41 @@ class _FrameSpec(list):
     decoded_order = ()       # the ORDER BY columns of a RangeRequest that are text or decoded on the host (_order_column_decoded)
 
 
-# The requests with partitions, in the order they are told apart: class -> (route, Engine switch, Library flag, the attribute that
-# lists the request's columns — None: ranks only —, the most columns the device takes)
-_WINDOW_ROUTES = (
-    (DistinctRequest, "group_distinct", "device_group_distinct", "has_group_distinct", "aggs", abi.GD_MAX_AGGS),
-    (GroupingRequest, "grouping_sets", "device_grouping_sets", "has_grouping_sets", "aggs", abi.GS_MAX_AGGS),
-    (FrameRequest, "window_agg", "device_window_agg", "has_window_agg", "aggs", abi.WAGG_MAX_AGGS),
-    (SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS),
-    (RangeRequest, "window_range", "device_window_range", "has_window_range", "ranges", abi.WRANGE_MAX_AGGS),
-    (QuantileRequest, "window_quantile", "device_window_quantile", "has_window_quantile", "quants", abi.WQUANT_MAX_COLS),
-    (ExcludeRequest, "window_exclude", "device_window_exclude", "has_window_exclude", "frames", abi.WEX_MAX_COLS),
-    (WindowRequest, "window", "device_window", "has_window", None, 0),
-)
+def _route_of(top):
+    """The record of _WINDOW_ROUTES that serves the request `top`; None for a plain (k, order)."""
+    return next((rec for rec in _WINDOW_ROUTES if isinstance(top, rec.request)), None)
 
 
 def _order_spec(top, spec_of, decoded_of):
-    """The device's columns for `top`: spec_of(order, eng_or_None) is _device_sort_spec over the table at hand.  A FrameRequest's
-    measures go through the same mapping with no engine to derive anything: whatever needs a decoder or a derivation is None there.
-    decoded_of(name) is _order_column_decoded over the same table: a RangeRequest's spec notes which of its ORDER BY columns are
-    text or decoded on the host (decoded_order) — here, so that no caller can leave it out."""
+    """The device's columns for `top`: spec_of(order, eng_or_None) is _device_sort_spec over the table at hand.  The measures of a
+    request that has any (its record's `measured`) go through the same mapping with no engine to derive anything: whatever needs a
+    decoder or a derivation is None there.  decoded_of(name) is _order_column_decoded over the same table: the spec of a request with
+    value frames notes which of its ORDER BY columns are text or decoded on the host (decoded_order) — here, so that no caller can
+    leave it out."""
     spec = spec_of(top[1], True)
-    if spec is None or not isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest, DistinctRequest)):
+    rec = _route_of(top)
+    if spec is None or rec is None or rec.measured is None:
         return spec
     spec = _FrameSpec(spec)
-    if isinstance(top, (RangeRequest, ExcludeRequest)):
+    if rec.value_frames:
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
-    measured = [a[2] for a in getattr(top, next(items for cls, _, _, _, items, _ in _WINDOW_ROUTES if isinstance(top, cls)))]
-    if isinstance(top, DistinctRequest):                     # only a sum or an average reads the column's numbers; a count needs its runs alone, and a
-        measured = [col if op in ("sum_distinct", "avg_distinct") else None for _, op, col in top.aggs]      # mode copies 64 bits, whatever they stand for
-    cols = list(dict.fromkeys(col for col in measured if col is not None))
+    measured = rec.measured(top, spec)
+    cols = list(dict.fromkeys(col for col in measured if isinstance(col, str)))
     plain = spec_of([(c, "asc") for c in cols], False) if cols else []      # (a QuantileRequest may measure nothing)
     if plain is not None:
         by_name = dict(zip(cols, plain))
-        spec.measures = [by_name.get(col) for col in measured]
-        if isinstance(top, DistinctRequest):                 # a mode: the stored column behind the value's term, underived — text comes back as the reference
-            for i, (_, op, col) in enumerate(top.aggs):      # the table stores, a packed field as the key that holds it: decoded as the column itself is
-                if op == "mode":
-                    t = spec[top.npartition + top.values.index(col)]
-                    spec.measures[i] = (t[0], t[1], False, bool(t[3]))
+        spec.measures = [by_name[col] if isinstance(col, str) else col for col in measured]
     return spec
 
 
 def _note_order_route(eng, top, spec, route):
+    rec = _route_of(top)
+    terms = route == "sorted_by" or (rec is not None and route == rec.route)      # the routes that take terms: a text column orders through its rank table
     note = {"route": route, "k": int(min(top[0], abi.SORT_ALL)), "order": [nm for nm, _ in top[1]],
-            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if route in ("sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets", "group_distinct") and _term_text(t) is not None]}
-    if isinstance(top, tuple(cls for cls, *_ in _WINDOW_ROUTES)):      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
+            "ranked": [nm for (nm, _), t in zip(top[1], spec or ()) if terms and _term_text(t) is not None]}
+    if rec is not None:                                      # "order": the ORDER BY names alone; the PARTITION BY names are "per"
         note["order"], note["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
-    if isinstance(top, GroupingRequest):                     # the sets as listed, the aggregates, and how many device calls serve them
-        note["sets"], note["aggs"], note["calls"] = [list(s) for s in top.sets], [list(a) for a in top.aggs], len(top.chains()) if route == "grouping_sets" else 0
-    elif isinstance(top, DistinctRequest):                   # "per": the grouping columns, "order": the value columns; "host_measures": a sum or an
-        calls = top.calls()                                  # average over a column the device cannot read as numbers (text, packed, decoded)
-        note["aggs"], note["calls"] = [list(a) for a in top.aggs], len(calls or ()) if route == "group_distinct" else 0
-        note["host_measures"] = spec is not None and getattr(spec, "measures", None) is None
-    elif isinstance(top, FrameRequest):                      # the aggregates in the order of their columns
-        note["aggs"] = [list(a) for a in top.aggs]
-    elif isinstance(top, SlideRequest):                      # lag / lead as the `first` they are, unbounded sides None
-        note["slides"] = [list(a) for a in top.slides]
-    elif isinstance(top, RangeRequest):                      # and the frames' unit
-        note["unit"], note["ranges"] = top.unit, [list(a) for a in top.ranges]
-    elif isinstance(top, ExcludeRequest):                    # what is taken out, and the frames with their own units
-        note["exclude"], note["frames"] = top.exclude, [list(a) for a in top.frames]
-    elif isinstance(top, QuantileRequest):                   # and the per-group limit it filters by
-        note["per_limit"], note["quantiles"] = int(min(top.per_limit, abi.SORT_ALL)), [list(a) for a in top.quants]
-    elif isinstance(top, WindowRequest):
-        note["kind"], note["per_limit"] = WINDOW_KINDS[top.kind], int(min(top.per_limit, abi.SORT_ALL))
+        note.update(rec.note(top, route, spec))
     eng.order_routes.append(note)
 
 
@@ -1822,51 +1773,37 @@ def _host_top(rs, top):
     return rs.windowed(top) if isinstance(top, WindowRequest) else rs.top(top[0], top[1])
 
 
+def _finish_groups(rs, ordered, top):
+    """... of a GroupingRequest: the device's groups, every chain's rows behind one another — the sets in listed order."""
+    pieces = []
+    for s, cols in enumerate(top.sets):
+        rows = np.nonzero(ordered.rank.set_of == s)[0]
+        pieces.append(({c: rs.column(c)[rows] for c in cols}, [np.asarray(a)[rows] for a in ordered.rank], len(rows)))
+    return grouped_result(top, rs.column, pieces)
+
+
+def _finish_distincts(rs, ordered, top):
+    """... of a DistinctRequest: the device's groups — `by` of their first rows and an aggregate a column."""
+    names = [nm for nm, _ in top.by]
+    return ResultSet(names + [name for name, _, _ in top.aggs], [rs.column(nm) for nm in names] + [np.asarray(a) for a in ordered.rank])
+
+
 def _finish_top(rs, ordered, top):
     """A result set whose rows the device may have ordered already (`ordered`) finished with `top`."""
     if top is None:
         return rs
     if not ordered:
         return _host_top(rs, top)
-    if isinstance(top, GroupingRequest):                    # the device's groups, every chain's rows behind one another: the sets in listed order
-        pieces = []
-        for s, cols in enumerate(top.sets):
-            rows = np.nonzero(ordered.rank.set_of == s)[0]
-            pieces.append(({c: rs.column(c)[rows] for c in cols}, [np.asarray(a)[rows] for a in ordered.rank], len(rows)))
-        return grouped_result(top, rs.column, pieces)
-    if isinstance(top, DistinctRequest):                    # the device's groups: `by` of their first rows and an aggregate a column
-        names = [nm for nm, _ in top.by]
-        return ResultSet(names + [name for name, _, _ in top.aggs], [rs.column(nm) for nm in names] + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, FrameRequest):                       # the device's aggregates, a column each
-        for name, _, _, _ in top.aggs:
-            if name in rs.columns:
-                raise KeyError("over: the result already has a column %r" % name)
-        return ResultSet(rs.columns + [name for name, _, _, _ in top.aggs], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, SlideRequest):                       # the device's slides, a column each
-        for name in (a[0] for a in top.slides):
-            if name in rs.columns:
-                raise KeyError("sliding: the result already has a column %r" % name)
-        return ResultSet(rs.columns + [a[0] for a in top.slides], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, RangeRequest):                       # the device's ranges, a column each
-        for name in (a[0] for a in top.ranges):
-            if name in rs.columns:
-                raise KeyError("ranged: the result already has a column %r" % name)
-        return ResultSet(rs.columns + [a[0] for a in top.ranges], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, ExcludeRequest):                     # the device's frames, a column each
-        for name in (a[0] for a in top.frames):
-            if name in rs.columns:
-                raise KeyError("excluding: the result already has a column %r" % name)
-        return ResultSet(rs.columns + [a[0] for a in top.frames], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, QuantileRequest):                    # the device's columns, one each
-        for name in (a[0] for a in top.quants):
-            if name in rs.columns:
-                raise KeyError("quantiles: the result already has a column %r" % name)
-        return ResultSet(rs.columns + [a[0] for a in top.quants], list(rs._cols) + [np.asarray(a) for a in ordered.rank])
-    if isinstance(top, WindowRequest) and top.name is not None:
-        if top.name in rs.columns:
-            raise KeyError("window: the result already has a column %r" % top.name)
-        return ResultSet(rs.columns + [top.name], list(rs._cols) + [np.asarray(ordered.rank)])
-    return rs
+    rec = _route_of(top)
+    if rec is None:
+        return rs
+    if rec.finish is not None:
+        return rec.finish(rs, ordered, top)
+    new = [(item[0], a) for item, a in zip(top.items, ordered.rank)] if rec.items else [(top.name, ordered.rank)] if top.name is not None else []
+    for name, _ in new:                                      # the device's columns, one each — or the ranks
+        if name in rs.columns:
+            raise KeyError("%s: the result already has a column %r" % (top.method, name))
+    return ResultSet(rs.columns + [name for name, _ in new], list(rs._cols) + [np.asarray(a) for _, a in new]) if new else rs
 
 
 def result_columns(plan):
@@ -1896,15 +1833,16 @@ def result_columns(plan):
 def _columns_fit(top_items, limit, spec):
     """Can the device take the columns `top_items` of a request with partitions (None: it has none) over the terms `spec`?  At most
     SORT_MAX_KEYS terms, at most `limit` columns, measures that are underived numeric columns (spec.measures), and — where a column has
-    a default, the sixth member of its tuple; an aggregate over a frame has none — no default beyond 2^53 for a column the table keeps
-    as integer-valued doubles: such a column takes its default as a double and back, and one no double holds stays on the host."""
+    a default, the last member of its tuple of six or more; an aggregate over a frame has none — no default beyond 2^53 for a column
+    the table keeps as integer-valued doubles: such a column takes its default as a double and back, and one no double holds stays on
+    the host (an average's default is a plain double, never written back as an integer: exempt)."""
     if not 1 <= len(spec) <= abi.SORT_MAX_KEYS:
         return False
     if top_items is None:
         return True
     if len(top_items) > limit or getattr(spec, "measures", None) is None:
         return False
-    return not any(len(item) > 5 and item[2] in spec.int_values and item[5] is not None and not isinstance(item[5], (float, np.floating)) and abs(int(item[5])) > 1 << 53
+    return not any(len(item) > 5 and item[1] != "avg" and item[2] in spec.int_values and item[-1] is not None and not isinstance(item[-1], (float, np.floating)) and abs(int(item[-1])) > 1 << 53
                    for item in top_items)
 
 
@@ -1928,29 +1866,10 @@ def _order_route(eng, top, spec):
     "topk"       sdqh_table_topk: at most MAX_TOPK rows by at most MAX_SORT_KEYS plain columns
     "sorted"     abi.Context.table_sorted: plain columns beyond that (the ordering extension, Engine.device_sort on)
     "sorted_by"  abi.Context.table_sorted_by: some term is derived, whatever k is (the sort-terms extension, Engine.device_sort on)
-    "window"     abi.Context.table_window: every WindowRequest the device takes — never the three above, which know nothing of
-                 partitions (the window extension and Engine.device_window on; derived terms need what "sorted_by" needs)
-    "window_agg" abi.Context.table_window_agg: a FrameRequest of at most WAGG_MAX_AGGS aggregates whose measures are underived numeric
-                 columns (the window aggregate extension and Engine.device_window_agg on; terms as for "window")
-    "window_slide" abi.Context.table_window_slide: a SlideRequest of at most WSLIDE_MAX_AGGS slides whose measures are underived numeric
-                 columns (the window slide extension and Engine.device_window_slide on; terms as for "window"); not with a default
-                 beyond 2^53 for a column the table keeps as integer-valued doubles
-    "window_range" abi.Context.table_window_range: a RangeRequest under "window_slide"'s conditions (at most WRANGE_MAX_AGGS ranges; the
-                 window range extension and Engine.device_window_range on) whose offsets the device's order term can take
-                 (_range_offsets): a value frame needs an underived or arithmetically derived term, no text ranks
-    "window_quantile" abi.Context.table_window_quantile: a QuantileRequest under "window_slide"'s conditions (at most WQUANT_MAX_COLS
-                 columns, underived numeric measures, NTH's default within 2^53 for a column kept as integer-valued doubles; the window
-                 quantile extension and Engine.device_window_quantile on; terms as for "window")
-    "window_exclude" abi.Context.table_window_exclude: an ExcludeRequest under "window_range"'s conditions (at most WEX_MAX_COLS columns;
-                 the window exclude extension and Engine.device_window_exclude on): its "value" columns' offsets are taken as a
-                 RangeRequest's are, "groups" and "rows" columns take ints (_exclude_offsets)
-    "grouping_sets" abi.Context.table_grouping_sets, once per chain of sets (_grouping_calls): a GroupingRequest of at most GS_MAX_AGGS
-                 aggregates whose measures are underived numeric columns, over at most SORT_MAX_KEYS grouping columns (the grouping
-                 sets extension and Engine.device_grouping_sets on; terms as for "window")
-    "group_distinct" abi.Context.table_group_distinct, once per value column (_distinct_calls): a DistinctRequest of at most GD_MAX_AGGS
-                 aggregates per value column (DistinctRequest.calls) whose sum / avg / mode read underived numeric columns, its
-                 grouping and value columns together at most SORT_MAX_KEYS (the group distinct extension and
-                 Engine.device_group_distinct on; terms as for "window")
+    the route of its record (_WINDOW_ROUTES, where every such route is described): a WindowRequest the device takes — never the
+                 three above, which know nothing of partitions.  At most SORT_MAX_KEYS terms (derived terms need what "sorted_by"
+                 needs), its columns within the record's limit with underived numeric measures (_columns_fit), whatever else the
+                 record asks (`fits`), the library's extension and the Engine's switch on
     "host"       everything else: the caller compacts and result.py orders."""
     if spec is None:
         return "host"
@@ -1960,22 +1879,11 @@ def _order_route(eng, top, spec):
     k, n = top[0], len(spec)
     derived = any(_term_derived(t) for t in spec)
     terms_ok = not derived or on("device_sort", "has_sort_terms")
-    for cls, route, switch, extension, items, limit in _WINDOW_ROUTES:
-        if isinstance(top, cls):
-            cols = None if items is None else getattr(top, items)
-            if cls is ExcludeRequest:                            # (a frame's default is its seventh member: read as a range's, its sixth — an
-                cols = [(name, op, col, lo, hi, None if op == "avg" else default) for name, op, col, _, lo, hi, default in cols]      # average's is a plain double, never written back as an integer)
-            if cls is DistinctRequest:                           # (the limit is per call: DistinctRequest.calls)
-                cols = cols if top.calls() is not None else None
-                limit = len(top.aggs)
-                fits = cols is not None and _columns_fit(cols, limit, spec)
-                return route if fits and on(switch, extension) and terms_ok else "host"
-            fits = _columns_fit(cols, limit, spec)
-            if fits and cls is RangeRequest:
-                fits = _range_offsets(top, spec) is not None
-            if fits and cls is ExcludeRequest:
-                fits = _exclude_offsets(top, spec) is not None
-            return route if fits and on(switch, extension) and terms_ok else "host"
+    rec = _route_of(top)
+    if rec is not None:
+        items = top.items if rec.items else None
+        fits = _columns_fit(items, len(items) if rec.per_call else rec.limit, spec) and (rec.fits is None or rec.fits(top, spec))
+        return rec.route if fits and on(rec.switch, rec.flag) and terms_ok else "host"
     if derived:
         return "sorted_by" if k >= 1 and n <= abi.SORT_MAX_KEYS and terms_ok else "host"
     if 1 <= k <= abi.MAX_TOPK and n <= abi.MAX_SORT_KEYS:
@@ -2106,49 +2014,156 @@ def _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits):
     return rows[0], rows[1], rows[2], rows[3], cols
 
 
+class _Route(tuple):
+    """How one class of request with partitions is served on the device.  The row reads (the request class, the route's name as
+    _order_route gives it, the Engine switch, the Library flag, the attribute that lists the request's columns — None: ranks only —,
+    the most columns the device takes); beside it
+    call(eng, table, min_hits, top, terms, spec, k, cap, want_hits): the request's columns marshalled and the abi.Context.table_* call(s)
+    note(top, route, spec): the keys of the Engine.order_routes entry beyond "route", "k", "order", "ranked" and "per"
+    integral(item): does the column take its measure's dtype — the device's doubles are rounded back to int64 for a measure the table
+        keeps as integer-valued doubles (BuiltTable.int_values)
+    fits(top, spec): what the device asks beyond _columns_fit, or None
+    measured(top, spec): per column the measure _order_spec looks up as a plain sort column — a name, None, or the column itself where
+        the request knows it — or None: the request measures nothing and its spec stays a plain list
+    value_frames: its frames may be offsets of the ORDER BY value (the spec notes decoded_order)
+    per_call: the limit holds per device call (the request says how it splits), not for the request
+    renote: the note follows the result's aliases (_finalize) — not where it has always named the table's own columns
+    raw_modes: a "mode" column comes back as the stored 64 bits, decoded as the field itself is (_mode_decoded)
+    finish(rs, ordered, top): the result where it is not the rows with a column each appended, or None."""
+
+    def __new__(cls, request, route, switch, flag, items, limit, call, note, integral=None, fits=None, measured=lambda top, spec: [item[2] for item in top.items],
+                value_frames=False, per_call=False, renote=True, raw_modes=False, finish=None):
+        self = tuple.__new__(cls, (request, route, switch, flag, items, limit))
+        self.request, self.route, self.switch, self.flag, self.items, self.limit = self
+        self.env = "SDQLPY_AMD_" + switch.upper()               # the switch's environment variable
+        self.call, self.note, self.integral, self.fits, self.measured = call, note, integral, fits, measured
+        self.value_frames, self.per_call, self.renote, self.raw_modes, self.finish = value_frames, per_call, renote, raw_modes, finish
+        return self
+
+
+def _window_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    return eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap, want_hits=want_hits, want_rank=top.name is not None)
+
+
+def _agg_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
+    return eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
+
+
+def _slide_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    slides = []
+    for (_, op, measure, lo, hi, default), col in zip(top.slides, spec.measures):
+        kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "sliding")
+        slides.append((SLIDE_OPS.index(op), kind, index, is_f64, abi.SLIDE_UNBOUNDED_PRECEDING if lo is None else lo,
+                       abi.SLIDE_UNBOUNDED_FOLLOWING if hi is None else hi, empty))
+    return eng.ctx.table_window_slide(table, min_hits, top.npartition, terms, slides, k, cap, want_hits=want_hits)
+
+
+def _range_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    ranges = []
+    for (_, op, measure, _, _, default), col, (lo, hi) in zip(top.ranges, spec.measures, _range_offsets(top, spec)):
+        kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "ranged")
+        ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
+    return eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
+
+
+def _exclude_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    return eng.ctx.table_window_exclude(table, min_hits, top.npartition, terms, _exclude_columns(top, spec), k, cap, want_hits=want_hits)
+
+
+def _quantile_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    quants = []
+    for (_, fn, measure, arg, p, default), col in zip(top.quants, spec.measures):
+        kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "quantiles" if fn == "nth" else None)      # (NTH alone has a default)
+        quants.append((QUANTILE_FNS.index(fn), kind, index, is_f64, 0 if arg is None else arg, 0.0 if p is None else p, empty))
+    return eng.ctx.table_window_quantile(table, min_hits, top.npartition, terms, quants, min(int(top.per_limit), abi.SORT_ALL), k, cap, want_hits=want_hits)
+
+
+def _distinct_measured(top, spec):
+    """Only a sum or an average reads the column's numbers; a count needs its runs alone, and a mode copies 64 bits, whatever they
+    stand for: the stored column behind the value's term, underived — text comes back as the reference the table stores, a packed
+    field as the key that holds it: decoded as the column itself is."""
+    def stored(col):
+        t = spec[top.npartition + top.values.index(col)]
+        return t[0], t[1], False, bool(t[3])
+    return [col if op in ("sum_distinct", "avg_distinct") else stored(col) if op == "mode" else None for _, op, col in top.aggs]
+
+
+def _distinct_note(top, route, spec):
+    """("per": the grouping columns, "order": the value columns)  "host_measures": a sum or an average over a column the device
+    cannot read as numbers (text, packed, decoded)."""
+    return {"aggs": [list(a) for a in top.aggs], "calls": len(top.calls() or ()) if route == "group_distinct" else 0,
+            "host_measures": spec is not None and getattr(spec, "measures", None) is None}
+
+
+# The requests with partitions, in the order they are told apart (a subclass before its base).  The switches default to on; with
+# SDQLPY_AMD_DEVICE_...=0 the host serves the kind (A/B measurements, tests).  Terms as for "window" throughout: derived ones need what
+# the route "sorted_by" needs.
+_WINDOW_ROUTES = (
+    # aggregates over the distinct values of a group (distincts), one abi.Context.table_group_distinct call per value column
+    # (_distinct_calls): at most GD_MAX_AGGS aggregates per value column (DistinctRequest.calls) whose sum / avg / mode read underived
+    # numeric columns, its grouping and value columns together at most SORT_MAX_KEYS.  Noted with "per", "aggs", "calls", "host_measures"
+    _Route(DistinctRequest, "group_distinct", "device_group_distinct", "has_group_distinct", "aggs", abi.GD_MAX_AGGS,
+           call=lambda eng, table, min_hits, top, terms, spec, k, cap, want_hits: _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits),
+           note=_distinct_note, integral=lambda item: item[1] in ("sum_distinct", "mode"),      # what is summed or copied; an average stays the double it is
+           fits=lambda top, spec: top.calls() is not None, measured=_distinct_measured, per_call=True, renote=False, raw_modes=True, finish=_finish_distincts),
+    # GROUP BY ROLLUP / CUBE / GROUPING SETS over a result, one abi.Context.table_grouping_sets call per chain of sets (_grouping_calls):
+    # at most GS_MAX_AGGS aggregates whose measures are underived numeric columns, over at most SORT_MAX_KEYS grouping columns.  Noted
+    # with the sets as listed, the aggregates, and how many device calls serve them
+    _Route(GroupingRequest, "grouping_sets", "device_grouping_sets", "has_grouping_sets", "aggs", abi.GS_MAX_AGGS,
+           call=lambda eng, table, min_hits, top, terms, spec, k, cap, want_hits: _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits),
+           note=lambda top, route, spec: {"sets": [list(s) for s in top.sets], "aggs": [list(a) for a in top.aggs], "calls": len(top.chains()) if route == "grouping_sets" else 0},
+           integral=lambda item: item[1] not in ("count", "avg"), finish=_finish_groups),
+    # aggregates over window frames (over), abi.Context.table_window_agg: at most WAGG_MAX_AGGS aggregates whose measures are underived
+    # numeric columns.  Noted with the aggregates in the order of their columns
+    _Route(FrameRequest, "window_agg", "device_window_agg", "has_window_agg", "aggs", abi.WAGG_MAX_AGGS, call=_agg_call,
+           note=lambda top, route, spec: {"aggs": [list(a) for a in top.aggs]}, integral=lambda item: item[1] != "count"),      # an integer-valued sum folded as doubles
+    # values over sliding frames (sliding), abi.Context.table_window_slide: at most WSLIDE_MAX_AGGS slides whose measures are underived
+    # numeric columns; not with a default beyond 2^53 for a column the table keeps as integer-valued doubles.  Noted with the slides:
+    # lag / lead as the `first` they are, unbounded sides None
+    _Route(SlideRequest, "window_slide", "device_window_slide", "has_window_slide", "slides", abi.WSLIDE_MAX_AGGS, call=_slide_call,
+           note=lambda top, route, spec: {"slides": [list(a) for a in top.slides]}, integral=lambda item: item[1] != "count"),      # whatever a slide takes of such a column is an integer
+    # values over value and group frames (ranged), abi.Context.table_window_range: under "window_slide"'s conditions (at most
+    # WRANGE_MAX_AGGS ranges) and with offsets the device's order term can take (_range_offsets): a value frame needs an underived or
+    # arithmetically derived term, no text ranks.  Noted with the frames' unit and the ranges
+    _Route(RangeRequest, "window_range", "device_window_range", "has_window_range", "ranges", abi.WRANGE_MAX_AGGS, call=_range_call,
+           note=lambda top, route, spec: {"unit": top.unit, "ranges": [list(a) for a in top.ranges]}, integral=lambda item: item[1] != "count",
+           fits=lambda top, spec: _range_offsets(top, spec) is not None, value_frames=True),
+    # functions of the group's size (quantiles), abi.Context.table_window_quantile: under "window_slide"'s conditions (at most
+    # WQUANT_MAX_COLS columns, NTH's default within 2^53 for a column kept as integer-valued doubles).  Noted with the per-group limit it
+    # filters by and the columns
+    _Route(QuantileRequest, "window_quantile", "device_window_quantile", "has_window_quantile", "quants", abi.WQUANT_MAX_COLS, call=_quantile_call,
+           note=lambda top, route, spec: {"per_limit": int(min(top.per_limit, abi.SORT_ALL)), "quantiles": [list(a) for a in top.quants]},
+           integral=lambda item: item[1] in ("nth", "percentile_disc")),      # what is copied; a percentile_cont of such a column read its doubles as they are
+    # values over frames with rows taken out (excluding), abi.Context.table_window_exclude: under "window_range"'s conditions (at most
+    # WEX_MAX_COLS columns): its "value" columns' offsets are taken as a RangeRequest's are, "groups" and "rows" columns take ints
+    # (_exclude_offsets).  Noted with what is taken out, and the frames with their own units
+    _Route(ExcludeRequest, "window_exclude", "device_window_exclude", "has_window_exclude", "frames", abi.WEX_MAX_COLS, call=_exclude_call,
+           note=lambda top, route, spec: {"exclude": top.exclude, "frames": [list(a) for a in top.frames]}, integral=lambda item: item[1] not in ("count", "avg"),
+           fits=lambda top, spec: _exclude_offsets(top, spec) is not None, value_frames=True),
+    # ORDER BY ... LIMIT per group (top_per / numbered), abi.Context.table_window: every WindowRequest of at most SORT_MAX_KEYS terms.
+    # Noted with "kind" and "per_limit"
+    _Route(WindowRequest, "window", "device_window", "has_window", None, 0, call=_window_call,
+           note=lambda top, route, spec: {"kind": WINDOW_KINDS[top.kind], "per_limit": int(min(top.per_limit, abi.SORT_ALL))}, measured=None),
+)
+
+
 def _ordered_call(eng, route, table, min_hits, hint_key, top, spec, want_hits):
-    """The routes "sorted", "sorted_by", "window", "window_agg", "window_slide", "window_range", "window_quantile" and "window_exclude" of _order_route: one waited-for call whose arrays are sized from the previous run
-    of the same plan step; the text a term names is replaced by its resident ranks column (Engine.rank_column: made on first use)."""
-    hint_key = ("window" if route in ("window", "window_agg", "window_slide", "window_range", "window_quantile", "window_exclude", "grouping_sets", "group_distinct") else "sorted", hint_key)
+    """The routes of _order_route beyond "topk": "sorted", "sorted_by", or the route of top's record — one waited-for call (a record may
+    make several) whose arrays are sized from the previous run of the same plan step; the text a term names is replaced by its resident
+    ranks column (Engine.rank_column: made on first use)."""
+    rec = _route_of(top)
+    hint_key = ("sorted" if rec is None else "window", hint_key)
     hint = eng.compact_hints.get(hint_key)
     cap = 4096 if hint is None else hint + hint // 8 + 1024
     k = min(int(top[0]), abi.SORT_ALL)
     terms = [t if _term_text(t) is None else t[:7] + (eng.rank_column(t[7]),) for t in spec]
-    if route == "sorted":
+    if rec is not None:
+        got = rec.call(eng, table, min_hits, top, terms, spec, k, cap, want_hits)
+    elif route == "sorted":
         got = eng.ctx.table_sorted(table, min_hits, k, spec, cap, want_hits=want_hits)
-    elif route == "sorted_by":
-        got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
-    elif route == "grouping_sets":
-        got = _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits)
-    elif route == "group_distinct":
-        got = _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits)
-    elif route == "window_agg":
-        aggs = [(WAGG_OPS.index(op), FRAMES.index(frame)) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _, frame), col in zip(top.aggs, spec.measures)]
-        got = eng.ctx.table_window_agg(table, min_hits, top.npartition, terms, aggs, k, cap, want_hits=want_hits)
-    elif route == "window_slide":
-        slides = []
-        for (_, op, measure, lo, hi, default), col in zip(top.slides, spec.measures):
-            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "sliding")
-            slides.append((SLIDE_OPS.index(op), kind, index, is_f64, abi.SLIDE_UNBOUNDED_PRECEDING if lo is None else lo,
-                           abi.SLIDE_UNBOUNDED_FOLLOWING if hi is None else hi, empty))
-        got = eng.ctx.table_window_slide(table, min_hits, top.npartition, terms, slides, k, cap, want_hits=want_hits)
-    elif route == "window_range":
-        ranges = []
-        for (_, op, measure, _, _, default), col, (lo, hi) in zip(top.ranges, spec.measures, _range_offsets(top, spec)):
-            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "ranged")
-            ranges.append((SLIDE_OPS.index(op), kind, index, is_f64, RANGE_UNITS.index(top.unit), lo, hi, empty))
-        got = eng.ctx.table_window_range(table, min_hits, top.npartition, terms, ranges, k, cap, want_hits=want_hits)
-    elif route == "window_exclude":
-        got = eng.ctx.table_window_exclude(table, min_hits, top.npartition, terms, _exclude_columns(top, spec), k, cap, want_hits=want_hits)
-    elif route == "window_quantile":
-        quants = []
-        for (_, fn, measure, arg, p, default), col in zip(top.quants, spec.measures):
-            kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "quantiles" if fn == "nth" else None)      # (NTH alone has a default)
-            quants.append((QUANTILE_FNS.index(fn), kind, index, is_f64, 0 if arg is None else arg, 0.0 if p is None else p, empty))
-        got = eng.ctx.table_window_quantile(table, min_hits, top.npartition, terms, quants, min(int(top.per_limit), abi.SORT_ALL), k, cap, want_hits=want_hits)
     else:
-        got = eng.ctx.table_window(table, min_hits, top.npartition, terms, top.kind, min(int(top.per_limit), abi.SORT_ALL), k, cap,
-                                   want_hits=want_hits, want_rank=top.name is not None)
+        got = eng.ctx.table_sorted_by(table, min_hits, k, terms, cap, want_hits=want_hits)
     eng.compact_hints[hint_key] = len(got[0])
     return got
 
@@ -2237,22 +2252,12 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
                     env["__rows_out__"] = collect.rows_out      # (PlanGraph: the recording is launched again only when no view of an earlier result is alive)
                 return p
         keys, payload, values, hits, ordered = _fetch_entries(eng, bt.table, 1, hint_key, top, spec, want_hits=want_hits, lazy=lazy)
-        if isinstance(ordered, _Ranked) and isinstance(top, FrameRequest):      # an integer-valued sum folded as doubles: the conversion its own column gets
-            ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _) in zip(ordered.rank, top.aggs)]
-        if isinstance(ordered, _Ranked) and isinstance(top, SlideRequest):      # likewise: whatever a slide takes of such a column is an integer
-            ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.slides)]
-        if isinstance(ordered, _Ranked) and isinstance(top, QuantileRequest):   # likewise for what is copied (nth, percentile_disc); a percentile_cont of such a
-            ordered.rank = [np.rint(a).astype(np.int64) if fn in ("nth", "percentile_disc") and col in bt.int_values else a     # column read its doubles as they are
-                            for a, (_, fn, col, _, _, _) in zip(ordered.rank, top.quants)]
-        if isinstance(ordered, _Ranked) and isinstance(top, ExcludeRequest):    # likewise; an average stays the double it is
-            ordered.rank = [np.rint(a).astype(np.int64) if op not in ("count", "avg") and col in bt.int_values else a for a, (_, op, col, _, _, _, _) in zip(ordered.rank, top.frames)]
-        if isinstance(ordered, _Ranked) and isinstance(top, GroupingRequest):   # likewise, in place (the columns carry set_of); an average stays the double it is
-            for i, (_, op, col) in enumerate(top.aggs):
-                if op not in ("count", "avg") and col in bt.int_values:
+        rec = _route_of(top)
+        if isinstance(ordered, _Ranked) and rec is not None:               # a column that takes its measure's dtype: the conversion the measure's own column gets —
+            for i, item in enumerate(top.items):                           # in place (a "grouping_sets" route's columns carry set_of)
+                if rec.integral(item) and item[2] in bt.int_values:
                     ordered.rank[i] = np.rint(ordered.rank[i]).astype(np.int64)
-        if isinstance(ordered, _Ranked) and isinstance(top, DistinctRequest):   # likewise for what is summed or copied; an average stays the double it is
-            ordered.rank = [np.rint(a).astype(np.int64) if op in ("sum_distinct", "mode") and col in bt.int_values else a for a, (_, op, col) in zip(ordered.rank, top.aggs)]
-
+        if isinstance(ordered, _Ranked) and rec is not None and rec.raw_modes:
             def key_fields_of(keys, payload):                # the key fields of rows, as the three ways below decode them
                 if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:
                     from . import xplan
@@ -2265,8 +2270,6 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
             for i, (_, op, col) in enumerate(top.aggs):      # a mode of a key field: the 64 bits the table stores, decoded in the field's own place
                 if op == "mode" and col not in vnames:
                     ordered.rank[i] = _mode_decoded(ordered.rank[i], spec.measures[i], col, keys, payload, key_fields_of)
-        if isinstance(ordered, _Ranked) and isinstance(top, RangeRequest):      # likewise
-            ordered.rank = [np.rint(a).astype(np.int64) if op != "count" and col in bt.int_values else a for a, (_, op, col, _, _, _) in zip(ordered.rank, top.ranges)]
         values = [values[j] for j in range(nv)]
         if getattr(bt, "key_radix", None) is not None and out_key_fields == [(bt.key_name, "key")]:    # several key fields in one mixed-radix integer
             from . import xplan
@@ -2364,7 +2367,7 @@ def _materialize(eng, value, env, hint_key=None, top=None, lazy_ok=False, defer=
         if got is not None:
             keys, payload = got[0], got[1]
             ordered = _Ranked(got[4]) if len(got) > 4 else True
-            if isinstance(top, DistinctRequest):             # a mode: the stored 64 bits, decoded in the field's own place
+            if getattr(_route_of(top), "raw_modes", False):  # a mode: the stored 64 bits, decoded in the field's own place
                 def key_fields_of(keys, payload):
                     if value.key_parts is not None:
                         decs = getattr(value, "key_part_decoders", None) or [None, None]
@@ -2414,27 +2417,18 @@ def _finalize(eng, op, env, top=None):
             elif len(side) == 1:
                 names[name] = side[0]
         inner_order = [(names.get(n, n), d) for n, d in top[1]]
-        inner_top = top.renamed(inner_order, names) if isinstance(top, (FrameRequest, SlideRequest, RangeRequest, QuantileRequest, ExcludeRequest, GroupingRequest)) else (top.renamed(inner_order) if isinstance(top, WindowRequest) else (top[0], inner_order))
+        inner_top = top.renamed(inner_order, names) if isinstance(top, WindowRequest) else (top[0], inner_order)
     noted = eng.order_routes[-1] if eng.order_routes else None
     d = _materialize(eng, src_val, env, hint_key=id(op), top=inner_top, lazy_ok=True, defer=op.out in env.get("__defer__", ()))     # (only a ResultSet is made of it: that waits for the rows itself)
     if top is not None and inner_top is not top and eng.order_routes and eng.order_routes[-1] is not noted:      # the route speaks of the result's own column names, not the aliased sides'
         route = eng.order_routes[-1]
         ranked = {i for i, (nm, _) in enumerate(inner_top[1]) if nm in route["ranked"]}
         route["order"], route["ranked"] = [nm for nm, _ in top[1]], [nm for i, (nm, _) in enumerate(top[1]) if i in ranked]
-        if isinstance(top, WindowRequest):
+        rec = _route_of(top)
+        if rec is not None:
             route["order"], route["per"] = [nm for nm, _ in top.order], [nm for nm, _ in top.by]
-        if isinstance(top, (FrameRequest, GroupingRequest)):
-            route["aggs"] = [list(a) for a in top.aggs]
-        if isinstance(top, GroupingRequest):
-            route["sets"] = [list(s) for s in top.sets]
-        if isinstance(top, SlideRequest):
-            route["slides"] = [list(a) for a in top.slides]
-        if isinstance(top, RangeRequest):
-            route["ranges"] = [list(a) for a in top.ranges]
-        if isinstance(top, ExcludeRequest):
-            route["frames"] = [list(a) for a in top.frames]
-        if isinstance(top, QuantileRequest):
-            route["quantiles"] = [list(a) for a in top.quants]
+            if rec.renote:
+                route.update(rec.note(top, route["route"], None))
     if isinstance(d, Pending):                              # launched, not waited for: the shaping below runs when it is collected
         return Pending(lambda: _shape_result(op, d.resolve(), top))
     return _shape_result(op, d, top)

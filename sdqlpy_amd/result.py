@@ -79,7 +79,17 @@ class WindowRequest(tuple):
     """ORDER BY ... LIMIT per group, travelling where a (k, order) of `top` travels: [0] = the limit on the whole result, [1] = the
     PARTITION BY terms followed by the ORDER BY terms — code that only orders reads it as a plain `top` — and beside them how many of
     the terms partition (npartition), the rank wanted (kind: a position in WINDOW_KINDS), the largest rank kept (per_limit) and the
-    name of the rank column the result gets (None: none)."""
+    name of the rank column the result gets (None: none).
+
+    The requests that travel the same way are its subclasses.  What tells them apart is said here once and declared by each: `method`,
+    its name as the user knows it and the prefix of its messages (`terms_method`: the one a missing PARTITION BY / ORDER BY column is
+    reported under — a window's, for every kind that keeps the rows); `items_attr`, the attribute that lists its new columns, a tuple
+    each with the column's name at [0] and its measure column (or None) at [2] — `items` reads it, () for a plain window; `served_by`,
+    the ResultSet method that serves it on the host; `reserved`, names its result takes for itself."""
+    method = terms_method = "window"
+    items_attr = None
+    served_by = "ranked"
+    reserved = ()
 
     def __new__(cls, k, terms, npartition, kind, per_limit, name=None):
         self = tuple.__new__(cls, (int(k), [(str(n), str(d)) for n, d in terms]))
@@ -91,9 +101,34 @@ class WindowRequest(tuple):
     by = property(lambda self: self[1][:self.npartition])
     order = property(lambda self: self[1][self.npartition:])
 
-    def renamed(self, terms):
-        """The same request over other column names (aliases of the same columns, term for term)."""
+    items = property(lambda self: getattr(self, self.items_attr) if self.items_attr else ())
+
+    def _with(self, terms, items):
+        """The request of the same class and settings over `terms` and the columns `items`."""
         return WindowRequest(self[0], terms, self.npartition, self.kind, self.per_limit, self.name)
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term (aliases of the same columns), the measures through
+        `names` (old name -> new)."""
+        names = names or {}
+        return self._with(terms, [item[:2] + (names.get(item[2], item[2]),) + item[3:] for item in self.items])
+
+    def check_columns(self, columns):
+        """KeyError for a column the result (its column names: `columns`) lacks, or a new column it has already."""
+        for nm, _ in self[1]:
+            if nm not in columns:
+                raise KeyError("%s: the result has no column %r" % (self.terms_method, nm))
+        if self.name is not None and self.name in columns:
+            raise KeyError("window: the result already has a column %r" % self.name)
+        for item in self.items:                                  # (the value columns of `distincts` are terms: checked above)
+            if item[2] is not None and item[2] not in columns:
+                raise KeyError("%s: the result has no column %r" % (self.method, item[2]))
+            if item[0] in columns or item[0] in self.reserved:
+                raise KeyError("%s: the result already has a column %r" % (self.method, item[0]))
+
+    def host(self, rs):
+        """The request served on the host: the ResultSet it makes of `rs`."""
+        return getattr(rs, self.served_by)(self)
 
 
 def window_request(columns, by, order, kind, per_limit, k=WINDOW_ALL, name=None):
@@ -115,41 +150,38 @@ def window_request(columns, by, order, kind, per_limit, k=WINDOW_ALL, name=None)
         raise ValueError("window: the rank column's name is a string")
     req = WindowRequest(k, terms, npartition, WINDOW_KINDS.index(kind), min(int(per_limit), WINDOW_ALL), name)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
-def check_window_columns(req, columns):
-    for nm, _ in req[1]:
-        if nm not in columns:
-            raise KeyError("window: the result has no column %r" % nm)
-    if req.name is not None and req.name in columns:
-        raise KeyError("window: the result already has a column %r" % req.name)
-    for name, _, col, _ in getattr(req, "aggs", ()):
-        if col is not None and col not in columns:
-            raise KeyError("over: the result has no column %r" % col)
-        if name in columns:
-            raise KeyError("over: the result already has a column %r" % name)
-    for name, _, col, _, _, _ in getattr(req, "slides", ()):
-        if col is not None and col not in columns:
-            raise KeyError("sliding: the result has no column %r" % col)
-        if name in columns:
-            raise KeyError("sliding: the result already has a column %r" % name)
-    for name, _, col, _, _, _ in getattr(req, "ranges", ()):
-        if col is not None and col not in columns:
-            raise KeyError("ranged: the result has no column %r" % col)
-        if name in columns:
-            raise KeyError("ranged: the result already has a column %r" % name)
-    for name, _, col, _, _, _, _ in getattr(req, "frames", ()):
-        if col is not None and col not in columns:
-            raise KeyError("excluding: the result has no column %r" % col)
-        if name in columns:
-            raise KeyError("excluding: the result already has a column %r" % name)
-    for name, _, col, _, _, _ in getattr(req, "quants", ()):
-        if col is not None and col not in columns:
-            raise KeyError("quantiles: the result has no column %r" % col)
-        if name in columns:
-            raise KeyError("quantiles: the result already has a column %r" % name)
+def _aggs_dict(who, aggs, shape, what="aggs", empty_ok=False):
+    """The dict a builder takes its new columns from, {new column: `shape`}: ValueError (under the method's name `who`) for anything else."""
+    if not isinstance(aggs, dict) or not (aggs or empty_ok):
+        raise ValueError("%s: %s is a %sdict {new column: %s}" % (who, what, "" if empty_ok else "non-empty ", shape))
+
+
+def _agg_spec(who, name, spec, shape, fits, what="an aggregate"):
+    """One entry of that dict: a name and a tuple or list whose length fits(len)."""
+    if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or not fits(len(spec)):
+        raise ValueError("%s: %s is name: %s" % (who, what, shape))
+
+
+def _agg_measure(who, op, col):
+    """An aggregate's measure: a column name, or None for a count."""
+    if col is None and op != "count":
+        raise ValueError("%s: %s needs a measure column" % (who, op))
+    if col is not None and not isinstance(col, str):
+        raise ValueError("%s: a measure is a column name" % who)
+
+
+def _agg_default(who, default):
+    if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
+        raise ValueError("%s: a default is a number, not %r" % (who, default))
+
+
+def _agg_frame(who, lo, hi):
+    if lo is not None and hi is not None and lo > hi:
+        raise ValueError("%s: the frame (%r, %r) ends before it starts" % (who, lo, hi))
 
 
 WAGG_OPS = ("sum", "count", "min", "max")                 # their positions are abi.WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX
@@ -161,6 +193,7 @@ class FrameRequest(WindowRequest):
     per-group limit and no rank column): [0] = the limit on the whole result, [1] = the PARTITION BY terms followed by the ORDER BY
     terms, npartition, and aggs = [(name of the new column, op: a name of WAGG_OPS, measure column or None for a count, frame: a
     name of FRAMES)] in the order the columns are appended."""
+    method, items_attr, served_by = "over", "aggs", "framed"
 
     def __new__(cls, k, terms, npartition, aggs):
         self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
@@ -169,10 +202,8 @@ class FrameRequest(WindowRequest):
             raise ValueError("over: bad aggregate")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
-        names = names or {}
-        return FrameRequest(self[0], terms, self.npartition, [(n, op, names.get(col, col), fr) for n, op, col, fr in self.aggs])
+    def _with(self, terms, items):
+        return FrameRequest(self[0], terms, self.npartition, items)
 
 
 def frame_request(columns, by, order, aggs, frame="range", k=WINDOW_ALL):
@@ -181,27 +212,22 @@ def frame_request(columns, by, order, aggs, frame="range", k=WINDOW_ALL):
     names when they are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has
     already, ValueError for everything else."""
     req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
-    if not isinstance(aggs, dict) or not aggs:
-        raise ValueError("over: aggs is a non-empty dict {new column: (op, measure[, frame])}")
+    _aggs_dict("over", aggs, "(op, measure[, frame])")
     if frame not in FRAMES:
         raise ValueError("over: frame is one of %s, not %r" % (", ".join(FRAMES), frame))
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (2, 3):
-            raise ValueError("over: an aggregate is name: (op, measure[, frame])")
+        _agg_spec("over", name, spec, "(op, measure[, frame])", lambda n: n in (2, 3))
         op, col, fr = spec[0], spec[1], (spec[2] if len(spec) == 3 else frame)
         if op not in WAGG_OPS:
             raise ValueError("over: op is one of %s, not %r" % (", ".join(WAGG_OPS), op))
         if fr not in FRAMES:
             raise ValueError("over: frame is one of %s, not %r" % (", ".join(FRAMES), fr))
-        if col is None and op != "count":
-            raise ValueError("over: %s needs a measure column" % op)
-        if col is not None and not isinstance(col, str):
-            raise ValueError("over: a measure is a column name")
+        _agg_measure("over", op, col)
         out.append((name, op, col, fr))
     req = FrameRequest(req[0], req[1], req.npartition, out)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
@@ -214,6 +240,7 @@ class SlideRequest(WindowRequest):
     of SLIDE_OPS, measure column or None for a count, lo, hi: the frame's offsets from the row — negative = preceding, None =
     unbounded —, default: what an empty frame gives, None = 0 for an int64 measure and NaN for a float64 one)] in the order the
     columns are appended.  lag / lead are `first` over (-k, -k) / (k, k) by the time they are here."""
+    method, items_attr, served_by = "sliding", "slides", "slid"
 
     def __new__(cls, k, terms, npartition, slides):
         self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
@@ -223,10 +250,8 @@ class SlideRequest(WindowRequest):
             raise ValueError("sliding: bad aggregate")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
-        names = names or {}
-        return SlideRequest(self[0], terms, self.npartition, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.slides])
+    def _with(self, terms, items):
+        return SlideRequest(self[0], terms, self.npartition, items)
 
 
 def _slide_int(x, what, who="sliding"):
@@ -242,12 +267,10 @@ def slide_request(columns, by, order, aggs, k=WINDOW_ALL):
     are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has already, ValueError
     for everything else (a default that does not fit its column is found when the column is known: slide_empty)."""
     req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
-    if not isinstance(aggs, dict) or not aggs:
-        raise ValueError("sliding: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default])}")
+    _aggs_dict("sliding", aggs, "(op, measure, lo, hi[, default])")
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) < 2:
-            raise ValueError("sliding: an aggregate is name: (op, measure, lo, hi[, default]) or (lag | lead, measure, k[, default])")
+        _agg_spec("sliding", name, spec, "(op, measure, lo, hi[, default]) or (lag | lead, measure, k[, default])", lambda n: n >= 2)
         op, col = spec[0], spec[1]
         if op in ("lag", "lead"):
             if len(spec) not in (3, 4):
@@ -260,23 +283,17 @@ def slide_request(columns, by, order, aggs, k=WINDOW_ALL):
         else:
             if op not in SLIDE_OPS:
                 raise ValueError("sliding: op is one of %s, lag, lead, not %r" % (", ".join(SLIDE_OPS), op))
-            if len(spec) not in (4, 5):
-                raise ValueError("sliding: an aggregate is name: (op, measure, lo, hi[, default])")
+            _agg_spec("sliding", name, spec, "(op, measure, lo, hi[, default])", lambda n: n in (4, 5))
             lo = None if spec[2] is None else _slide_int(spec[2], "a bound")
             hi = None if spec[3] is None else _slide_int(spec[3], "a bound")
             default = spec[4] if len(spec) == 5 else None
-            if lo is not None and hi is not None and lo > hi:
-                raise ValueError("sliding: the frame (%d, %d) ends before it starts" % (lo, hi))
-        if col is None and op != "count":
-            raise ValueError("sliding: %s needs a measure column" % op)
-        if col is not None and not isinstance(col, str):
-            raise ValueError("sliding: a measure is a column name")
-        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
-            raise ValueError("sliding: a default is a number, not %r" % (default,))
+            _agg_frame("sliding", lo, hi)
+        _agg_measure("sliding", op, col)
+        _agg_default("sliding", default)
         out.append((name, op, col, lo, hi, default))
     req = SlideRequest(req[0], req[1], req.npartition, out)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
@@ -290,6 +307,7 @@ class RangeRequest(WindowRequest):
     — of the ORDER BY value (unit "value": ints or floats) or in tie runs (unit "groups": ints), negative = preceding, None = unbounded
     —, default: what an empty frame gives, None = 0 for an int64 measure and NaN for a float64 one)] in the order the columns are
     appended."""
+    method, items_attr, served_by = "ranged", "ranges", "ranged_by"
 
     def __new__(cls, k, terms, npartition, unit, ranges):
         self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
@@ -302,10 +320,8 @@ class RangeRequest(WindowRequest):
             raise ValueError("ranged: a value frame is ordered by exactly one column")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
-        names = names or {}
-        return RangeRequest(self[0], terms, self.npartition, self.unit, [(n, op, names.get(col, col), lo, hi, d) for n, op, col, lo, hi, d in self.ranges])
+    def _with(self, terms, items):
+        return RangeRequest(self[0], terms, self.npartition, self.unit, items)
 
 
 def _range_offset(x, unit, who="ranged"):
@@ -329,30 +345,23 @@ def range_request(columns, by, order, aggs, unit="value", k=WINDOW_ALL):
         raise ValueError("ranged: unit is one of %s, not %r" % (", ".join(RANGE_UNITS), unit))
     if unit == "value" and len(req[1]) != req.npartition + 1:
         raise ValueError("ranged: a value frame is ordered by exactly one column, not %d" % (len(req[1]) - req.npartition))
-    if not isinstance(aggs, dict) or not aggs:
-        raise ValueError("ranged: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default])}")
+    _aggs_dict("ranged", aggs, "(op, measure, lo, hi[, default])")
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5):
-            raise ValueError("ranged: an aggregate is name: (op, measure, lo, hi[, default])")
+        _agg_spec("ranged", name, spec, "(op, measure, lo, hi[, default])", lambda n: n in (4, 5))
         op, col = spec[0], spec[1]
         if op not in SLIDE_OPS:
             raise ValueError("ranged: op is one of %s, not %r" % (", ".join(SLIDE_OPS), op))
         lo = None if spec[2] is None else _range_offset(spec[2], unit)
         hi = None if spec[3] is None else _range_offset(spec[3], unit)
         default = spec[4] if len(spec) == 5 else None
-        if lo is not None and hi is not None and lo > hi:
-            raise ValueError("ranged: the frame (%r, %r) ends before it starts" % (lo, hi))
-        if col is None and op != "count":
-            raise ValueError("ranged: %s needs a measure column" % op)
-        if col is not None and not isinstance(col, str):
-            raise ValueError("ranged: a measure is a column name")
-        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
-            raise ValueError("ranged: a default is a number, not %r" % (default,))
+        _agg_frame("ranged", lo, hi)
+        _agg_measure("ranged", op, col)
+        _agg_default("ranged", default)
         out.append((name, op, col, lo, hi, default))
     req = RangeRequest(req[0], req[1], req.npartition, unit, out)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
@@ -377,6 +386,7 @@ class ExcludeRequest(WindowRequest):
     name of EXCLUDE_UNITS — the column's own —, lo, hi: the frame's offsets in that unit, negative = preceding, None = unbounded,
     default: what a column gives where nothing remains, None = 0 for an int64 column and NaN for a float64 one)] in the order the
     columns are appended."""
+    method, items_attr, served_by = "excluding", "frames", "excluded"
 
     def __new__(cls, k, terms, npartition, exclude, frames):
         self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
@@ -389,10 +399,8 @@ class ExcludeRequest(WindowRequest):
             raise ValueError("excluding: a value frame is ordered by exactly one column")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
-        names = names or {}
-        return ExcludeRequest(self[0], terms, self.npartition, self.exclude, [(n, op, names.get(col, col), unit, lo, hi, d) for n, op, col, unit, lo, hi, d in self.frames])
+    def _with(self, terms, items):
+        return ExcludeRequest(self[0], terms, self.npartition, self.exclude, items)
 
 
 def exclude_request(columns, by, order, aggs, exclude="current row", unit="rows", k=WINDOW_ALL):
@@ -407,12 +415,10 @@ def exclude_request(columns, by, order, aggs, exclude="current row", unit="rows"
         raise ValueError("excluding: exclude is one of %s, not %r" % (", ".join(EXCLUDES), exclude))
     if unit not in EXCLUDE_UNITS:
         raise ValueError("excluding: unit is one of %s, not %r" % (", ".join(EXCLUDE_UNITS), unit))
-    if not isinstance(aggs, dict) or not aggs:
-        raise ValueError("excluding: aggs is a non-empty dict {new column: (op, measure, lo, hi[, default[, unit]])}")
+    _aggs_dict("excluding", aggs, "(op, measure, lo, hi[, default[, unit]])")
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) not in (4, 5, 6):
-            raise ValueError("excluding: an aggregate is name: (op, measure, lo, hi[, default[, unit]])")
+        _agg_spec("excluding", name, spec, "(op, measure, lo, hi[, default[, unit]])", lambda n: n in (4, 5, 6))
         op, col = spec[0], spec[1]
         own = spec[5] if len(spec) == 6 else unit
         if op not in EXCLUDE_OPS:
@@ -424,18 +430,13 @@ def exclude_request(columns, by, order, aggs, exclude="current row", unit="rows"
         lo = None if spec[2] is None else _range_offset(spec[2], own, "excluding")
         hi = None if spec[3] is None else _range_offset(spec[3], own, "excluding")
         default = spec[4] if len(spec) >= 5 else None
-        if lo is not None and hi is not None and lo > hi:
-            raise ValueError("excluding: the frame (%r, %r) ends before it starts" % (lo, hi))
-        if col is None and op != "count":
-            raise ValueError("excluding: %s needs a measure column" % op)
-        if col is not None and not isinstance(col, str):
-            raise ValueError("excluding: a measure is a column name")
-        if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
-            raise ValueError("excluding: a default is a number, not %r" % (default,))
+        _agg_frame("excluding", lo, hi)
+        _agg_measure("excluding", op, col)
+        _agg_default("excluding", default)
         out.append((name, op, col, own, lo, hi, default))
     req = ExcludeRequest(req[0], req[1], req.npartition, exclude, out)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
@@ -448,6 +449,7 @@ class QuantileRequest(WindowRequest):
     quants = [(name of the new column, fn: a name of QUANTILE_FNS, measure column or None, arg: NTILE's b / NTH's k or None, p: a
     percentile's or None, default: what NTH gives beyond the group, None = 0 for an int64 measure and NaN for a float64 one)] in the
     order the columns are appended.  median is percentile_cont at 0.5 by the time it is here."""
+    method, items_attr, served_by = "quantiles", "quants", "quantiled"
 
     def __new__(cls, k, terms, npartition, per_limit, quants):
         self = WindowRequest.__new__(cls, k, terms, npartition, 0, per_limit, None)
@@ -456,10 +458,8 @@ class QuantileRequest(WindowRequest):
             raise ValueError("quantiles: bad column")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: the terms term for term, the measures through `names` (old name -> new)."""
-        names = names or {}
-        return QuantileRequest(self[0], terms, self.npartition, self.per_limit, [(n, fn, names.get(col, col), arg, p, d) for n, fn, col, arg, p, d in self.quants])
+    def _with(self, terms, items):
+        return QuantileRequest(self[0], terms, self.npartition, self.per_limit, items)
 
 
 def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
@@ -472,13 +472,11 @@ def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
     if per is not None and (isinstance(per, bool) or not isinstance(per, (int, np.integer)) or int(per) < 1):
         raise ValueError("quantiles: per is None or an integer of at least 1, not %r" % (per,))
     req = window_request(None, by, order, "row_number", WINDOW_ALL if per is None else int(per), k=k)     # (its checks of by / order / k)
-    if not isinstance(cols, dict) or not cols:
-        raise ValueError("quantiles: cols is a non-empty dict {new column: (function, ...)}")
+    _aggs_dict("quantiles", cols, "(function, ...)", what="cols")
     shapes = {"ntile": (2,), "percent_rank": (1,), "cume_dist": (1,), "nth": (3, 4), "percentile_disc": (3,), "percentile_cont": (3,), "median": (2,)}
     out = []
     for name, spec in cols.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) < 1:
-            raise ValueError("quantiles: a column is name: (function, ...)")
+        _agg_spec("quantiles", name, spec, "(function, ...)", lambda n: n >= 1, what="a column")
         fn = spec[0]
         if not isinstance(fn, str) or fn not in shapes:
             raise ValueError("quantiles: the function is one of %s, median, not %r" % (", ".join(QUANTILE_FNS), fn))
@@ -498,8 +496,7 @@ def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
                 if arg == 0 or not -(1 << 63) <= arg < (1 << 63):
                     raise ValueError("quantiles: nth's k is not 0 and fits int64, not %d" % arg)
                 default = spec[3] if len(spec) == 4 else None
-                if default is not None and (isinstance(default, bool) or not isinstance(default, (int, float, np.integer, np.floating))):
-                    raise ValueError("quantiles: a default is a number, not %r" % (default,))
+                _agg_default("quantiles", default)
             else:
                 p = 0.5 if fn == "median" else spec[2]
                 if isinstance(p, bool) or not isinstance(p, (int, float, np.integer, np.floating)) or not 0.0 <= float(p) <= 1.0:      # (a NaN fails both)
@@ -509,7 +506,7 @@ def quantile_request(columns, by, order, cols, per=None, k=WINDOW_ALL):
         out.append((name, fn, col, arg, p, default))
     req = QuantileRequest(req[0], req[1], req.npartition, req.per_limit, out)
     if columns is not None:
-        check_window_columns(req, columns)
+        req.check_columns(columns)
     return req
 
 
@@ -523,6 +520,8 @@ class GroupingRequest(WindowRequest):
     holds `by`, the aggregates and an int64 column "grouping" (SQL's GROUPING(by...): bit len(by) - 1 - i set where by[i] is rolled
     up in the row; such a column holds 0 / NaN / ""); every other column of the query's result is dropped.  The sets come in the
     order listed, inside a set the rows are ordered by the set's columns as the set lists them."""
+    method = terms_method = "grouping_sets"
+    items_attr, served_by, reserved = "aggs", "grouped", ("grouping",)
 
     def __new__(cls, terms, sets, aggs):
         self = WindowRequest.__new__(cls, WINDOW_ALL, terms, len(terms), 0, WINDOW_ALL, None)
@@ -535,11 +534,9 @@ class GroupingRequest(WindowRequest):
             raise ValueError("grouping_sets: bad aggregate")
         return self
 
-    def renamed(self, terms, names=None):
-        """The same request over other column names: `by` term for term (and the sets with it), the measures through `names`."""
-        names = names or {}
-        to = {old: new for (old, _), (new, _) in zip(self[1], terms)}
-        return GroupingRequest(terms, [tuple(to[c] for c in s) for s in self.sets], [(n, op, names.get(col, col)) for n, op, col in self.aggs])
+    def _with(self, terms, items):
+        to = {old: new for (old, _), (new, _) in zip(self[1], terms)}      # (the sets follow `by`)
+        return GroupingRequest(terms, [tuple(to[c] for c in s) for s in self.sets], items)
 
     def chains(self):
         """The sets as the device serves them: [(the chain's column tuple, {level: index of the set it serves})].  A set rides in
@@ -588,35 +585,19 @@ def grouping_request(columns, sets, aggs):
         if tuple(cols) in listed:
             raise ValueError("grouping_sets: the set %r comes twice" % (tuple(cols),))
         listed.append(tuple(cols))
-    if not isinstance(aggs, dict):
-        raise ValueError("grouping_sets: aggs is a dict {new column: (op, measure)}")
+    _aggs_dict("grouping_sets", aggs, "(op, measure)", empty_ok=True)
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) != 2:
-            raise ValueError("grouping_sets: an aggregate is name: (op, measure)")
+        _agg_spec("grouping_sets", name, spec, "(op, measure)", lambda n: n == 2)
         op, col = spec
         if op not in GROUP_OPS:
             raise ValueError("grouping_sets: op is one of %s, not %r" % (", ".join(GROUP_OPS), op))
-        if col is None and op != "count":
-            raise ValueError("grouping_sets: %s needs a measure column" % op)
-        if col is not None and not isinstance(col, str):
-            raise ValueError("grouping_sets: a measure is a column name")
+        _agg_measure("grouping_sets", op, col)
         out.append((name, op, col))
     req = GroupingRequest([(nm, d or "asc") for nm, d in direction.items()], listed, out)
     if columns is not None:
-        check_grouping_columns(req, columns)
+        req.check_columns(columns)
     return req
-
-
-def check_grouping_columns(req, columns):
-    for nm, _ in req[1]:
-        if nm not in columns:
-            raise KeyError("grouping_sets: the result has no column %r" % nm)
-    for name, _, col in req.aggs:
-        if col is not None and col not in columns:
-            raise KeyError("grouping_sets: the result has no column %r" % col)
-        if name in columns or name == "grouping":
-            raise KeyError("grouping_sets: the result already has a column %r" % name)
 
 
 def rollup_sets(by):
@@ -665,6 +646,8 @@ class DistinctRequest(WindowRequest):
     their directions (npartition of them) followed by the value columns, ascending, in order of first appearance; aggs = [(name of
     the new column, op: a name of DISTINCT_OPS, value column or None for a count)].  The result holds `by` and the aggregates, one row
     per group, ordered by `by`; every other column of the query's result is dropped."""
+    method = terms_method = "distincts"
+    items_attr, served_by = "aggs", "distincted"
 
     def __new__(cls, by, aggs):
         aggs = [(str(n), str(op), None if col is None else str(col)) for n, op, col in aggs]
@@ -714,12 +697,10 @@ def distinct_request(columns, by, aggs):
         if name in [nm for nm, _ in terms]:
             raise ValueError("distincts: column %r comes twice in by" % name)
         terms.append((name, d))
-    if not isinstance(aggs, dict) or not aggs:
-        raise ValueError("distincts: aggs is a non-empty dict {new column: (op, value column)}")
+    _aggs_dict("distincts", aggs, "(op, value column)")
     out = []
     for name, spec in aggs.items():
-        if not isinstance(name, str) or not isinstance(spec, (tuple, list)) or len(spec) != 2:
-            raise ValueError("distincts: an aggregate is name: (op, value column)")
+        _agg_spec("distincts", name, spec, "(op, value column)", lambda n: n == 2)
         op, col = spec
         if op not in DISTINCT_OPS:
             raise ValueError("distincts: op is one of %s, not %r" % (", ".join(DISTINCT_OPS), op))
@@ -735,17 +716,8 @@ def distinct_request(columns, by, aggs):
         raise ValueError("distincts: a new column has the name of a grouping column")
     req = DistinctRequest(terms, out)
     if columns is not None:
-        check_distinct_columns(req, columns)
+        req.check_columns(columns)
     return req
-
-
-def check_distinct_columns(req, columns):
-    for nm, _ in req[1]:
-        if nm not in columns:
-            raise KeyError("distincts: the result has no column %r" % nm)
-    for name, _, _ in req.aggs:
-        if name in columns:
-            raise KeyError("distincts: the result already has a column %r" % name)
 
 
 def slide_empty(default, is_f64, what="sliding"):
@@ -920,7 +892,7 @@ class ResultSet:
         below +0.0, nothing but NaNs: NaN) — which is the ROWS value; RANGE / PARTITION rows take the ROWS value of the last row of
         their tie run / partition.  int64 for COUNT and integer measures, float64 otherwise."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, part_head, tie_head = self._window_heads(req.by, req.order)
         n = self._n
         starts = np.nonzero(part_head)[0]
@@ -967,7 +939,7 @@ class ResultSet:
         mod 2^64); a double SUM and MIN / MAX (on the images of sdqh_extrema.h) fold exactly the frame's rows, nothing is subtracted:
         row by row for narrow frames, else through prefix and suffix folds of blocks of the frame's width, as the device does."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, part_head, _ = self._window_heads(req.by, req.order)
         n = self._n
         pos = np.arange(n, dtype=np.int64)
@@ -1024,7 +996,7 @@ class ResultSet:
         difference of wrapping prefix sums (exact mod 2^64); a double SUM and MIN / MAX (on the images of sdqh_extrema.h) fold exactly
         the frame's rows through a binary fold tree over the sorted positions, lower positions on the left: nothing is subtracted."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, part_head, tie_head = self._window_heads(req.by, req.order)
         n = self._n
         pos = np.arange(n, dtype=np.int64)
@@ -1096,7 +1068,7 @@ class ResultSet:
         SUM and MIN / MAX fold every piece through ranged_by's fold tree and join the pieces left to right: nothing is subtracted.
         AVG is that SUM as a float64 divided by the count as a float64, one division."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, part_head, tie_head = self._window_heads(req.by, req.order)
         n = self._n
         pos = np.arange(n, dtype=np.int64)
@@ -1205,7 +1177,7 @@ class ResultSet:
         row j in a partition [s, e]: m = e - s + 1, i = j - s, [f, l] the offsets of its tie run; every function looks at the whole
         partition, per_limit and the limit cut the rows off afterwards."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, part_head, tie_head = self._window_heads(req.by, req.order)
         n = self._n
         pos = np.arange(n, dtype=np.int64)
@@ -1270,7 +1242,7 @@ class ResultSet:
         sum / min / max take the measure's dtype (int64 or float64), count is int64, avg float64.  An empty result has no groups, not
         even the grand total."""
         self._wait()
-        check_grouping_columns(req, self.columns)
+        req.check_columns(self.columns)
         n = self._n
         direction = dict(req[1])
         top = np.uint64(1) << np.uint64(63)
@@ -1340,7 +1312,7 @@ class ResultSet:
         take the column's dtype (a sum of integers wraps; mode may be text), avg_distinct is float64: the sum as a double over the
         number of runs.  Among runs of equal length the mode is the first in order.  An empty result has no groups."""
         self._wait()
-        check_distinct_columns(req, self.columns)
+        req.check_columns(self.columns)
         n = self._n
         by = [(nm, d == "desc") for nm, d in req.by]
         by_images = [order_image(self.column(nm), desc) for nm, desc in by]
@@ -1413,23 +1385,13 @@ class ResultSet:
         return self.framed(frame_request(self.columns, by, order, aggs, frame))
 
     def windowed(self, req):
-        """The rows a WindowRequest keeps, in its order, with its rank column when it names one (a FrameRequest: framed)."""
-        if isinstance(req, GroupingRequest):
-            return self.grouped(req)
-        if isinstance(req, DistinctRequest):
-            return self.distincted(req)
-        if isinstance(req, FrameRequest):
-            return self.framed(req)
-        if isinstance(req, SlideRequest):
-            return self.slid(req)
-        if isinstance(req, RangeRequest):
-            return self.ranged_by(req)
-        if isinstance(req, ExcludeRequest):
-            return self.excluded(req)
-        if isinstance(req, QuantileRequest):
-            return self.quantiled(req)
+        """A WindowRequest of any kind served on the host, by the method its class names (WindowRequest.served_by)."""
+        return req.host(self)
+
+    def ranked(self, req):
+        """The rows a plain WindowRequest keeps, in its order, with its rank column when it names one."""
         self._wait()
-        check_window_columns(req, self.columns)
+        req.check_columns(self.columns)
         idx, rank = self.window_index(req.by, req.order, req.kind, req.per_limit, req[0])
         cols = [a[idx] for a in self._cols]                              # undecoded text stays undecoded
         return ResultSet(self.columns + ([req.name] if req.name is not None else []), cols + ([rank] if req.name is not None else []))

@@ -389,13 +389,13 @@ def sdql_compile(in_type):
             from . import abi
             return top(abi.SORT_ALL, order)
 
-        def _windowed(by, order, kind, per_limit, name):
-            from . import engine, frontend
-            from .result import window_request
+        def _requested(builder, *what, **how):
+            """The runner of the query finished with the request result.`builder` makes of `what` — checked here, before anything
+            is launched: the names against the columns the plan's last loop gives its result."""
+            from . import engine, frontend, result
             if "plan" not in cache:
                 cache["plan"] = frontend.lower_function(func, in_type)
-            # checked here, before anything is launched: the names against the columns the plan's last loop gives its result
-            req = window_request(engine.result_columns(cache["plan"]), by, order, kind, per_limit, name=name)
+            req = getattr(result, builder)(engine.result_columns(cache["plan"]), *what, **how)
             return lambda *args: run(args, req)
 
         def top_per(k, by, order, ties=False):
@@ -403,13 +403,13 @@ def sdql_compile(in_type):
             (column, "asc" | "desc") to say in which order the groups come) in the order of `order`, e.g.
             ``q3.top_per(3, ["o_orderdate"], [("revenue", "desc")])(li, cu, ord)``.  ties=True keeps every row tied with the k-th
             (RANK() <= k instead of ROW_NUMBER() <= k); by=[] is one group: "top k with ties"."""
-            return _windowed(list(by), list(order), "rank" if ties else "row_number", k, None)
+            return _requested("window_request", list(by), list(order), "rank" if ties else "row_number", k)
 
         def numbered(by, order, kind="row_number", name="rank"):
             """The same query finished with ORDER BY `by`, `order` and an int64 column `name`: every row's row_number / rank /
             dense_rank (kind) inside its group of `by`."""
             from . import abi
-            return _windowed(list(by), list(order), kind, abi.SORT_ALL, name)
+            return _requested("window_request", list(by), list(order), kind, abi.SORT_ALL, name=name)
 
         def over(by, order, aggs, frame="range"):
             """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a window frame inside the row's
@@ -417,12 +417,7 @@ def sdql_compile(in_type):
             in "rows" (group start .. this row) / "range" (.. the last row tied with this one: SQL's default) / "partition" (the
             whole group), e.g. ``q3.over(["o_orderdate"], [("revenue", "desc")], {"running": ("sum", "revenue"), "n": ("count",
             None, "partition")})(li, cu, ord)``.  int64 for counts and integer measures, float64 otherwise."""
-            from . import engine, frontend
-            from .result import frame_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = frame_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, frame)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("frame_request", list(by), list(order), aggs, frame)
 
         def sliding(by, order, aggs):
             """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a SLIDING frame inside the row's
@@ -433,12 +428,7 @@ def sdql_compile(in_type):
             `default` (0 for an int64 measure, NaN for a float64 one), a count 0.  Names, ops, bounds and k are checked here, before
             anything is launched; whether a default fits its column (a float for an int64 measure does not) can only be told once the
             query has run and the column's dtype is known: that ValueError comes from the call."""
-            from . import engine, frontend
-            from .result import slide_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = slide_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("slide_request", list(by), list(order), aggs)
 
         def ranged(by, order, aggs, unit="value"):
             """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a VALUE or GROUP frame inside the
@@ -450,12 +440,7 @@ def sdql_compile(in_type):
             frame gives `default` (0 for an int64 measure, NaN for a float64 one), a count 0.  Names, ops, the unit and bounds are
             checked here, before anything is launched; what depends on a column's dtype (a default that does not fit, an order column
             without arithmetic) can only be told once the query has run: that ValueError comes from the call."""
-            from . import engine, frontend
-            from .result import range_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = range_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, unit)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("range_request", list(by), list(order), aggs, unit)
 
         def excluding(by, order, aggs, exclude="current row", unit="rows"):
             """The same query finished with ORDER BY `by`, `order` and one column per aggregate over a frame inside the row's group of
@@ -468,12 +453,7 @@ def sdql_compile(in_type):
             gives `default` (0 for an int64 column, NaN for a float64 one), a count 0; an avg is float64.  Names, ops, units and
             bounds are checked here, before anything is launched; what depends on a column's dtype can only be told once the query
             has run: that ValueError comes from the call."""
-            from . import engine, frontend
-            from .result import exclude_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = exclude_request(engine.result_columns(cache["plan"]), list(by), list(order), aggs, exclude, unit)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("exclude_request", list(by), list(order), aggs, exclude, unit)
 
         def quantiles(by, order, cols, per=None):
             """The same query finished with ORDER BY `by`, `order` and one column per function of the size of the row's group of `by`:
@@ -486,12 +466,7 @@ def sdql_compile(in_type):
             `default` (0 for an int64 measure, NaN for a float64 one).  Names, functions, b, k and p are checked here, before anything
             is launched; whether a default fits its column can only be told once the query has run: that ValueError comes from the
             call."""
-            from . import engine, frontend
-            from .result import quantile_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = quantile_request(engine.result_columns(cache["plan"]), list(by), list(order), cols, per)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("quantile_request", list(by), list(order), cols, per)
 
         def grouping_sets(sets, aggs):
             """The same query finished with GROUP BY GROUPING SETS over its result: one row per group of every set in `sets` — column
@@ -502,12 +477,7 @@ def sdql_compile(in_type):
             the row, and such a column holds 0 / NaN / "" — and none of the query's other columns; the sets come in the order
             listed, inside a set the rows are ordered by the set's columns.  sum / min / max take the measure's dtype, count is
             int64, avg float64.  Names and ops are checked here, before anything is launched."""
-            from . import engine, frontend
-            from .result import grouping_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = grouping_request(engine.result_columns(cache["plan"]), list(sets), aggs)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("grouping_request", list(sets), aggs)
 
         def rollup(by, aggs):
             """The same query finished with GROUP BY ROLLUP(by): the grouping sets by[:d], by[:d - 1], ..., () — subtotals for every
@@ -531,12 +501,7 @@ def sdql_compile(in_type):
             group, ordered by `by`.  count_distinct, mode_count and count are int64, sum_distinct and mode take the value column's
             dtype (mode may be text; among equally frequent values the first in ascending order), avg_distinct is float64.  Names
             and ops are checked here, before anything is launched."""
-            from . import engine, frontend
-            from .result import distinct_request
-            if "plan" not in cache:
-                cache["plan"] = frontend.lower_function(func, in_type)
-            req = distinct_request(engine.result_columns(cache["plan"]), list(by) if isinstance(by, (list, tuple)) else by, aggs)     # checked before anything is launched
-            return lambda *args: run(args, req)
+            return _requested("distinct_request", list(by) if isinstance(by, (list, tuple)) else by, aggs)
 
         wrapper.top = top
         wrapper.order_by = order_by
