@@ -70,6 +70,11 @@ GS_MAX_AGGS = 4
 GROUP_DISTINCT_EXPORTS = ["sdqh_table_group_distinct", "sdqh_group_distinct_geometry"]
 GD_COUNT_DISTINCT, GD_SUM_DISTINCT, GD_AVG_DISTINCT, GD_MODE, GD_MODE_COUNT, GD_COUNT = 0, 1, 2, 3, 4, 5
 GD_MAX_AGGS = 4
+# ... and its eleventh (include/sdqh_sort_moments.h, Library.has_group_moments): the second moments per group — VAR / STDDEV / COVAR /
+# CORR / REGR_SLOPE / REGR_INTERCEPT at the levels of the grouping sets, two passes over the rows
+GROUP_MOMENTS_EXPORTS = ["sdqh_table_group_moments", "sdqh_group_moments_geometry"]
+GM_VAR_POP, GM_VAR_SAMP, GM_STDDEV_POP, GM_STDDEV_SAMP, GM_COVAR_POP, GM_COVAR_SAMP, GM_CORR, GM_REGR_SLOPE, GM_REGR_INTERCEPT = range(9)
+GM_MAX_AGGS = 4
 # all of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
@@ -80,6 +85,7 @@ WINDOW_EXTENSIONS = {
     "has_window_exclude": (WINDOW_EXCLUDE_EXPORTS, "sdqh_sort_exclude.h", "window exclude", "has_window_range"),
     "has_grouping_sets": (GROUPING_SETS_EXPORTS, "sdqh_sort_groups.h", "grouping sets", "has_window_agg"),
     "has_group_distinct": (GROUP_DISTINCT_EXPORTS, "sdqh_sort_distinct.h", "group distinct", "has_grouping_sets"),
+    "has_group_moments": (GROUP_MOMENTS_EXPORTS, "sdqh_sort_moments.h", "group moments", "has_grouping_sets"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -188,6 +194,22 @@ class WindowExclude(C.Structure):
 class GroupAgg(C.Structure):
     """sdqh_group_agg: an op (WAGG_SUM / WAGG_COUNT / WAGG_MIN / WAGG_MAX / WEX_AVG) and its measure, named as a SortKey names a column."""
     _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32)]
+
+
+class MomentAgg(C.Structure):
+    """sdqh_moment_agg: an op (GM_*) and its two measures, each named as a SortKey names a column: Y first, then X (VAR / STDDEV read Y alone)."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32),
+                ("kind2", C.c_int32), ("index2", C.c_int32), ("is_f64_2", C.c_int32), ("_pad", C.c_int32)]
+
+
+def _marshal_moment_aggs(aggs):
+    """[(op, kind, index, is_f64) | (op, kind, index, is_f64, kind2, index2, is_f64_2)] -> a MomentAgg array (one spare element for an empty list)."""
+    arr = (MomentAgg * max(1, len(aggs)))()
+    for i, a in enumerate(aggs):
+        arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(a[0]), int(a[1]), int(a[2]), 1 if a[3] else 0
+        if len(a) > 4:
+            arr[i].kind2, arr[i].index2, arr[i].is_f64_2 = int(a[4]), int(a[5]), 1 if a[6] else 0
+    return arr
 
 
 class WindowQuantile(C.Structure):
@@ -1525,6 +1547,32 @@ class Context:
         """Sorted positions (and, at the upper stage, value runs) per tile of sdqh_table_group_distinct's passes: what the tests size their cases from."""
         return self._window_geometry("has_group_distinct", 1)
 
+    def table_group_moments(self, table, min_hits, terms, levels, aggs, limit, capacity, want_hits=True):
+        """The second moments of the groups table_grouping_sets returns — terms, levels, rows and level_rows are its —: aggs: [(op, kind,
+        index, is_f64)] or [(op, kind, index, is_f64, kind2, index2, is_f64_2)], op one of GM_*, the first measure Y, the second X
+        (GM_VAR_* / GM_STDDEV_* read Y alone), 1 .. GM_MAX_AGGS of them.  Returns (keys, payload, values, hits, aggs, level_rows) — aggs
+        one float64 array per aggregate (a NaN where SQL has NULL)."""
+        self._need("has_group_moments", "table_group_moments")
+        level_rows = np.zeros(SORT_MAX_KEYS + 1, np.int64)
+        lead = (C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_uint32(levels), C.c_int(len(aggs)), _marshal_moment_aggs(aggs), C.c_int64(limit))
+        got = self._sorted_call("table_group_moments", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(aggs)), trail=(_np_ptr(level_rows),))
+        return got[:4] + ([got[4][i].view(np.float64) for i in range(len(aggs))], level_rows)
+
+    def table_group_moments_count(self, table, min_hits, terms, levels, aggs, limit=SORT_ALL):
+        """The count-only call of table_group_moments: (min(limit, groups), level_rows) — the sort and the level pass run, no row is fetched."""
+        self._need("has_group_moments", "table_group_moments")
+        level_rows = np.zeros(SORT_MAX_KEYS + 1, np.int64)
+        n = C.c_int64()
+        self._check(self.lib.sdqh_table_group_moments(self.handle, table.handle, C.c_int64(min_hits), C.c_int(len(terms)), _marshal_sort_terms(terms), C.c_uint32(levels),
+                                                      C.c_int(len(aggs)), _marshal_moment_aggs(aggs), C.c_int64(limit), C.c_int64(0), None, None, None, None, None,
+                                                      _np_ptr(level_rows), C.byref(n)))
+        self._after_call("table_group_moments")
+        return n.value, level_rows
+
+    def group_moments_geometry(self):
+        """Sorted positions per tile of sdqh_table_group_moments' passes: what the tests size their cases from."""
+        return self._window_geometry("has_group_moments", 1)
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1809,6 +1857,10 @@ class Library:
             L.sdqh_table_group_distinct.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_group_distinct_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        if self.has_group_moments:
+            L.sdqh_table_group_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_group_moments_geometry.argtypes = [C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -129,6 +129,16 @@
 //                     the rows to value runs: a run's sorted position, depth and length, per aggregate the element the groups fold
 //   k_gs_tiles / k_wagg_scan / k_sort_bins / k_gs_run
 //                     the runs folded into groups, as a lower level of GROUPS; k_gd_finish unpacks MODE and divides an AVG — see the section
+//   MOMENTS           in their place (STEP_MOMENTS).  sdqh_table_group_moments (include/sdqh_sort_moments.h) returns the rows of GROUPS with
+//                     VAR / STDDEV / COVAR / CORR / REGR_SLOPE / REGR_INTERCEPT per group, two passes over the rows per level:
+//
+//   k_gs_depth / k_sort_bins
+//                     as for GROUPS: the heads of every level, the level counts to the host
+//   k_gd_heads / k_mo_stage
+//                     per level: its groups' sorted positions, then per row every distinct measure as a double minus its representative's
+//   k_gs_tiles / k_wagg_scan / k_gs_run
+//                     pass 1, over the rows at that level: the groups' sums; k_mo_center hands every row its group's mean and writes the
+//                     centred squares and products; the same three again, pass 2; k_mo_finish applies the ops — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -147,6 +157,7 @@
 #include "sdqh_sort_exclude.h"
 #include "sdqh_sort_groups.h"
 #include "sdqh_sort_distinct.h"
+#include "sdqh_sort_moments.h"
 
 using namespace sdqh_host;
 
@@ -1671,6 +1682,143 @@ __global__ __launch_bounds__(TPB) void k_gd_finish(DevStage st, DevGdAggs gd, co
     }
 }
 
+// ---- second moments per group (sdqh_table_group_moments) ---------------------------------------------------------------------------
+// VAR / STDDEV / COVAR / CORR / REGR per group at the levels of GROUPS, by the two-pass algorithm (include/sdqh_sort_moments.h).  A
+// variance is no fold of one 64-bit element per row: sum x^2 - (sum x)^2 / m cancels, merged (n, mean, M2) states are a multi-word
+// operator and less accurate.  Two folds of doubles are: per level L asked for, over the ROWS (a coarser level's mean is another
+// mean, so nothing folds from the level above),
+//   k_gd_heads        the level's groups: slot = the head's rank among the level-L heads, its sorted position — the representative
+//   k_mo_stage        per position the call's distinct measures (at most two per aggregate; aggregates naming the same measure share
+//                     a column) read through perm -> refs -> stage once, converted to double, minus the representative's: s = x - x_r
+//   k_gs_tiles / k_wagg_scan / k_gs_run
+//                     pass 1: the s folded per group as WAGG_ADD_F elements, at most SDQH_WAGG_MAX_AGGS columns a launch
+//   k_mo_center       per position its group's slot again, mu = S / m (m off the positions), d = s - mu per measure, and the
+//                     elements of pass 2: d * d per measure an aggregate needs a Q of, dx * dy per pair
+//   k_gs_tiles / k_wagg_scan / k_gs_run
+//                     pass 2: those folded per group, the same way
+// and at the end k_mo_finish, a thread per returned group, applies the op's formula.  A wave's lanes mostly share a slot, so the
+// loads of the representative and of the group's sums broadcast.  No atomics; the level's tile offsets are k_sort_bins' (tcount).
+constexpr int MO_MAX_MEAS = 2 * SDQH_GM_MAX_AGGS, MO_MAX_CEN = 3 * SDQH_GM_MAX_AGGS;
+struct DevMoAggs {
+    DevSortKey sk[MO_MAX_MEAS];                                       // the distinct measures (desc unused)
+    int32_t ci[MO_MAX_CEN], cj[MO_MAX_CEN];                           // pass 2's column c: d of measure ci[c] times d of measure cj[c]
+    int32_t op[SDQH_GM_MAX_AGGS], my[SDQH_GM_MAX_AGGS], mx[SDQH_GM_MAX_AGGS];                  // per aggregate: the op, its measures
+    int32_t qy[SDQH_GM_MAX_AGGS], qx[SDQH_GM_MAX_AGGS], cc[SDQH_GM_MAX_AGGS];                  // ... and its columns of pass 2 (-1: not read)
+    int32_t nmeas, ncen, n, _pad;
+};
+
+__device__ __forceinline__ double mo_f64(uint64_t bits) { return __longlong_as_double((long long)bits); }
+__device__ __forceinline__ uint64_t mo_bits(double d) { return (uint64_t)__double_as_longlong(d); }
+// measure sk of staged row idx as a double: an integer by one conversion
+__device__ __forceinline__ double mo_value(const DevSortKey& sk, const DevStage& st, int64_t idx, uint32_t hits) {
+    const int64_t raw = sort_raw(sk, st, idx, hits);
+    return sk.is_f64 ? __longlong_as_double(raw) : (double)raw;
+}
+
+// 1. a wave per tile of sorted positions: elem[k * stride + r] = measure k at position r minus measure k at the representative of
+// r's level-L group.  toff: the level-L heads before the tile, lpos: the sorted position of every level-L group (ng of them).
+__global__ __launch_bounds__(TPB) void k_mo_stage(DevStage st, DevMoAggs mo, int L, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ depth,
+                                                 const uint32_t* __restrict__ toff, const uint32_t* __restrict__ lpos, uint32_t ng, uint32_t n, size_t stride,
+                                                 uint64_t* __restrict__ elem, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint64_t le = lanemask_lt() | (1ull << (uint32_t)lane_id());
+    uint32_t at0 = toff[w];
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t j = b + (uint32_t)lane_id();
+        const bool live = j < r1;
+        const GsBatch h = gs_batch(depth, L, j, r1, n, le);
+        const uint32_t slot = at0 + (uint32_t)__popcll(h.hl) - 1u;       // (position 0 is a head: at least one lies at or below every item)
+        const uint32_t rp = (live && slot < ng) ? lpos[slot] : n;
+        const uint32_t g = live ? (perm ? perm[j] : (uint32_t)j) : n;
+        const uint32_t gr = rp < n ? (perm ? perm[rp] : rp) : n;
+        const bool ok = g < n && gr < n;                                 // (positions and a permutation of [0, n): every live lane)
+        const int64_t idx = ok ? (int64_t)refs[g] : 0, idr = ok ? (int64_t)refs[gr] : 0;
+        const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u, hitr = ok && st.shits ? st.shits[idr] : 0u;
+#pragma unroll
+        for (int k = 0; k < MO_MAX_MEAS; ++k) if (k < mo.nmeas) {
+            const double s = ok ? mo_value(mo.sk[k], st, idx, hits) - mo_value(mo.sk[k], st, idr, hitr) : 0.0;
+            if (live) elem[(size_t)k * stride + j] = mo_bits(s);
+        }
+        at0 += (uint32_t)__popcll(h.mh);
+    }
+}
+// 2. the tile again: position r's group is slot toff + heads up to r - 1, its size the distance to the next group's position (or to
+// n), its shifted means sums / size; cen[c * stride + r] = d_ci * d_cj with d_k = elem[k] - mean_k.  sums: pass 1's, gstride apart.
+__global__ __launch_bounds__(TPB) void k_mo_center(DevMoAggs mo, int L, const uint8_t* __restrict__ depth, const uint32_t* __restrict__ toff, const uint32_t* __restrict__ lpos,
+                                                  uint32_t ng, uint32_t n, size_t stride, const uint64_t* __restrict__ elem, size_t gstride, const uint64_t* __restrict__ sums,
+                                                  uint64_t* __restrict__ cen, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint64_t le = lanemask_lt() | (1ull << (uint32_t)lane_id());
+    uint32_t at0 = toff[w];
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t j = b + (uint32_t)lane_id();
+        const GsBatch h = gs_batch(depth, L, j, r1, n, le);
+        const uint32_t slot = at0 + (uint32_t)__popcll(h.hl) - 1u;
+        if (j < r1 && slot < ng) {
+            const uint32_t next = slot + 1u < ng ? lpos[slot + 1u] : n;
+            const double size = (double)(next - lpos[slot]);
+#pragma unroll
+            for (int c = 0; c < MO_MAX_CEN; ++c) if (c < mo.ncen) {
+                const int ki = mo.ci[c], kj = mo.cj[c];
+                const double di = mo_f64(elem[(size_t)ki * stride + j]) - mo_f64(sums[(size_t)ki * gstride + slot]) / size;
+                const double dj = mo_f64(elem[(size_t)kj * stride + j]) - mo_f64(sums[(size_t)kj * gstride + slot]) / size;
+                cen[(size_t)c * stride + j] = mo_bits(di * dj);
+            }
+        }
+        at0 += (uint32_t)__popcll(h.mh);
+    }
+}
+// 3. a thread per returned group: the op's formula, in the header's order of operations, on pass 2's sums (cen), pass 1's (sums),
+// the representative's measures and the group's size — the distance to the next representative of its level, or to n
+__global__ __launch_bounds__(TPB) void k_mo_finish(DevStage st, DevMoAggs mo, DevGsLevels lv, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ pos,
+                                                  uint32_t n, uint32_t m, size_t gstride, const uint64_t* __restrict__ sums, const uint64_t* __restrict__ cen, uint64_t* __restrict__ val) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        int k = 0;
+        while (k + 1 < lv.n && j >= lv.off[k + 1]) ++k;
+        const uint32_t p = pos[j];
+        const uint32_t next = j + 1 < lv.off[k + 1] ? pos[j + 1] : n;
+        const uint32_t rows = next - p;
+        const double size = (double)rows;
+        const uint32_t g = p < n ? (perm ? perm[p] : p) : n;
+        if (g >= n) continue;                                            // (a position and a permutation of [0, n): never taken)
+        const int64_t idx = (int64_t)refs[g];
+        const uint32_t hits = st.shits ? st.shits[idx] : 0u;
+#pragma unroll
+        for (int a = 0; a < SDQH_GM_MAX_AGGS; ++a) if (a < mo.n) {
+            const int op = mo.op[a];
+            const double qy = mo.qy[a] >= 0 ? mo_f64(cen[(size_t)mo.qy[a] * gstride + j]) : 0.0;
+            const double qx = mo.qx[a] >= 0 ? mo_f64(cen[(size_t)mo.qx[a] * gstride + j]) : 0.0;
+            const double c = mo.cc[a] >= 0 ? mo_f64(cen[(size_t)mo.cc[a] * gstride + j]) : 0.0;
+            uint64_t out = WAGG_QNAN;
+            if (op == SDQH_GM_VAR_POP) out = mo_bits(qy / size);
+            else if (op == SDQH_GM_STDDEV_POP) out = mo_bits(sqrt(qy / size));
+            else if (op == SDQH_GM_COVAR_POP) out = mo_bits(c / size);
+            else if (op == SDQH_GM_VAR_SAMP) { if (rows > 1u) out = mo_bits(qy / (size - 1.0)); }
+            else if (op == SDQH_GM_STDDEV_SAMP) { if (rows > 1u) out = mo_bits(sqrt(qy / (size - 1.0))); }
+            else if (op == SDQH_GM_COVAR_SAMP) { if (rows > 1u) out = mo_bits(c / (size - 1.0)); }
+            else if (op == SDQH_GM_CORR) {
+                if (qx != 0.0 && qy != 0.0) {
+                    double t = c / (sqrt(qx) * sqrt(qy));
+                    if (t > 1.0) t = 1.0;
+                    if (t < -1.0) t = -1.0;
+                    out = mo_bits(t);
+                }
+            } else if (qx != 0.0) {                                      // REGR_SLOPE, REGR_INTERCEPT
+                const double slope = c / qx;
+                if (op == SDQH_GM_REGR_SLOPE) out = mo_bits(slope);
+                else {
+                    const double muy = mo_value(mo.sk[mo.my[a]], st, idx, hits) + mo_f64(sums[(size_t)mo.my[a] * gstride + j]) / size;
+                    const double mux = mo_value(mo.sk[mo.mx[a]], st, idx, hits) + mo_f64(sums[(size_t)mo.mx[a] * gstride + j]) / size;
+                    out = mo_bits(muy - slope * mux);
+                }
+            }
+            val[(size_t)a * gstride + j] = out;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -1873,7 +2021,9 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // aggregates are `aggs` (an AVG as the SUM it divides: avg), and like a filter it knows its count only behind the sort.
 // STEP_DISTINCTS (sdqh_table_group_distinct) returns one row per group of the first `ngroup` terms; `aggs` are the folds of the upper
 // stage, `gd` the ops and measures as the caller named them.
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS };
+// STEP_MOMENTS (sdqh_table_group_moments) returns the rows of STEP_GROUPS — `levels`, level_rows —; `mo` holds its aggregates, the
+// distinct measures they read and the columns its second pass folds.
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
@@ -1881,6 +2031,7 @@ struct SortStep {
     union { DevWaggs aggs; DevWslides sl; DevWranges rg; DevWquants q; DevWexs ex; };
     uint32_t levels; int64_t* level_rows; DevGsAvg avg;
     int ngroup; DevGdAggs gd;
+    DevMoAggs mo;
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -2327,6 +2478,86 @@ static int step_distincts(StepRun& r) {
     return SDQH_OK;
 }
 
+// Second moments per group (sdqh_table_group_moments).  Block 3 = step_groups' [depths | head flags of the highest level | heads per
+// tile and level | level counts]; the level counts go to the host and the ways out are taken as there.  Block 4 = [groups: positions |
+// depths | pass 1's sums | pass 2's sums | results] [rows: staged measures | centred products] [value carries | first heads | heads
+// per tile].  Every level asked for is folded over the rows, its tile offsets k_sort_bins' (tcount).
+static int step_moments(StepRun& r) {
+    sdqh_ctx* ctx = r.ctx;
+    const int nl = r.nsort + 1;
+    const uint32_t levels = r.step.levels;
+    int top = r.nsort;
+    while (!((levels >> top) & 1u)) --top;                            // (levels != 0 and no bit above nsort: the entry point's check)
+    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
+    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
+            depth = c.take<uint8_t>((size_t)r.n);
+            heads = c.take<uint8_t>((size_t)r.n);
+            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
+            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
+        })) return r.nomem();
+    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);      // per level: the tiles' offsets in place, the level's count
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
+    std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
+    DevGsLevels lv; std::memset(&lv, 0, sizeof(lv));
+    int lvl[SDQH_SORT_MAX_KEYS + 1];
+    int64_t g = 0;
+    for (int L = top; L >= 0; --L) if ((levels >> L) & 1u) { lvl[lv.n] = L; g += (int64_t)tot[L]; lv.off[++lv.n] = (uint32_t)g; }
+    if (g > 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 groups over the levels asked for");
+    if (r.step.level_rows) for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) r.step.level_rows[L] = (L < nl && ((levels >> L) & 1u)) ? (int64_t)tot[L] : 0;
+    r.m = std::min<int64_t>(r.limit, g);
+    if (r.count_only) return r.done(r.m);
+    if (r.m > r.capacity) return r.overflow(r.m);
+    DevMoAggs mo = r.step.mo;
+    if (!r.step.out) mo.n = mo.nmeas = mo.ncen = 0;                   // rows only: nothing is folded
+    const size_t na = (size_t)mo.n, nm = (size_t)mo.nmeas, nc = (size_t)mo.ncen, gstride = round_up((size_t)g * 8) / 8;
+    uint32_t *sel = nullptr, *tcnt = nullptr; uint8_t* gdepth = nullptr;
+    uint64_t *sums = nullptr, *cens = nullptr, *fin = nullptr, *elem = nullptr, *cen = nullptr, *tval = nullptr; WaggHeads* tfirst = nullptr;
+    if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
+            sel = c.take<uint32_t>((size_t)g);
+            gdepth = c.take<uint8_t>((size_t)g);
+            sums = c.take<uint64_t>(gstride * nm);
+            cens = c.take<uint64_t>(gstride * nc);
+            fin = c.take<uint64_t>(gstride * na);
+            elem = c.take<uint64_t>(r.stride * nm);
+            cen = c.take<uint64_t>(r.stride * nc);
+            tval = c.take<uint64_t>((size_t)ntiles * SDQH_WAGG_MAX_AGGS);
+            tfirst = c.take<WaggHeads>(ntiles);
+            tcnt = c.take<uint32_t>(ntiles);
+        })) return r.nomem();
+    for (int k = 0; k < lv.n; ++k) {
+        const int L = lvl[k];
+        const uint32_t from = lv.off[k], ng = tot[L];
+        const uint32_t* toff = tcount + (size_t)L * ntiles;
+        LAUNCH(ctx, "k_gd_heads", k_gd_heads, tgrid, L, depth, r.un, toff, ntiles, sel + from, gdepth + from, ng);
+        if (!na) continue;
+        // `cols` columns of doubles at `src`, one per row, summed per level-L group into `dst`: the frames' folds, four columns a launch
+        auto fold = [&](const uint64_t* src, size_t cols, uint64_t* dst) {
+            for (size_t c0 = 0; c0 < cols; c0 += SDQH_WAGG_MAX_AGGS) {
+                DevWaggs ag; std::memset(&ag, 0, sizeof(ag));
+                ag.n = (int32_t)std::min<size_t>(SDQH_WAGG_MAX_AGGS, cols - c0);
+                for (int a = 0; a < ag.n; ++a) { ag.a[a].op = SDQH_WAGG_SUM; ag.a[a].frame = SDQH_FRAME_ROWS; ag.a[a].cls = WAGG_ADD_F; ag.a[a].sk.is_f64 = 1; }
+                LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, tgrid, ag, L, depth, src + c0 * r.stride, r.stride, r.un, tval, tfirst, tcnt, ntiles);
+                LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)ag.n, ag, tfirst, r.un, tval, ntiles);
+                LAUNCH(ctx, "k_gs_run", k_gs_run, tgrid, ag, L, 1, depth, (const uint32_t*)nullptr, src + c0 * r.stride, r.stride, r.un, tval, toff, ntiles,
+                       dst + c0 * gstride, gstride, gdepth + from, sel + from, ng);
+            }
+        };
+        LAUNCH(ctx, "k_mo_stage", k_mo_stage, tgrid, r.table->stage, mo, L, r.s.refs, r.s.perm, depth, toff, sel + from, ng, r.un, r.stride, elem, ntiles);
+        fold(elem, nm, sums + from);
+        LAUNCH(ctx, "k_mo_center", k_mo_center, tgrid, mo, L, depth, toff, sel + from, ng, r.un, r.stride, elem, gstride, sums + from, cen, ntiles);
+        fold(cen, nc, cens + from);
+    }
+    if (na) LAUNCH(ctx, "k_mo_finish", k_mo_finish, r.row_grid(), r.table->stage, mo, lv, r.s.refs, r.s.perm, sel, r.un, (uint32_t)r.m, gstride, sums, cens, fin);
+    r.sel = sel;
+    for (r.ncols = 0; r.ncols < mo.n; ++r.ncols) r.col_src[r.ncols] = fin + (size_t)r.ncols * gstride;
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -2341,7 +2572,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
     StepRun r{ctx, table, me, step, s, scratch, nsort, n, limit, capacity, count_only, all_kept, out_n, (uint32_t)n, round_up((size_t)n * 8) / 8, std::min<int64_t>(limit, n)};
     // The ways out before anything is ordered.  With every row kept m = min(limit, n) already; a filtering call knows its count
     // only after the ranks, so of these it takes the first alone (and leaves *out_n untouched if a later step fails).
-    if (n == 0 && step.kind == STEP_GROUPS && step.level_rows) std::memset(step.level_rows, 0, sizeof(int64_t) * (SDQH_SORT_MAX_KEYS + 1));
+    if (n == 0 && (step.kind == STEP_GROUPS || step.kind == STEP_MOMENTS) && step.level_rows) std::memset(step.level_rows, 0, sizeof(int64_t) * (SDQH_SORT_MAX_KEYS + 1));
     if (n == 0) return r.done(0);                                     // nothing selected (limit >= 1: m = 0 means n = 0)
     if (all_kept && count_only) return r.done(r.m);                   // count-only call
     if (all_kept && r.m > capacity) return r.overflow(r.m);           // the needed count, nothing written
@@ -2360,6 +2591,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_EXCLUDES: if (step.out) step_rc = step_excludes(r); break;
         case STEP_GROUPS: step_rc = step_groups(r); break;            // (the rows themselves are the step's: always)
         case STEP_DISTINCTS: step_rc = step_distincts(r); break;      // (likewise)
+        case STEP_MOMENTS: step_rc = step_moments(r); break;          // (likewise)
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -2700,6 +2932,51 @@ int sdqh_table_group_distinct(sdqh_ctx* ctx, const sdqh_table* table, int64_t mi
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_group_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int nterms, const sdqh_sort_term* in, uint32_t levels,
+                             int naggs, const sdqh_moment_agg* aggs, int64_t limit, int64_t capacity,
+                             int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_level_rows, int64_t* out_n) {
+    const char* who = "table_group_moments";
+    bool ok = naggs >= 1 && naggs <= SDQH_GM_MAX_AGGS && aggs && levels != 0u && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && !(levels >> (nterms + 1));
+    for (int a = 0; ok && a < naggs; ++a) ok = aggs[a].op >= SDQH_GM_VAR_POP && aggs[a].op <= SDQH_GM_REGR_INTERCEPT;
+    SortStep st = sort_step(STEP_MOMENTS, 0, out_aggs);
+    st.filters = true; st.per_limit = 0;                              // no row is kept for its rank: the count is the groups', known behind the level pass
+    st.levels = levels; st.level_rows = out_level_rows;
+    DevMoAggs& mo = st.mo;
+    mo.n = ok ? naggs : 0;
+    // a measure's column among the distinct ones (aggregates naming the same measure share it), and a product's among pass 2's
+    auto measure = [&](const DevSortKey& sk) {
+        for (int k = 0; k < mo.nmeas; ++k) if (mo.sk[k].kind == sk.kind && mo.sk[k].index == sk.index && mo.sk[k].is_f64 == sk.is_f64) return k;
+        mo.sk[mo.nmeas] = sk;
+        return mo.nmeas++;
+    };
+    auto product = [&](int i, int j) {
+        if (i > j) std::swap(i, j);
+        for (int c = 0; c < mo.ncen; ++c) if (mo.ci[c] == i && mo.cj[c] == j) return c;
+        mo.ci[mo.ncen] = i; mo.cj[mo.ncen] = j;
+        return mo.ncen++;
+    };
+    // the measures in front of window_enter, as sdqh_table_grouping_sets checks them: every argument error comes before SDQH_ERR_UNSUPPORTED
+    for (int a = 0; ctx && table && ok && a < naggs; ++a) {
+        const sdqh_moment_agg& g = aggs[a];
+        const bool two = g.op >= SDQH_GM_COVAR_POP;                   // (VAR_* and STDDEV_* ignore the second measure)
+        DevSortKey y, x; std::memset(&y, 0, sizeof(y)); std::memset(&x, 0, sizeof(x));
+        if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind, g.index, g.is_f64, y)) return rc;
+        if (two) if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind2, g.index2, g.is_f64_2, x)) return rc;
+        mo.op[a] = g.op;
+        mo.my[a] = measure(y); mo.mx[a] = two ? measure(x) : mo.my[a];
+        mo.qy[a] = mo.qx[a] = mo.cc[a] = -1;
+        if (!two) mo.qy[a] = product(mo.my[a], mo.my[a]);
+        else {
+            mo.cc[a] = product(mo.my[a], mo.mx[a]);
+            if (g.op >= SDQH_GM_CORR) mo.qx[a] = product(mo.mx[a], mo.mx[a]);
+            if (g.op == SDQH_GM_CORR) mo.qy[a] = product(mo.my[a], mo.my[a]);
+        }
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, 0, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
 // what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
 // a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
 static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, bool has_narrow, int64_t* narrow_max_width) {
@@ -2708,6 +2985,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_group_moments_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_moments_geometry", tile_rows, false, nullptr); }
 int sdqh_group_distinct_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_distinct_geometry", tile_rows, false, nullptr); }
 int sdqh_grouping_sets_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "grouping_sets_geometry", tile_rows, false, nullptr); }
 int sdqh_window_exclude_geometry(sdqh_ctx* ctx, int64_t* tile_rows, int64_t* narrow_max_width) { return window_tile_rows(ctx, "window_exclude_geometry", tile_rows, true, narrow_max_width); }

@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
+from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, MOMENT_OPS, MomentsRequest, moments_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -162,7 +162,7 @@ class Engine:
         # "ranked": the order columns that went through a rank table} (the last 256)
         self.order_routes = collections.deque(maxlen=256)
         # the requests with partitions (result.WindowRequest and its subclasses) are served on the device where the library has their
-        # extension and their switch is on — one switch per kind, device_window .. device_group_distinct, set from its environment
+        # extension and their switch is on — one switch per kind, device_window .. device_group_moments, set from its environment
         # variable SDQLPY_AMD_DEVICE_...; 0 forces the host route (A/B measurements, tests).  _WINDOW_ROUTES says which is whose.
         for rec in _WINDOW_ROUTES:
             setattr(self, rec.switch, os.environ.get(rec.env, "1") != "0")
@@ -1737,12 +1737,12 @@ def _order_spec(top, spec_of, decoded_of):
     spec = _FrameSpec(spec)
     if rec.value_frames:
         spec.decoded_order = tuple(nm for nm, _ in top.order if decoded_of(nm))
-    measured = rec.measured(top, spec)
-    cols = list(dict.fromkeys(col for col in measured if isinstance(col, str)))
+    measured = rec.measured(top, spec)                       # (a list of names: a column of several measures — a MomentsRequest's (y, x))
+    cols = list(dict.fromkeys(c for col in measured for c in (col if isinstance(col, list) else [col]) if isinstance(c, str)))
     plain = spec_of([(c, "asc") for c in cols], False) if cols else []      # (a QuantileRequest may measure nothing)
     if plain is not None:
         by_name = dict(zip(cols, plain))
-        spec.measures = [by_name[col] if isinstance(col, str) else col for col in measured]
+        spec.measures = [by_name[col] if isinstance(col, str) else [by_name[c] for c in col] if isinstance(col, list) else col for col in measured]
     return spec
 
 
@@ -1786,6 +1786,15 @@ def _finish_distincts(rs, ordered, top):
     """... of a DistinctRequest: the device's groups — `by` of their first rows and an aggregate a column."""
     names = [nm for nm, _ in top.by]
     return ResultSet(names + [name for name, _, _ in top.aggs], [rs.column(nm) for nm in names] + [np.asarray(a) for a in ordered.rank])
+
+
+def _finish_moments(rs, ordered, top):
+    """... of a MomentsRequest: the device's groups, the levels behind one another from the highest down — rollup_sets' order."""
+    pieces = []
+    for s, cols in enumerate(top.sets):
+        rows = np.nonzero(ordered.rank.set_of == s)[0]
+        pieces.append(({c: rs.column(c)[rows] for c in cols}, [np.asarray(a)[rows] for a in ordered.rank], len(rows)))
+    return moments_result(top, rs.column, pieces)
 
 
 def _finish_top(rs, ordered, top):
@@ -1983,6 +1992,19 @@ def _grouping_calls(eng, table, min_hits, top, terms, spec, cap, want_hits):
     return joined(0, 0), joined(1, 1), joined(2, 1), joined(3, 0), cols
 
 
+def _moments_call(eng, table, min_hits, top, terms, spec, cap, want_hits):
+    """The route "group_moments": one abi.Context.table_group_moments call over the grouping terms — levels = every prefix with rollup,
+    else the terms' own — and its rows: (keys, payload, values, hits, _GroupColumns), set_of following top.sets."""
+    n = len(terms)
+    aggs = []
+    for (_, op, _, _), cols in zip(top.aggs, spec.measures):
+        aggs.append((MOMENT_OPS.index(op),) + tuple(a for col in cols for a in _measure_args(col, None, None, spec, None)[:3]))
+    got = eng.ctx.table_group_moments(table, min_hits, terms, (1 << (n + 1)) - 1 if top.rollup else 1 << n, aggs, abi.SORT_ALL, cap, want_hits=want_hits)
+    cols = _GroupColumns(got[4])
+    cols.set_of = np.concatenate([np.full(int(got[5][len(s)]), i, np.int64) for i, s in enumerate(top.sets)])      # (the levels come from the highest down)
+    return got[0], got[1], got[2], got[3], cols
+
+
 def _mode_decoded(raw, measure, col, keys, payload, key_fields_of):
     """The column `col` of a "group_distinct" route's mode: raw = the 64 bits of the stored column `measure` names at the winning rows
     — put in that column's place among the rows' own arrays and decoded by key_fields_of(keys, payload), the result's own decoding."""
@@ -2107,6 +2129,14 @@ _WINDOW_ROUTES = (
            call=lambda eng, table, min_hits, top, terms, spec, k, cap, want_hits: _distinct_calls(eng, table, min_hits, top, terms, spec, cap, want_hits),
            note=_distinct_note, integral=lambda item: item[1] in ("sum_distinct", "mode"),      # what is summed or copied; an average stays the double it is
            fits=lambda top, spec: top.calls() is not None, measured=_distinct_measured, per_call=True, renote=False, raw_modes=True, finish=_finish_distincts),
+    # VAR / STDDEV / COVAR / CORR / REGR per group (moments), one abi.Context.table_group_moments call (_moments_call): at most GM_MAX_AGGS
+    # aggregates whose measures — one or two a column — are underived numeric columns, over at most SORT_MAX_KEYS grouping columns; with
+    # rollup every prefix is a level of the same call.  Every column is a double: none takes its measure's dtype.  Noted with "aggs",
+    # "rollup" and "calls"
+    _Route(MomentsRequest, "group_moments", "device_group_moments", "has_group_moments", "aggs", abi.GM_MAX_AGGS,
+           call=lambda eng, table, min_hits, top, terms, spec, k, cap, want_hits: _moments_call(eng, table, min_hits, top, terms, spec, cap, want_hits),
+           note=lambda top, route, spec: {"aggs": [list(a) for a in top.aggs], "rollup": top.rollup, "calls": 1 if route == "group_moments" else 0},
+           integral=lambda item: False, measured=lambda top, spec: [[y] if x is None else [y, x] for _, _, y, x in top.aggs], finish=_finish_moments),
     # GROUP BY ROLLUP / CUBE / GROUPING SETS over a result, one abi.Context.table_grouping_sets call per chain of sets (_grouping_calls):
     # at most GS_MAX_AGGS aggregates whose measures are underived numeric columns, over at most SORT_MAX_KEYS grouping columns.  Noted
     # with the sets as listed, the aggregates, and how many device calls serve them

@@ -720,6 +720,130 @@ def distinct_request(columns, by, aggs):
     return req
 
 
+MOMENT_OPS = ("var_pop", "var_samp", "stddev_pop", "stddev_samp", "covar_pop", "covar_samp", "corr", "regr_slope", "regr_intercept")      # their positions are abi.GM_VAR_POP .. GM_REGR_INTERCEPT
+MOMENT_UNIVARIATE = MOMENT_OPS[:4]                         # the ops of one column; the others take (y, x)
+MOMENT_NULL = np.array([0x7FF8000000000000], np.uint64).view(np.float64)[0]      # what stands for SQL's NULL: the device's quiet NaN, bit for bit
+
+
+class MomentsRequest(WindowRequest):
+    """The second moments per group, travelling where a WindowRequest travels: [1] = the grouping columns `by` with their directions
+    (all of them partition); aggs = [(name of the new column, op: a name of MOMENT_OPS, y, x or None)] — a univariate op reads y alone, a
+    bivariate one y (the dependent measure, as in SQL's REGR_SLOPE(Y, X)) and x; rollup: the sets are rollup_sets(by), not `by` alone.
+    The result holds `by` and a float64 column per aggregate, one row per group, ordered by `by`; with rollup the sets one after the
+    other, rolled-up columns filled and an int64 column "grouping" last, as a GroupingRequest's.  Every other column is dropped."""
+    method = terms_method = "moments"
+    items_attr, served_by = "aggs", "momented"
+
+    def __new__(cls, by, aggs, rollup=False):
+        self = WindowRequest.__new__(cls, WINDOW_ALL, list(by), len(by), 0, WINDOW_ALL, None)
+        self.aggs = [(str(n), str(op), str(y), None if x is None else str(x)) for n, op, y, x in aggs]
+        self.rollup = bool(rollup)
+        names = [nm for nm, _ in self[1]]
+        if not names or len(set(names)) != len(names) or not self.aggs:
+            raise ValueError("moments: bad columns")
+        if any(op not in MOMENT_OPS or (x is None) != (op in MOMENT_UNIVARIATE) or y in names or x in names for _, op, y, x in self.aggs):
+            raise ValueError("moments: bad aggregate")
+        return self
+
+    reserved = property(lambda self: ("grouping",) if self.rollup else ())
+    sets = property(lambda self: rollup_sets([nm for nm, _ in self[1]]) if self.rollup else [tuple(nm for nm, _ in self[1])])
+
+    def masks(self):
+        """the `grouping` value of every set's rows (GroupingRequest.masks)"""
+        names = [nm for nm, _ in self[1]]
+        return [sum(1 << (len(names) - 1 - i) for i, nm in enumerate(names) if nm not in s) for s in self.sets]
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, both measures through `names` (old name -> new)."""
+        names = names or {}
+        return MomentsRequest(terms, [(n, op, names.get(y, y), names.get(x, x)) for n, op, y, x in self.aggs], self.rollup)
+
+    def check_columns(self, columns):
+        WindowRequest.check_columns(self, columns)               # (the terms, y and the new names)
+        for _, _, _, x in self.aggs:
+            if x is not None and x not in columns:
+                raise KeyError("moments: the result has no column %r" % x)
+
+
+def moments_request(columns, by, aggs, rollup=False):
+    """The checked MomentsRequest of moments: by = a non-empty list of columns, a column `name` or (name, "asc" | "desc"); aggs = {new
+    column: (op, y) | (op, y, x)} with op a name of MOMENT_OPS — "var_pop" .. "stddev_samp" take one column, "covar_pop" ..
+    "regr_intercept" two, y first.  columns: the result's column names when they are known (None: checked when the result is).
+    KeyError for a column the result lacks or a new column it has already, ValueError for everything else."""
+    if isinstance(by, str) or not isinstance(by, (list, tuple)) or not by:
+        raise ValueError("moments: by is a non-empty list of columns")
+    terms = []
+    for c in by:
+        name, d = (c, "asc") if isinstance(c, str) else (c[0], c[1]) if isinstance(c, (list, tuple)) and len(c) == 2 else (None, None)
+        if not isinstance(name, str) or d not in ("asc", "desc"):
+            raise ValueError("moments: a column is a name or (name, 'asc' | 'desc')")
+        if name in [nm for nm, _ in terms]:
+            raise ValueError("moments: column %r comes twice in by" % name)
+        terms.append((name, d))
+    _aggs_dict("moments", aggs, "(op, y) or (op, y, x)")
+    out = []
+    for name, spec in aggs.items():
+        _agg_spec("moments", name, spec, "(op, y) or (op, y, x)", lambda n: n in (2, 3))
+        op, y, x = spec[0], spec[1], spec[2] if len(spec) == 3 else None
+        if op not in MOMENT_OPS:
+            raise ValueError("moments: op is one of %s, not %r" % (", ".join(MOMENT_OPS), op))
+        if op in MOMENT_UNIVARIATE and x is not None:
+            raise ValueError("moments: %s takes one column" % op)
+        if op not in MOMENT_UNIVARIATE and x is None:
+            raise ValueError("moments: %s takes two columns, (y, x)" % op)
+        for col in (y,) if x is None else (y, x):
+            if not isinstance(col, str):
+                raise ValueError("moments: a measure is a column name")
+            if col in [nm for nm, _ in terms]:
+                raise ValueError("moments: the measure %r is a grouping column" % col)
+        out.append((name, op, y, x))
+    if len(set(n for n, _, _, _ in out) | set(nm for nm, _ in terms)) != len(out) + len(terms):
+        raise ValueError("moments: a new column has the name of a grouping column")
+    if rollup and "grouping" in [n for n, _, _, _ in out]:
+        raise ValueError("moments: with rollup the result's own column is named 'grouping'")
+    req = MomentsRequest(terms, out, rollup)
+    if columns is not None:
+        req.check_columns(columns)
+    return req
+
+
+def moments_result(req, column_of, pieces):
+    """The ResultSet of a MomentsRequest out of its sets' rows, whoever took the moments: pieces[s] = ({column of set s: its groups'
+    values}, [one float64 array per aggregate], the number of groups).  Without rollup the one set's columns and the aggregates; with
+    it grouped_result's layout: the sets in order, rolled-up columns filled, the `grouping` column last."""
+    names = [nm for nm, _ in req[1]]
+    sizes = [m for _, _, m in pieces]
+    cols = []
+    for nm in names:
+        src = column_of(nm)
+        cols.append(np.concatenate([np.asarray(by[nm]) if nm in by else _rolled_up(src, m) for (by, _, _), m in zip(pieces, sizes)]))
+    for a in range(len(req.aggs)):
+        cols.append(np.concatenate([np.asarray(aggs[a], np.float64) for _, aggs, _ in pieces]))
+    out = names + [n for n, _, _, _ in req.aggs]
+    if req.rollup:
+        cols.append(np.concatenate([np.full(m, mask, np.int64) for m, mask in zip(sizes, req.masks())]))
+        out.append("grouping")
+    return ResultSet(out, cols)
+
+
+def moment_finish(op, count, qy, qx, c, muy, mux):
+    """An op of MOMENT_OPS out of its group's centred sums, in the order of operations include/sdqh_sort_moments.h states: count the
+    groups' sizes as doubles, qy / qx / c the sums of squares and products (what the op does not read: None), muy / mux the means."""
+    with np.errstate(all="ignore"):
+        if op in ("var_pop", "stddev_pop", "covar_pop"):
+            v = (c if op == "covar_pop" else qy) / count
+            return np.sqrt(v) if op == "stddev_pop" else v
+        if op in ("var_samp", "stddev_samp", "covar_samp"):
+            v = (c if op == "covar_samp" else qy) / (count - 1.0)
+            return np.where(count > 1.0, np.sqrt(v) if op == "stddev_samp" else v, MOMENT_NULL)
+        if op == "corr":
+            t = c / (np.sqrt(qx) * np.sqrt(qy))
+            t = np.where(t > 1.0, 1.0, np.where(t < -1.0, -1.0, t))
+            return np.where((qx != 0.0) & (qy != 0.0), t, MOMENT_NULL)
+        slope = c / qx
+        return np.where(qx != 0.0, slope if op == "regr_slope" else muy - slope * mux, MOMENT_NULL)
+
+
 def slide_empty(default, is_f64, what="sliding"):
     """What an empty frame gives for a measure of dtype float64 (is_f64) or int64: `default`, or with None NaN / 0.  ValueError for a
     default that does not fit the dtype: a float for an int64 column, an int outside int64."""
@@ -1371,6 +1495,65 @@ class ResultSet:
         and how often it comes, and ("count", None), the group's rows.  The result holds `by` and the aggregates, one row per group,
         ordered by `by` (see DistinctRequest)."""
         return self.distincted(distinct_request(self.columns, by, aggs))
+
+    def momented(self, req):
+        """The groups of a MomentsRequest, what sdqh_table_group_moments does on the device (include/sdqh_sort_moments.h), on the host:
+        the two-pass algorithm in numpy.  Per set a stable lexsort by the set's columns (order_image: the device's total order), a
+        group wherever a neighbour differs; every measure as float64 minus its group's first sorted row's, np.add.reduceat for the
+        sums, np.repeat of the means back to the rows, reduceat again over the centred squares and products, and the op's formula
+        (moment_finish).  The exact cases are the device's: a constant group has Q = 0.0, *_samp of one row, corr with a constant
+        column and regr_* with a constant x are NaN.  An empty result has no groups, not even the grand total."""
+        self._wait()
+        req.check_columns(self.columns)
+        n = self._n
+        direction = dict(req[1])
+        measures = {}
+        for name, op, y, x in req.aggs:
+            for col in (y, x):
+                if col is not None and col not in measures:
+                    v = self.column(col)
+                    if v.dtype.kind not in "iubf":
+                        raise ValueError("moments: %s of column %r: the measure is not numeric" % (op, col))
+                    measures[col] = np.ascontiguousarray(v, np.float64)
+        pieces = []
+        for s in req.sets:
+            images = [order_image(self.column(c), direction[c] == "desc") for c in s]
+            idx = np.lexsort(images[::-1]) if images else np.arange(n)    # stable: ties keep the stored order
+            head = np.zeros(n, bool)
+            if n:
+                head[0] = True
+            for u in images:
+                head[1:] |= u[idx][1:] != u[idx][:-1]
+            starts = np.nonzero(head)[0]
+            m = len(starts)
+            rows = np.diff(np.append(starts, n))
+            count = rows.astype(np.float64)
+            shifted, centred, mean = {}, {}, {}
+            with np.errstate(all="ignore"):
+                for col, v in measures.items() if m else ():
+                    v = v[idx]
+                    shifted[col] = v - np.repeat(v[starts], rows)             # the shift by the representative
+                    mu = np.add.reduceat(shifted[col], starts) / count
+                    centred[col] = shifted[col] - np.repeat(mu, rows)
+                    mean[col] = v[starts] + mu
+                aggs = []
+                for name, op, y, x in req.aggs:
+                    if not m:
+                        aggs.append(np.zeros(0, np.float64))
+                        continue
+                    qy = np.add.reduceat(centred[y] * centred[y], starts)
+                    qx = np.add.reduceat(centred[x] * centred[x], starts) if x is not None else None
+                    c = np.add.reduceat(centred[x] * centred[y], starts) if x is not None else None
+                    aggs.append(moment_finish(op, count, qy, qx, c, mean[y], mean.get(x)))
+            pieces.append(({c: self.column(c)[idx[starts]] for c in s}, aggs, m))
+        return moments_result(req, self.column, pieces)
+
+    def moments(self, by, aggs, rollup=False):
+        """VAR / STDDEV / COVAR / CORR / REGR per group of `by` (a non-empty list of columns, a column a name or (name, "asc" |
+        "desc")): aggs = {new column: (op, y) | (op, y, x)}, op in MOMENT_OPS.  The result holds `by` and a float64 column per
+        aggregate, one row per group, ordered by `by`; rollup=True: every prefix of `by` down to the grand total, with `grouping`
+        (see MomentsRequest)."""
+        return self.momented(moments_request(self.columns, by, aggs, rollup))
 
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:

@@ -503,6 +503,19 @@ def sdql_compile(in_type):
             and ops are checked here, before anything is launched."""
             return _requested("distinct_request", list(by) if isinstance(by, (list, tuple)) else by, aggs)
 
+        def moments(by, aggs, rollup=False):
+            """The same query finished with the second moments of every group of `by` — a non-empty list of columns, a column a name or
+            (name, "asc" | "desc") —, aggs = {new column: (op, y) | (op, y, x)}: op in "var_pop" / "var_samp" / "stddev_pop" /
+            "stddev_samp" (one column) or "covar_pop" / "covar_samp" / "corr" / "regr_slope" / "regr_intercept" (two: y, the dependent
+            one, then x, as SQL's REGR_SLOPE(Y, X)), e.g. ``q3.moments(["o_orderdate"], {"spread": ("stddev_samp", "revenue"),
+            "trend": ("regr_slope", "revenue", "o_shippriority")})(li, cu, ord)``.  The result holds `by` and a float64 column per
+            aggregate and none of the query's other columns, one row per group, ordered by `by`; where SQL gives NULL — a sample
+            variance of one row, a correlation with a constant column — the column holds NaN.  rollup=True: every prefix of `by` down
+            to the grand total behind the same sort, with rollup's `grouping` column and fill.  Taken by the two-pass algorithm (the
+            mean first, then the centred squares and products): data far from zero loses nothing.  Names and ops are checked here,
+            before anything is launched."""
+            return _requested("moments_request", list(by) if isinstance(by, (list, tuple)) else by, aggs, rollup)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -516,6 +529,7 @@ def sdql_compile(in_type):
         wrapper.cube = cube
         wrapper.grouping_sets = grouping_sets
         wrapper.distincts = distincts
+        wrapper.moments = moments
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
