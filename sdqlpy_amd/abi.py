@@ -75,6 +75,12 @@ GD_MAX_AGGS = 4
 GROUP_MOMENTS_EXPORTS = ["sdqh_table_group_moments", "sdqh_group_moments_geometry"]
 GM_VAR_POP, GM_VAR_SAMP, GM_STDDEV_POP, GM_STDDEV_SAMP, GM_COVAR_POP, GM_COVAR_SAMP, GM_CORR, GM_REGR_SLOPE, GM_REGR_INTERCEPT = range(9)
 GM_MAX_AGGS = 4
+# ... and its twelfth (include/sdqh_sort_sessions.h, Library.has_sessions): sessions — a partition cut where the ORDER BY value jumps by
+# more than a gap or a marker column changes —, columns over the row's whole session, per row or one row per session
+SESSIONS_EXPORTS = ["sdqh_table_sessions", "sdqh_sessions_geometry"]
+SS_GAP, SS_CHANGE = 0, 1
+SS_SUM, SS_COUNT, SS_MIN, SS_MAX, SS_FIRST, SS_LAST, SS_AVG, SS_NUMBER, SS_ROW = range(9)      # 0..5 are the slides' ops, 6 is WEX_AVG
+SS_MAX_COLS = 4
 # all of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
@@ -86,6 +92,7 @@ WINDOW_EXTENSIONS = {
     "has_grouping_sets": (GROUPING_SETS_EXPORTS, "sdqh_sort_groups.h", "grouping sets", "has_window_agg"),
     "has_group_distinct": (GROUP_DISTINCT_EXPORTS, "sdqh_sort_distinct.h", "group distinct", "has_grouping_sets"),
     "has_group_moments": (GROUP_MOMENTS_EXPORTS, "sdqh_sort_moments.h", "group moments", "has_grouping_sets"),
+    "has_sessions": (SESSIONS_EXPORTS, "sdqh_sort_sessions.h", "sessions", "has_grouping_sets"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -209,6 +216,40 @@ def _marshal_moment_aggs(aggs):
         arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(a[0]), int(a[1]), int(a[2]), 1 if a[3] else 0
         if len(a) > 4:
             arr[i].kind2, arr[i].index2, arr[i].is_f64_2 = int(a[4]), int(a[5]), 1 if a[6] else 0
+    return arr
+
+
+class SessionRule(C.Structure):
+    """sdqh_session_rule: the rule (SS_GAP / SS_CHANGE), SS_CHANGE's marker named as a SortKey names a column, SS_GAP's gap — an int64,
+    or the bits of a double for a double gap term."""
+    _fields_ = [("rule", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32), ("gap", C.c_int64)]
+
+
+class SessionCol(C.Structure):
+    """sdqh_session_col: an op (SS_SUM .. SS_ROW) and its measure, named as a SortKey names a column."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32)]
+
+
+assert C.sizeof(SessionRule) == 24 and C.sizeof(SessionCol) == 16      # the header's sizes
+
+
+def _marshal_session_rule(rule):
+    """(SS_GAP, gap) — gap an int, or a float for a double gap term: its bits travel — or (SS_CHANGE, kind, index, is_f64) -> a SessionRule."""
+    r = SessionRule()
+    r.rule = int(rule[0])
+    if r.rule == SS_GAP:
+        gap = rule[1]
+        r.gap = int(np.array([gap], np.float64).view(np.int64)[0]) if isinstance(gap, (float, np.floating)) else int(gap)
+    elif len(rule) > 3:
+        r.kind, r.index, r.is_f64 = int(rule[1]), int(rule[2]), 1 if rule[3] else 0
+    return r
+
+
+def _marshal_session_cols(cols):
+    """[(op, kind, index, is_f64)] -> a SessionCol array (one spare element for an empty list)."""
+    arr = (SessionCol * max(1, len(cols)))()
+    for i, (op, kind, index, is_f64) in enumerate(cols):
+        arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
     return arr
 
 
@@ -1573,6 +1614,35 @@ class Context:
         """Sorted positions per tile of sdqh_table_group_moments' passes: what the tests size their cases from."""
         return self._window_geometry("has_group_moments", 1)
 
+    def table_sessions(self, table, min_hits, npartition, terms, rule, cols, limit, capacity, per_session=False, want_hits=True):
+        """Sessions inside the partitions of the ordered entries (include/sdqh_sort_sessions.h): terms and npartition as table_window
+        takes them; rule: (SS_GAP, gap) — a new session where terms[npartition]'s value moves on by more than gap, an int, or a float for
+        a double term — or (SS_CHANGE, kind, index, is_f64) — where that field's stored bits change; cols: [(op, kind, index, is_f64)],
+        op in SS_SUM .. SS_ROW over the row's whole session, at most SS_MAX_COLS.  Every selected row, the first min(limit, n) in
+        sorted order, or with per_session one row per session (its first row).  Returns (keys, payload, values, hits, cols) — cols one
+        array per column: float64 for SS_AVG and for a double measure under SS_SUM / MIN / MAX / FIRST / LAST, else int64."""
+        self._need("has_sessions", "table_sessions")
+        lead = (C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms), C.byref(_marshal_session_rule(rule)), C.c_int(1 if per_session else 0),
+                C.c_int(len(cols)), _marshal_session_cols(cols), C.c_int64(limit))
+        got = self._sorted_call("table_sessions", table, lead, limit, capacity, want_hits, True, naggs=max(1, len(cols)))
+        as_f64 = [op == SS_AVG or (op in (SS_SUM, SS_MIN, SS_MAX, SS_FIRST, SS_LAST) and _measure_is_f64(kind, is_f64)) for op, kind, _, is_f64 in cols]
+        return got[:4] + ([got[4][i].view(np.float64) if f else got[4][i] for i, f in enumerate(as_f64)],)
+
+    def table_sessions_count(self, table, min_hits, npartition, terms, rule, per_session=False, limit=SORT_ALL):
+        """The count-only call of table_sessions: min(limit, rows), or with per_session min(limit, sessions) — then the sort and the
+        boundary pass run —; no row is fetched."""
+        self._need("has_sessions", "table_sessions")
+        n = C.c_int64()
+        self._check(self.lib.sdqh_table_sessions(self.handle, table.handle, C.c_int64(min_hits), C.c_int(npartition), C.c_int(len(terms)), _marshal_sort_terms(terms),
+                                                 C.byref(_marshal_session_rule(rule)), C.c_int(1 if per_session else 0), C.c_int(0), None, C.c_int64(limit), C.c_int64(0),
+                                                 None, None, None, None, None, C.byref(n)))
+        self._after_call("table_sessions")
+        return n.value
+
+    def sessions_geometry(self):
+        """Sorted positions per tile of sdqh_table_sessions' passes: what the tests size their cases from."""
+        return self._window_geometry("has_sessions", 1)
+
     def _need_extrema(self, what):
         if not self.library.has_extrema:
             raise SdqhError(ERR_UNSUPPORTED, "%s: %s has no extrema extension" % (what, self.library.path))
@@ -1861,6 +1931,10 @@ class Library:
             L.sdqh_table_group_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_group_moments_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        if self.has_sessions:
+            L.sdqh_table_sessions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_sessions_geometry.argtypes = [C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

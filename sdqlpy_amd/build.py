@@ -39,7 +39,8 @@ EXCLUDE_HEADER = os.path.join(INCLUDE, "sdqh_sort_exclude.h")
 GROUPS_HEADER = os.path.join(INCLUDE, "sdqh_sort_groups.h")
 DISTINCT_HEADER = os.path.join(INCLUDE, "sdqh_sort_distinct.h")
 MOMENTS_HEADER = os.path.join(INCLUDE, "sdqh_sort_moments.h")
-UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER], "sdqh_extrema.hip": HIP_HEADERS[:3] + [EXTREMA_HEADER]}
+SESSIONS_HEADER = os.path.join(INCLUDE, "sdqh_sort_sessions.h")
+UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER, SESSIONS_HEADER], "sdqh_extrema.hip": HIP_HEADERS[:3] + [EXTREMA_HEADER]}
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-ffp-contract=off",          # keep the reference's a*(1.0-b) association: no FMA contraction
@@ -110,7 +111,7 @@ def hipcc_path():
 def build_hip(force=False, save_temps=False):
     """Compile the HIP kernels + C ABI for gfx950.  hipcc cross-compiles without a GPU."""
     objs = [os.path.join(CSRC, obj) for _, obj in HIP_UNITS]
-    if not (force or _stale(HIP_LIB, HIP_SOURCES + HIP_HEADERS + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER, EXTREMA_HEADER]) or not all(os.path.exists(o) for o in objs)):
+    if not (force or _stale(HIP_LIB, HIP_SOURCES + HIP_HEADERS + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER, SESSIONS_HEADER, EXTREMA_HEADER]) or not all(os.path.exists(o) for o in objs)):
         return HIP_LIB                                  # (a unit without its object: the library predates the unit)
     hipcc = hipcc_path()
     if hipcc is None:

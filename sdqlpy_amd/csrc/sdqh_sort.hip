@@ -139,6 +139,17 @@
 //   k_gs_tiles / k_wagg_scan / k_gs_run
 //                     pass 1, over the rows at that level: the groups' sums; k_mo_center hands every row its group's mean and writes the
 //                     centred squares and products; the same three again, pass 2; k_mo_finish applies the ops — see the section
+//   SESSIONS          in their place (STEP_SESSIONS).  sdqh_table_sessions (include/sdqh_sort_sessions.h) cuts every partition where the
+//                     ORDER BY value jumps by more than a gap or a marker column changes, and returns columns over the row's session:
+//
+//   k_ss_heads        the boundary pass: each position against its predecessor BY VALUE (through refs, before the keys' encoding);
+//                     the cuts as two flag bytes and a depth byte, the tile carries and counts the passes below expect
+//   k_win_scan / k_win_rank
+//                     the session's number in its partition (a dense rank), the row's number in its session (a row number)
+//   k_wagg_tiles / k_wagg_scan / k_wagg_run / k_wagg_next, k_ss_rows
+//                     per row: SUM / COUNT / MIN / MAX over sessions as over partitions; every row takes the value at its session's end
+//   k_sort_bins, k_wagg_tiles / k_wagg_scan / k_gs_run, k_ss_sessions
+//                     per session: the count to the host, the folds kept in the session's slot as a level of GROUPS — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -158,6 +169,7 @@
 #include "sdqh_sort_groups.h"
 #include "sdqh_sort_distinct.h"
 #include "sdqh_sort_moments.h"
+#include "sdqh_sort_sessions.h"
 
 using namespace sdqh_host;
 
@@ -1819,6 +1831,160 @@ __global__ __launch_bounds__(TPB) void k_mo_finish(DevStage st, DevMoAggs mo, De
     }
 }
 
+// ---- sessions inside partitions (sdqh_table_sessions) -----------------------------------------------------------------------------
+// Every pass above cuts where the KEYS decide; a session is cut where the data along the order decide (include/sdqh_sort_sessions.h):
+// sorted position r opens one iff it opens its partition or the rule says so about the raw values at r - 1 and r.  k_ss_heads makes
+// that comparison once and leaves the cuts in the three encodings the passes above read, so that they run over sessions unchanged:
+//   headsA            WIN_PART on partition heads, WIN_TIE on session heads: a dense rank over it (k_win_scan / k_win_rank) numbers the
+//                     sessions of a partition — SDQH_SS_NUMBER
+//   headsB            WIN_PART | WIN_TIE on every session head: a row number over it is SDQH_SS_ROW, and the frames' passes
+//                     (k_wagg_tiles / _scan / _run / _next) fold SUM / COUNT / MIN / MAX over sessions as they fold over partitions
+//   depth             0 partition head, 1 session head, 2 neither: level 2 of the grouping sets' passes is "sessions" — k_sort_bins
+//                     counts them, k_gs_run keeps the value at a session's last row in the session's slot
+// Per row, k_ss_rows walks a tile backwards (k_wagg_ends' shape): the session's last position is read off the ballots and the tiles
+// behind, its first off the row number; a fold's value is the running value at the last position, an AVG divides it by the length,
+// FIRST / LAST gather the measure there.  Per session, k_ss_sessions does the same from the sessions' positions.  No atomics.
+struct DevSsRule { DevSortTerm tm; int64_t gap; int32_t rule, _pad; };      // tm: the gap term, or the marker as a term with no derivation
+struct DevSsCols { DevSortKey sk[SDQH_SS_MAX_COLS]; int32_t op[SDQH_SS_MAX_COLS], slot[SDQH_SS_MAX_COLS]; int32_t n, _pad; };      // slot: the column's fold among the call's folds (-1: none)
+static_assert(SDQH_SS_MAX_COLS == SDQH_WAGG_MAX_AGGS, "the sessions' folds are the frames'");
+
+// the rule's value at gathered entry g: the stored 64 bits, a derived term's `field` (k_sort_keys' derivation, before sort_bits)
+__device__ __forceinline__ int64_t ss_value(const DevSortTerm& tm, const DevStage& st, const uint32_t* __restrict__ refs, uint32_t g) {
+    const int64_t idx = (int64_t)refs[g];
+    const uint32_t hits = st.shits ? st.shits[idx] : 0u;
+    const int64_t raw = sort_raw(tm.sk, st, idx, hits);
+    if (!term_derived(tm)) return raw;
+    uint64_t f = (uint64_t)raw;
+    if (tm.div > 1) f /= tm.div;
+    if (tm.mod) f %= tm.mod;
+    return (int64_t)(f + (uint64_t)tm.add);
+}
+// does the row with value `cur` continue the session of its predecessor in the order, `prev`?  An integer gap by the unsigned
+// difference of the two order-adjacent values (prev <= cur ascending, >= descending: exact, nothing wraps), a double gap by one
+// IEEE addition and two comparisons
+__device__ __forceinline__ bool ss_continues(const DevSsRule& ru, int64_t prev, int64_t cur) {
+    if (ru.rule == SDQH_SS_CHANGE) return prev == cur;
+    if (!ru.tm.sk.is_f64) {
+        const uint64_t d = ru.tm.sk.desc ? (uint64_t)prev - (uint64_t)cur : (uint64_t)cur - (uint64_t)prev;
+        return d <= (uint64_t)ru.gap;
+    }
+    const double vp = __longlong_as_double(prev), vc = __longlong_as_double(cur), gap = __longlong_as_double(ru.gap);
+    if (vc != vc) return prev == cur;
+    if (vp != vp) return false;
+    const double a = vc + (ru.tm.sk.desc ? gap : -gap);
+    return (a < vc ? a : vc) <= vp && vp <= (a < vc ? vc : a);
+}
+
+// 1. a wave per tile of sorted positions: the two flag bytes and the depth of every position, per tile the carries of both flag
+// arrays (k_win_scan's), the first session head (what k_wagg_scan and k_wagg_next read) and the heads of levels 0 .. 2
+// (tcount[L * ntiles + tile], k_sort_bins').  keys: the staged keys of the npart partition terms.
+__global__ __launch_bounds__(TPB) void k_ss_heads(DevStage st, DevSsRule ru, const uint64_t* __restrict__ keys, size_t key_stride, int npart, const uint32_t* __restrict__ refs,
+                                                 const uint32_t* __restrict__ perm, uint32_t n, uint8_t* __restrict__ headsA, uint8_t* __restrict__ headsB, uint8_t* __restrict__ depth,
+                                                 WinCarry* __restrict__ carryA, WinCarry* __restrict__ carryB, WaggHeads* __restrict__ tfirst, uint32_t* __restrict__ tcount, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    WinCarry runA = {0u, 0u, 0u, 0u}, runB = {0u, 0u, 0u, 0u};
+    WaggHeads fh = {n, n};
+    uint32_t cp = 0u, cs = 0u;
+    for (uint64_t b = r0; b < r1; b += WAVE) {
+        const uint64_t r = b + lane_id();
+        const bool live = r < r1;
+        bool ph = false, sh = false;
+        if (live) {
+            if (r == 0) ph = sh = true;
+            else {
+                const uint32_t g = perm ? perm[r] : (uint32_t)r, h = perm ? perm[r - 1] : (uint32_t)(r - 1);
+                if (g < n && h < n) {                                    // (a permutation of [0, n): always)
+                    for (int c = 0; c < npart; ++c) ph |= keys[(size_t)c * key_stride + g] != keys[(size_t)c * key_stride + h];
+                    sh = ph || !ss_continues(ru, ss_value(ru.tm, st, refs, h), ss_value(ru.tm, st, refs, g));
+                }
+            }
+            headsA[r] = (uint8_t)((ph ? WIN_PART : 0u) | (sh ? WIN_TIE : 0u));
+            headsB[r] = (uint8_t)(sh ? (WIN_PART | WIN_TIE) : 0u);
+            depth[r] = (uint8_t)(ph ? 0u : (sh ? 1u : 2u));
+        }
+        const uint64_t mp = __ballot(ph), ms = __ballot(sh);
+        const uint32_t cnt = (uint32_t)min((uint64_t)WAVE, r1 - b);
+        win_step(runA, mp, ms, cnt);
+        win_step(runB, ms, ms, cnt);
+        if (ms && fh.part == n) fh.part = fh.tie = (uint32_t)b + (uint32_t)__builtin_ctzll(ms);
+        cp += (uint32_t)__popcll(mp); cs += (uint32_t)__popcll(ms);
+    }
+    if (lane_id() == 0) {
+        carryA[w] = runA; carryB[w] = runB; tfirst[w] = fh;
+        tcount[w] = w == 0 ? 1u : 0u; tcount[(size_t)ntiles + w] = cp; tcount[(size_t)2 * ntiles + w] = cs;
+    }
+}
+// an AVG: the session's sum (an integer one converted once) by its number of rows, one IEEE division — k_gs_avg's
+__device__ __forceinline__ uint64_t ss_avg(uint64_t s, int is_f64, uint32_t rows) {
+    const double sum = is_f64 ? __longlong_as_double((long long)s) : (double)(int64_t)s;
+    return (uint64_t)__double_as_longlong(sum / (double)rows);
+}
+// 2a. per row: the columns of the first m positions.  A tile walked backwards; `se` is the last position of lane's session — the
+// position before the next session head above the lane, in the batches behind or in the tiles behind (tnext) —, its first the row's
+// own position minus its row number (rowb, from 1; nullptr: no column reads it).  rows: k_wagg_run's running values over headsB,
+// numb: the dense ranks over headsA.  ntiles: the tiles that hold a position below m.
+__global__ __launch_bounds__(TPB) void k_ss_rows(DevStage st, DevSsCols sc, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint8_t* __restrict__ headsB,
+                                                const WaggHeads* __restrict__ tnext, const uint32_t* __restrict__ numb, const uint32_t* __restrict__ rowb, uint32_t n, uint32_t m,
+                                                size_t stride, const uint64_t* __restrict__ rows, uint64_t* __restrict__ fin, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t le = lanemask_lt() | (1ull << lane);
+    uint32_t next = tnext[w].part;
+    for (uint64_t b = r0 + ((r1 - r0 - 1) / WAVE) * WAVE; ; b -= WAVE) {
+        const uint64_t r = b + lane;
+        const bool live = r < r1;
+        const WaggBatch h = wagg_batch(headsB, r, live, le);
+        const uint64_t pg = h.mp & ~le;
+        const uint32_t se = (pg ? (uint32_t)b + (uint32_t)__builtin_ctzll(pg) : next) - 1u;
+        if (live && r < m && se < n && se >= r) {                        // (r <= se < n: always)
+            const uint32_t rn = rowb ? rowb[r] : 1u;
+            const uint32_t s0 = (uint32_t)r - (rn - 1u);                 // (a row number is at most r + 1)
+#pragma unroll
+            for (int c = 0; c < SDQH_SS_MAX_COLS; ++c) if (c < sc.n) {
+                const int op = sc.op[c];
+                uint64_t v;
+                if (op == SDQH_SS_NUMBER) v = (uint64_t)numb[r];
+                else if (op == SDQH_SS_ROW) v = (uint64_t)rn;
+                else if (op == SDQH_WSLIDE_FIRST) v = gd_measure(sc.sk[c], st, refs, perm, s0, n);
+                else if (op == SDQH_WSLIDE_LAST) v = gd_measure(sc.sk[c], st, refs, perm, se, n);
+                else {
+                    v = sc.slot[c] >= 0 ? rows[(size_t)sc.slot[c] * stride + se] : 0ull;      // (every other op folds: always)
+                    if (op == SDQH_WEX_AVG) v = ss_avg(v, sc.sk[c].is_f64, se - s0 + 1u);
+                }
+                fin[(size_t)c * stride + r] = v;
+            }
+        }
+        if (h.mp) next = (uint32_t)b + (uint32_t)__builtin_ctzll(h.mp);
+        if (b == r0) break;
+    }
+}
+// 2b. per session: a thread per returned session j.  pos: the sessions' sorted positions (k_gs_run's, all ng of them), sums: the
+// folds' values in the sessions' slots (gstride apart); the session's rows are [pos[j], pos[j + 1]) or up to n
+__global__ __launch_bounds__(TPB) void k_ss_sessions(DevStage st, DevSsCols sc, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, const uint32_t* __restrict__ pos,
+                                                    const uint32_t* __restrict__ numb, uint32_t n, uint32_t ng, uint32_t m, size_t gstride, const uint64_t* __restrict__ sums,
+                                                    uint64_t* __restrict__ val) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t p = pos[j];
+        const uint32_t next = j + 1 < ng ? pos[j + 1] : n;
+        if (p >= n || next <= p || next > n) continue;                   // (positions in order, below n: never taken)
+#pragma unroll
+        for (int c = 0; c < SDQH_SS_MAX_COLS; ++c) if (c < sc.n) {
+            const int op = sc.op[c];
+            uint64_t v;
+            if (op == SDQH_SS_NUMBER) v = (uint64_t)numb[p];
+            else if (op == SDQH_WSLIDE_FIRST) v = gd_measure(sc.sk[c], st, refs, perm, p, n);
+            else if (op == SDQH_WSLIDE_LAST) v = gd_measure(sc.sk[c], st, refs, perm, next - 1u, n);
+            else {
+                v = sc.slot[c] >= 0 ? sums[(size_t)sc.slot[c] * gstride + j] : 0ull;          // (every other op folds: always)
+                if (op == SDQH_WEX_AVG) v = ss_avg(v, sc.sk[c].is_f64, next - p);
+            }
+            val[(size_t)c * gstride + j] = v;
+        }
+    }
+}
+
 // The emit of every entry point: row j of the result = the entry at sorted position sel[j] (sel == nullptr: every position is
 // kept, j itself), which is gathered entry perm[position] (perm == nullptr: the gathered order itself).  o's arrays and out_rank
 // hold m rows each; a null array is not written, and rank is read only for out_rank.
@@ -2023,7 +2189,9 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // stage, `gd` the ops and measures as the caller named them.
 // STEP_MOMENTS (sdqh_table_group_moments) returns the rows of STEP_GROUPS — `levels`, level_rows —; `mo` holds its aggregates, the
 // distinct measures they read and the columns its second pass folds.
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS };
+// STEP_SESSIONS (sdqh_table_sessions) cuts the partitions of the first npart terms by `ssr` and returns every row (per_session 0) or
+// one row per session — then it filters as STEP_GROUPS does; `ss` are its columns, `aggs` the folds among them.
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS, STEP_SESSIONS };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
@@ -2032,6 +2200,7 @@ struct SortStep {
     uint32_t levels; int64_t* level_rows; DevGsAvg avg;
     int ngroup; DevGdAggs gd;
     DevMoAggs mo;
+    int per_session; DevSsRule ssr; DevSsCols ss;
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -2558,6 +2727,101 @@ static int step_moments(StepRun& r) {
     return SDQH_OK;
 }
 
+// Sessions (sdqh_table_sessions).  Block 3 = [flags A | flags B | depths | carries A | carries B | first heads | next heads | heads
+// per tile and level | level counts | session numbers | row numbers | kept per tile] and, per row, [elements, then running values |
+// columns | value carries].  Per session the count of level 2 goes to the host — the call's second wait, as step_groups' — and the
+// ways out are taken; block 4 = [sessions: positions | depths | folds | columns] [rows: elements | value carries].
+static int step_sessions(StepRun& r) {
+    sdqh_ctx* ctx = r.ctx;
+    const bool per = r.step.per_session != 0;
+    DevSsCols sc = r.step.ss;
+    DevWaggs ag = r.step.aggs;
+    if (!r.step.out) { sc.n = 0; ag.n = 0; }                          // rows only: no column is computed
+    const size_t nc = (size_t)sc.n, nf = (size_t)ag.n;
+    bool number = false, rown = false;                                // does a column read the sessions' numbers, the rows' numbers?
+    for (int c = 0; c < sc.n; ++c) {
+        number |= sc.op[c] == SDQH_SS_NUMBER;
+        rown |= !per && (sc.op[c] == SDQH_SS_ROW || sc.op[c] == SDQH_WSLIDE_FIRST || sc.op[c] == SDQH_WEX_AVG);
+    }
+    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
+    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    uint8_t *headsA = nullptr, *headsB = nullptr, *depth = nullptr; WinCarry *carryA = nullptr, *carryB = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
+    uint32_t *tcount = nullptr, *ltot = nullptr, *numb = nullptr, *rowb = nullptr, *tile_kept = nullptr;
+    uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr;
+    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
+            headsA = c.take<uint8_t>((size_t)r.n);
+            headsB = c.take<uint8_t>((size_t)r.n);
+            depth = c.take<uint8_t>((size_t)r.n);
+            carryA = c.take<WinCarry>(ntiles);
+            carryB = c.take<WinCarry>(ntiles);
+            tfirst = c.take<WaggHeads>(ntiles);
+            tnext = c.take<WaggHeads>(ntiles);
+            tcount = c.take<uint32_t>((size_t)ntiles * 3);
+            ltot = c.take<uint32_t>(3);
+            numb = c.take<uint32_t>(number ? (size_t)r.n : 0);
+            rowb = c.take<uint32_t>(rown ? (size_t)r.n : 0);
+            tile_kept = c.take<uint32_t>(ntiles);
+            elem = c.take<uint64_t>(per ? 0 : r.stride * nf);
+            fin = c.take<uint64_t>(per ? 0 : r.stride * nc);
+            tval = c.take<uint64_t>(per ? 0 : (size_t)ntiles * nf);
+        })) return r.nomem();
+    if (!number) numb = nullptr;
+    if (!rown) rowb = nullptr;
+    LAUNCH(ctx, "k_ss_heads", k_ss_heads, tgrid, r.table->stage, r.step.ssr, r.s.keys, r.s.key_stride, r.step.npart, r.s.refs, r.s.perm, r.un, headsA, headsB, depth,
+           carryA, carryB, tfirst, tcount, ntiles);
+    if (number) {
+        LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carryA, ntiles);
+        LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, headsA, carryA, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, numb, tile_kept, ntiles);
+    }
+    if (!per) {
+        if (rown) {
+            LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carryB, ntiles);
+            LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, headsB, carryB, r.un, (int)SDQH_WIN_ROW_NUMBER, ~0ull, rowb, tile_kept, ntiles);
+        }
+        if (nf) {
+            LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, headsB, r.un, r.stride, elem, tval, tfirst, ntiles);
+            LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)nf, ag, tfirst, r.un, tval, ntiles);
+            LAUNCH(ctx, "k_wagg_run", k_wagg_run, tgrid, ag, headsB, r.un, r.stride, elem, tval, ntiles);
+        }
+        const uint32_t mtiles = (uint32_t)((r.m + SORT_TILE - 1) / SORT_TILE);
+        LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, r.un, tnext, ntiles);
+        LAUNCH(ctx, "k_ss_rows", k_ss_rows, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), r.table->stage, sc, r.s.refs, r.s.perm, headsB, tnext, numb, rowb, r.un, (uint32_t)r.m,
+               r.stride, elem, fin, mtiles);
+        r.columns(fin, sc.n);
+        return SDQH_OK;
+    }
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 3, tcount, ntiles, ltot);  // per level: the tiles' offsets in place, the level's count
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = sync_stream(ctx)) return rc;
+    uint32_t tot[3];
+    std::memcpy(tot, ctx->result_host, sizeof(tot));
+    const int64_t g = (int64_t)tot[2];
+    if (g >= 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 sessions");      // (a selection holds fewer rows: never taken)
+    r.m = std::min<int64_t>(r.limit, g);
+    if (r.count_only) return r.done(r.m);
+    if (r.m > r.capacity) return r.overflow(r.m);
+    const size_t gstride = round_up((size_t)g * 8) / 8;
+    uint32_t* sel = nullptr; uint8_t* gdepth = nullptr; uint64_t *sums = nullptr, *val = nullptr;
+    if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
+            sel = c.take<uint32_t>((size_t)g);
+            gdepth = c.take<uint8_t>((size_t)g);
+            sums = c.take<uint64_t>(gstride * nf);
+            val = c.take<uint64_t>(gstride * nc);
+            elem = c.take<uint64_t>(r.stride * nf);
+            tval = c.take<uint64_t>((size_t)ntiles * nf);
+        })) return r.nomem();
+    if (nf) {
+        LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, headsB, r.un, r.stride, elem, tval, tfirst, ntiles);
+        LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)nf, ag, tfirst, r.un, tval, ntiles);
+    }
+    LAUNCH(ctx, "k_gs_run", k_gs_run, tgrid, ag, 2, 1, depth, (const uint32_t*)nullptr, elem, r.stride, r.un, tval, tcount + (size_t)2 * ntiles, ntiles,
+           sums, gstride, gdepth, sel, tot[2]);
+    if (nc) LAUNCH(ctx, "k_ss_sessions", k_ss_sessions, r.row_grid(), r.table->stage, sc, r.s.refs, r.s.perm, sel, numb, r.un, tot[2], (uint32_t)r.m, gstride, sums, val);
+    r.sel = sel;
+    for (r.ncols = 0; r.ncols < sc.n; ++r.ncols) r.col_src[r.ncols] = val + (size_t)r.ncols * gstride;
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -2592,6 +2856,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_GROUPS: step_rc = step_groups(r); break;            // (the rows themselves are the step's: always)
         case STEP_DISTINCTS: step_rc = step_distincts(r); break;      // (likewise)
         case STEP_MOMENTS: step_rc = step_moments(r); break;          // (likewise)
+        case STEP_SESSIONS: if (step.per_session || (step.out && step.ss.n)) step_rc = step_sessions(r); break;      // (per session likewise; per row its columns alone)
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -2977,6 +3242,47 @@ int sdqh_table_group_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_sessions(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                        const sdqh_session_rule* rule, int per_session, int ncols, const sdqh_session_col* cols, int64_t limit, int64_t capacity,
+                        int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
+    const char* who = "table_sessions";
+    bool ok = rule && (rule->rule == SDQH_SS_GAP || rule->rule == SDQH_SS_CHANGE) && (per_session == 0 || per_session == 1) &&
+              ncols >= 0 && ncols <= SDQH_SS_MAX_COLS && (cols || ncols == 0);
+    for (int c = 0; ok && c < ncols; ++c) ok = cols[c].op >= SDQH_WAGG_SUM && cols[c].op <= SDQH_SS_ROW && !(per_session && cols[c].op == SDQH_SS_ROW);
+    const bool gap = ok && rule->rule == SDQH_SS_GAP;
+    if (gap) {                                                        // the gap term (read here, so: is it there?), one with arithmetic, and a gap of its type
+        ok = in && npartition >= 0 && nterms >= npartition + 1 && nterms <= SDQH_SORT_MAX_KEYS && in[npartition].ranks == nullptr;
+        if (ok && column_is_f64(in[npartition].kind, in[npartition].is_f64)) {
+            double d; std::memcpy(&d, &rule->gap, 8);
+            ok = std::isfinite(d) && d >= 0.0;
+        } else if (ok) ok = rule->gap >= 0;
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_SESSIONS, npartition, out_cols);
+    st.per_session = per_session;
+    if (per_session) { st.filters = true; st.per_limit = 0; }         // no row is kept for its rank: the count is the sessions', known behind the boundary pass
+    st.ssr.rule = rule->rule; st.ssr.gap = rule->gap;
+    if (gap) st.ssr.tm = terms[npartition];
+    else if (int rc = measure_set(ctx, table, who, "marker", 0, rule->kind, rule->index, rule->is_f64, st.ssr.tm.sk)) return rc;
+    st.ss.n = ncols;
+    for (int c = 0; c < ncols; ++c) {
+        const sdqh_session_col& g = cols[c];
+        st.ss.op[c] = g.op; st.ss.slot[c] = -1;
+        if (g.op == SDQH_WAGG_COUNT || g.op == SDQH_SS_NUMBER || g.op == SDQH_SS_ROW) continue;      // (they ignore their measure)
+        if (int rc = measure_set(ctx, table, who, "column", c, g.kind, g.index, g.is_f64, st.ss.sk[c])) return rc;
+    }
+    for (int c = 0; c < ncols; ++c) {                                 // the folds among the columns (an AVG as the SUM it divides), as the frames' passes take them
+        const int op = st.ss.op[c] == SDQH_WEX_AVG ? SDQH_WAGG_SUM : st.ss.op[c];
+        if (op > SDQH_WAGG_MAX) continue;
+        DevWagg& d = st.aggs.a[st.aggs.n];
+        d.op = op; d.frame = SDQH_FRAME_ROWS; d.sk = st.ss.sk[c];
+        d.cls = fold_class(op, d.sk.is_f64, true);
+        st.ss.slot[c] = st.aggs.n++;
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
 // what the tests size their cases from: one tile for every family; narrow (the two exports that have it): the largest frame width
 // a kernel walks row by row — none does (slides fold two blocks, ranges make two searches and a tree query)
 static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, bool has_narrow, int64_t* narrow_max_width) {
@@ -2985,6 +3291,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_sessions_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "sessions_geometry", tile_rows, false, nullptr); }
 int sdqh_group_moments_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_moments_geometry", tile_rows, false, nullptr); }
 int sdqh_group_distinct_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_distinct_geometry", tile_rows, false, nullptr); }
 int sdqh_grouping_sets_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "grouping_sets_geometry", tile_rows, false, nullptr); }

@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, MOMENT_OPS, MomentsRequest, moments_result, QUANTILE_FNS, RANGE_UNITS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SlideRequest, \
+from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, MOMENT_OPS, MomentsRequest, moments_result, QUANTILE_FNS, RANGE_UNITS, SESSION_OPS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SessionRequest, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -162,7 +162,7 @@ class Engine:
         # "ranked": the order columns that went through a rank table} (the last 256)
         self.order_routes = collections.deque(maxlen=256)
         # the requests with partitions (result.WindowRequest and its subclasses) are served on the device where the library has their
-        # extension and their switch is on — one switch per kind, device_window .. device_group_moments, set from its environment
+        # extension and their switch is on — one switch per kind, device_window .. device_sessions, set from its environment
         # variable SDQLPY_AMD_DEVICE_...; 0 forces the host route (A/B measurements, tests).  _WINDOW_ROUTES says which is whose.
         for rec in _WINDOW_ROUTES:
             setattr(self, rec.switch, os.environ.get(rec.env, "1") != "0")
@@ -2005,6 +2005,47 @@ def _moments_call(eng, table, min_hits, top, terms, spec, cap, want_hits):
     return got[0], got[1], got[2], got[3], cols
 
 
+def _session_gap(top, spec):
+    """The gap of a SessionRequest as the device's gap term takes it — an int for an integer term, a float for a double one — or None
+    where it cannot, under _range_offsets' conditions: the term orders by its own arithmetic (no text ranks), the column is not text
+    or decoded on the host (spec.decoded_order), an integer term takes an integral gap inside int64, and a column the table keeps as
+    integer-valued doubles an integral one of at most 2^53 (no double holds the next).  The host refuses or saturates the rest."""
+    t = spec[top.npartition]
+    if _term_text(t) is not None or top.order[0][0] in getattr(spec, "decoded_order", ()):
+        return None
+    is_f64 = t[0] == abi.SORT_VALUE or (t[0] == abi.SORT_PAYLOAD and bool(t[3]))
+    gap = top.gap
+    if is_f64 and top.order[0][0] not in getattr(spec, "int_values", ()):
+        return float(gap)
+    integral = not isinstance(gap, (float, np.floating)) or float(gap) == int(gap)
+    if not integral or int(gap) >= 1 << 63 or (is_f64 and int(gap) > 1 << 53):
+        return None
+    return float(int(gap)) if is_f64 else int(gap)
+
+
+def _session_measured(top, spec):
+    """Per column its measure (None: it reads none) and, behind them, the marker of the change rule: like a measure it must be an
+    underived numeric column of the table — its stored bits are what the device compares."""
+    return [item[2] for item in top.cols] + ([top.marker] if top.rule == "change" else [])
+
+
+def _session_note(top, route, spec):
+    """("per": the partition columns, "order": the order columns)  The rule with its gap or marker, the columns, whether the rows are
+    the sessions, and how many device calls serve the request."""
+    return {"rule": top.rule, "gap": top.gap, "change": top.marker, "cols": [list(c) for c in top.cols], "per_session": top.per == "session",
+            "calls": 1 if route == "sessions" else 0}
+
+
+def _session_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    """The route "sessions": one abi.Context.table_sessions call."""
+    if top.rule == "gap":
+        rule = (abi.SS_GAP, _session_gap(top, spec))
+    else:
+        rule = (abi.SS_CHANGE,) + _measure_args(spec.measures[len(top.cols)], None, None, spec, None)[:3]
+    cols = [(SESSION_OPS.index(op),) + _measure_args(col, None, None, spec, None)[:3] for (_, op, _), col in zip(top.cols, spec.measures)]
+    return eng.ctx.table_sessions(table, min_hits, top.npartition, terms, rule, cols, k, cap, per_session=top.per == "session", want_hits=want_hits)
+
+
 def _mode_decoded(raw, measure, col, keys, payload, key_fields_of):
     """The column `col` of a "group_distinct" route's mode: raw = the 64 bits of the stored column `measure` names at the winning rows
     — put in that column's place among the rows' own arrays and decoded by key_fields_of(keys, payload), the result's own decoding."""
@@ -2171,6 +2212,13 @@ _WINDOW_ROUTES = (
     _Route(ExcludeRequest, "window_exclude", "device_window_exclude", "has_window_exclude", "frames", abi.WEX_MAX_COLS, call=_exclude_call,
            note=lambda top, route, spec: {"exclude": top.exclude, "frames": [list(a) for a in top.frames]}, integral=lambda item: item[1] not in ("count", "avg"),
            fits=lambda top, spec: _exclude_offsets(top, spec) is not None, value_frames=True),
+    # sessions — gaps and islands — inside partitions (sessions), one abi.Context.table_sessions call (_session_call): at most SS_MAX_COLS
+    # columns whose measures — and the change rule's marker — are underived numeric columns, a gap the device's gap term can take
+    # (_session_gap: no text, no column decoded on the host, nothing beyond 2^53 for integers kept as doubles).  Noted with "rule",
+    # "gap", "change", "cols", "per_session" and "calls"
+    _Route(SessionRequest, "sessions", "device_sessions", "has_sessions", "cols", abi.SS_MAX_COLS, call=_session_call, note=_session_note,
+           integral=lambda item: item[1] in ("sum", "min", "max", "first", "last"),      # what is summed or copied; counts, numbers and averages are what they are
+           fits=lambda top, spec: top.rule == "change" or _session_gap(top, spec) is not None, measured=_session_measured, value_frames=True),
     # ORDER BY ... LIMIT per group (top_per / numbered), abi.Context.table_window: every WindowRequest of at most SORT_MAX_KEYS terms.
     # Noted with "kind" and "per_limit"
     _Route(WindowRequest, "window", "device_window", "has_window", None, 0, call=_window_call,

@@ -844,6 +844,106 @@ def moment_finish(op, count, qy, qx, c, muy, mux):
         return np.where(qx != 0.0, slope if op == "regr_slope" else muy - slope * mux, MOMENT_NULL)
 
 
+SESSION_OPS = ("sum", "count", "min", "max", "first", "last", "avg", "number", "row")      # their positions are abi.SS_SUM .. SS_ROW
+SESSION_UNMEASURED = ("count", "number", "row")            # the ops that read no measure
+SESSION_HOST_MAX_COLS = 64                                 # the columns of one request (the device takes abi.SS_MAX_COLS a call; the rest is the host's)
+
+
+class SessionRequest(WindowRequest):
+    """Sessions (gaps and islands), travelling where a WindowRequest travels (no rank column): [0] = the limit on the whole result,
+    [1] = the PARTITION BY terms followed by the ORDER BY terms, npartition; rule "gap" — a new session where the first ORDER BY
+    column moves on by more than `gap`, an int or a float >= 0 — or "change" — where the column `marker` changes; cols = [(name of the
+    new column, op: a name of SESSION_OPS, measure column or None)] in the order the columns are appended, each over the row's whole
+    session; per None: every row, "session": one row per session — its first row."""
+    method, items_attr, served_by = "sessions", "cols", "sessioned"
+
+    def __new__(cls, k, terms, npartition, rule, gap, marker, cols, per=None):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.rule, self.gap, self.marker, self.per = str(rule), gap, None if marker is None else str(marker), per
+        self.cols = [(str(n), str(op), None if col is None else str(col)) for n, op, col in cols]
+        if self.rule not in ("gap", "change") or self.per not in (None, "session") or (self.rule == "gap") != (self.marker is None) or (self.rule == "gap") == (gap is None):
+            raise ValueError("sessions: bad rule")
+        if self.rule == "gap" and (len(self[1]) < self.npartition + 1 or isinstance(gap, bool) or not isinstance(gap, (int, float, np.integer, np.floating)) or not gap >= 0 or gap == float("inf")):
+            raise ValueError("sessions: bad gap")
+        if any(op not in SESSION_OPS or (col is None) != (op in SESSION_UNMEASURED) or (op == "row" and self.per == "session") for _, op, col in self.cols):
+            raise ValueError("sessions: bad column")
+        return self
+
+    def _with(self, terms, items):
+        return SessionRequest(self[0], terms, self.npartition, self.rule, self.gap, self.marker, items, self.per)
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, the measures and the marker through `names`."""
+        req = WindowRequest.renamed(self, terms, names)
+        req.marker = None if self.marker is None else (names or {}).get(self.marker, self.marker)
+        return req
+
+    def check_columns(self, columns):
+        WindowRequest.check_columns(self, columns)               # (the terms, the measures and the new names)
+        if self.marker is not None and self.marker not in columns:
+            raise KeyError("sessions: the result has no column %r" % self.marker)
+
+
+def sessions_request(columns, partition, order, gap=None, change=None, cols=None, per=None, k=WINDOW_ALL):
+    """The checked SessionRequest of `sessions`: partition / order as window_request takes by / order; exactly one of gap — a new
+    session where the first order column moves on by more than gap along the order: an int or a finite float >= 0 (a date column counts
+    in its yyyymmdd units) — and change — the name of a column: a new session where it changes —; cols = {new column: (op, measure) |
+    ("count",) | ("number",) | ("row",)} with op a name of SESSION_OPS, at most SESSION_HOST_MAX_COLS of them (an empty dict: the rows
+    alone); per None or "session".  columns: the result's column names when they are known (None: checked when the result is).
+    KeyError for a column the result lacks or a new column it has already, ValueError for everything else (an order column without
+    arithmetic is found when the column is known)."""
+    if (gap is None) == (change is None):
+        raise ValueError("sessions: exactly one of gap and change says where a session starts")
+    if per not in (None, "session"):
+        raise ValueError("sessions: per is None or 'session', not %r" % (per,))
+    if gap is not None:
+        if isinstance(gap, bool) or not isinstance(gap, (int, float, np.integer, np.floating)) or not np.isfinite(float(gap) if isinstance(gap, (float, np.floating)) else 0.0) or not gap >= 0:
+            raise ValueError("sessions: gap is an integer or a finite float, at least 0, not %r" % (gap,))
+        if not order:
+            raise ValueError("sessions: a gap is a difference of the first order column: order is empty")
+        gap = float(gap) if isinstance(gap, (float, np.floating)) else int(gap)
+    elif not isinstance(change, str):
+        raise ValueError("sessions: change is a column name, not %r" % (change,))
+    req = window_request(None, partition, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    cols = {} if cols is None else cols
+    _aggs_dict("sessions", cols, "(op, measure)", what="cols", empty_ok=True)
+    if len(cols) > SESSION_HOST_MAX_COLS:
+        raise ValueError("sessions: at most %d columns, not %d" % (SESSION_HOST_MAX_COLS, len(cols)))
+    out = []
+    for name, spec in cols.items():
+        _agg_spec("sessions", name, spec, "(op, measure)", lambda n: n in (1, 2), what="a column")
+        op, col = spec[0], spec[1] if len(spec) == 2 else None
+        if op not in SESSION_OPS:
+            raise ValueError("sessions: op is one of %s, not %r" % (", ".join(SESSION_OPS), op))
+        if op in SESSION_UNMEASURED and col is not None and op != "count":
+            raise ValueError("sessions: %s takes no measure" % op)
+        if op not in SESSION_UNMEASURED and not isinstance(col, str):
+            raise ValueError("sessions: %s needs a measure column" % op)
+        if op == "row" and per == "session":
+            raise ValueError("sessions: a row's number in its session is no column of one row per session")
+        out.append((name, op, None if op in SESSION_UNMEASURED else col))
+    req = SessionRequest(req[0], req[1], req.npartition, "gap" if gap is not None else "change", gap, change, out, per)
+    if columns is not None:
+        req.check_columns(columns)
+    return req
+
+
+def session_continues(v, desc, gap):
+    """Per sorted row but the first: does it continue its predecessor's session under the gap rule of include/sdqh_sort_sessions.h?  v:
+    the order column along the order, int64 or float64.  Integers by the unsigned 64-bit difference of the two order-adjacent values
+    (exact: nothing wraps); doubles by ONE IEEE addition, a = v(j) + d * (-gap), and min(a, v(j)) <= v(j - 1) <= max(a, v(j)) — -0.0
+    and +0.0 are one value, a NaN row continues only a row with the same bits."""
+    prev, cur = v[:-1], v[1:]
+    if v.dtype.kind != "f":
+        a, b = np.ascontiguousarray(prev, np.int64).view(np.uint64), np.ascontiguousarray(cur, np.int64).view(np.uint64)
+        return (a - b if desc else b - a) <= np.uint64(min(int(gap), (1 << 64) - 1))
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = cur + np.float64(gap if desc else -gap)
+        inside = (np.where(a < cur, a, cur) <= prev) & (prev <= np.where(a < cur, cur, a))
+    same = np.ascontiguousarray(prev).view(np.uint64) == np.ascontiguousarray(cur).view(np.uint64)
+    return np.where(np.isnan(cur), same, inside & ~np.isnan(prev))
+
+
 def slide_empty(default, is_f64, what="sliding"):
     """What an empty frame gives for a measure of dtype float64 (is_f64) or int64: `default`, or with None NaN / 0.  ValueError for a
     default that does not fit the dtype: a float for an int64 column, an int outside int64."""
@@ -1554,6 +1654,91 @@ class ResultSet:
         aggregate, one row per group, ordered by `by`; rollup=True: every prefix of `by` down to the grand total, with `grouping`
         (see MomentsRequest)."""
         return self.momented(moments_request(self.columns, by, aggs, rollup))
+
+    def sessioned(self, req):
+        """The rows of a SessionRequest in its order (the first req[0] of them) with its columns appended, or with per "session" one
+        row per session: what sdqh_table_sessions does on the device (include/sdqh_sort_sessions.h), on the host.  The order,
+        partitions and ties are sdqh_table_window's (_window_heads); a session starts at a partition's head and wherever the rule
+        says so about two neighbours — the gap rule by session_continues (the unsigned integer difference, the one IEEE addition), the
+        change rule by the marker's order_image.  Every column is folded per session by np.ufunc.reduceat — an integer SUM wraps, MIN /
+        MAX are the unsigned maximum of the images with a NaN left out, AVG is the sum as float64 by the count, one division — and
+        handed back to the session's rows; a double SUM is numpy's association, not the device's."""
+        self._wait()
+        req.check_columns(self.columns)
+        idx, part_head, _ = self._window_heads(req.by, req.order)
+        n = self._n
+        if req.rule == "gap":
+            name, direction = req.order[0]
+            col = self.column(name)
+            if col.dtype.kind not in "iubf":
+                raise ValueError("sessions: a gap over column %r: the order column is not numeric" % name)
+            is_fv = col.dtype.kind == "f"
+            gap = req.gap
+            if not is_fv:
+                if isinstance(gap, (float, np.floating)) and float(gap) != int(gap):
+                    raise ValueError("sessions: the gap %r over an integer column is not an integer" % (gap,))
+                gap = int(gap)
+            cont = session_continues(np.ascontiguousarray(col[idx], np.float64 if is_fv else np.int64), direction == "desc", gap) if n else np.zeros(0, bool)
+        else:
+            u = order_image(self.column(req.marker), False)[idx]
+            cont = u[1:] == u[:-1]
+        head = part_head.copy()
+        if n:
+            head[1:] |= ~cont
+        starts = np.nonzero(head)[0]
+        stops = np.append(starts[1:], n)
+        ns = len(starts)
+        sid = np.cumsum(head) - 1                                        # every position's session
+        rows = (stops - starts).astype(np.int64)
+        top = np.uint64(1) << np.uint64(63)
+        new = []
+        for name, op, col in req.cols:
+            x = None if col is None else self.column(col)[idx]
+            if x is not None and x.dtype.kind not in "iubf":
+                raise ValueError("sessions: %s of column %r: the measure is not numeric" % (op, col))
+            is_f = x is not None and x.dtype.kind == "f"
+            if x is not None:
+                x = np.ascontiguousarray(x, np.float64 if is_f else np.int64)
+            if op == "row":
+                new.append((name, (np.arange(n, dtype=np.int64) - starts[sid] + 1) if n else np.zeros(0, np.int64)))
+                continue
+            if not ns:
+                s = np.zeros(0, np.float64 if (is_f or op == "avg") else np.int64)
+            elif op == "count":
+                s = rows
+            elif op == "number":
+                at = np.arange(ns, dtype=np.int64)
+                s = at - np.maximum.accumulate(np.where(part_head[starts], at, 0)) + 1
+            elif op == "first":
+                s = x[starts]
+            elif op == "last":
+                s = x[stops - 1]
+            elif op in ("sum", "avg"):
+                with np.errstate(invalid="ignore", over="ignore"):
+                    s = np.add.reduceat(x, starts) if is_f else np.add.reduceat(x.view(np.uint64), starts).view(np.int64)
+                    if op == "avg":
+                        s = s.astype(np.float64) / rows.astype(np.float64)
+            else:                                                        # unsigned maximum of the images, reversed for MIN, NaN = 0
+                e = order_image(x, op == "min")
+                e = np.where(np.isnan(x), np.uint64(0), e) if is_f else e
+                val = np.maximum.reduceat(e, starts)
+                u = ~val if op == "min" else val
+                if is_f:
+                    s = np.where(val == 0, np.uint64(0x7FF8000000000000), np.where(u >> np.uint64(63) != 0, u ^ top, ~u)).view(np.float64)
+                else:
+                    s = (u ^ top).view(np.int64)
+            new.append((name, np.ascontiguousarray(s) if req.per == "session" else np.ascontiguousarray(s[sid])))
+        keep = (starts if req.per == "session" else np.arange(n))[:max(0, int(req[0]))]
+        cols = [c[idx[keep]] for c in self._cols]                        # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [c[:len(keep)] for _, c in new])
+
+    def sessions(self, partition, order, gap=None, change=None, cols=None, per=None):
+        """Sessions (gaps and islands) inside every group of `partition`, the rows ordered by `partition` then `order`: a new session
+        where the first order column moves on by more than `gap` (gap=...), or where the column `change` changes (change=...).  cols =
+        {new column: (op, measure) | ("count",) | ("number",) | ("row",)}, op in SESSION_OPS, each over the row's whole session:
+        "first" / "last" of the order column are the session's start and end, "number" counts the sessions of a group from 1, "row"
+        the rows of a session.  per=None: every row with its columns; per="session": one row per session, its first row."""
+        return self.sessioned(sessions_request(self.columns, partition, order, gap, change, cols, per))
 
     def sliding(self, by, order, aggs):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a sliding frame inside the row's group of `by`:

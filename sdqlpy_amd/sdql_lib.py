@@ -516,6 +516,18 @@ def sdql_compile(in_type):
             before anything is launched."""
             return _requested("moments_request", list(by) if isinstance(by, (list, tuple)) else by, aggs, rollup)
 
+        def sessions(partition, order, gap=None, change=None, cols=None, per=None):
+            """The same query finished with sessions (gaps and islands) inside every group of `partition`, the rows ordered by
+            `partition` then `order`: a new session wherever the first order column moves on by more than `gap` — an int or a float
+            >= 0; a date column counts in its yyyymmdd units — or wherever the column `change` changes; exactly one of the two.  cols =
+            {new column: (op, measure) | ("count",) | ("number",) | ("row",)}, op in "sum" / "count" / "min" / "max" / "first" / "last" /
+            "avg" over the row's WHOLE session, "number" the session's number in its group and "row" the row's number in its session,
+            both from 1, e.g. ``q3.sessions(["o_shippriority"], [("o_orderdate", "asc")], gap=1, cols={"from": ("first",
+            "o_orderdate"), "to": ("last", "o_orderdate"), "revenue_sum": ("sum", "revenue")}, per="session")(li, cu, ord)``: the runs
+            of consecutive order dates per ship priority, one row each.  per=None: every row with its columns beside it;
+            per="session": one row per session, its first row.  Names and ops are checked here, before anything is launched."""
+            return _requested("sessions_request", list(partition) if isinstance(partition, (list, tuple)) else partition, order, gap, change, cols, per)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -530,6 +542,7 @@ def sdql_compile(in_type):
         wrapper.grouping_sets = grouping_sets
         wrapper.distincts = distincts
         wrapper.moments = moments
+        wrapper.sessions = sessions
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
