@@ -96,9 +96,10 @@ class Exact:
         return v, 1.01 * eslope * abs(mux) + 2 * m * U * (self.ay + abs(slope) * self.ax) + 4 * U * (abs(muy) + abs(slope * mux))
 
 
-def check(op, got, y, x=None, what=None):
-    """Assert one computed value against the definition within its bound; returns error / bound (0 where the value is exact)."""
-    want, bound = Exact(y, x).value(op)
+def check(op, got, y, x=None, what=None, exact=None):
+    """Assert one computed value against the definition within its bound; returns error / bound (0 where the value is exact).  exact: the
+    Exact of these y (and x), where a caller checks several ops of one group."""
+    want, bound = (exact or Exact(y, x)).value(op)
     got = np.float64(got)
     if want is None:
         assert int(got.view(np.uint64)) == NULL_BITS, (what, op, got)

@@ -94,8 +94,8 @@ def _pattern(name, n, T):
     return b // 3, b
 
 
-def _symmetric(b, rng, centre):
-    """per position centre + d with the d of every run of b symmetric about 0: pairs +d, -d (and one 0 in a run of odd length)"""
+def _symmetric(b, rng, centre, amp=1 << 20):
+    """per position centre + d, |d| < amp, with the d of every run of b symmetric about 0: pairs +d, -d (and one 0 in a run of odd length)"""
     n = len(b)
     pos = np.arange(n)
     head = np.ones(n, bool)
@@ -103,7 +103,7 @@ def _symmetric(b, rng, centre):
     start = np.maximum.accumulate(np.where(head, pos, 0))
     size = np.diff(np.append(np.nonzero(head)[0], n))[np.cumsum(head) - 1]
     i = pos - start
-    d = rng.integers(-(1 << 20) + 1, 1 << 20, n)
+    d = rng.integers(-amp + 1, amp, n)
     d = np.where(i & 1, -d[np.maximum(pos - 1, 0)], d)
     d = np.where((size & 1) & (i == size - 1), 0, d)
     return (centre + d).astype(np.float64)
@@ -122,6 +122,39 @@ def _exact_columns(g, L, xs, ys, kx, ky):
         samp = lambda q: np.where(m > 1, q / (m - 1.0), nan)              # noqa: E731
         out = {"var_pop": qy / m, "var_samp": samp(qy), "covar_pop": c / m, "covar_samp": samp(c), "regr_slope": np.where(qx != 0, c / qx, nan)}
     return out, (qx, qy, c, m)
+
+
+def _check_exact_levels(g, mask, got, xs, ys, kx, ky, what):
+    """the assertions of test_exact_by_bits on one mask's columns `got` = {(op, measures): column}: bits for VAR_* / COVAR_* / REGR_SLOPE,
+    STDDEV within 1 ulp of the square root of the same call's variance, CORR symmetric by bits and |corr| <= 1, NULL where the header
+    says so, and CORR / REGR_INTERCEPT of at most 40 groups per level against exact rationals"""
+    for L, sl in _level_slices(g, mask):
+        want, (qx, qy, c, m) = _exact_columns(g, L, xs, ys, kx, ky)
+        for op in ("var_pop", "var_samp"):
+            assert (ref.bits(got[(op, MY)][sl]) == ref.bits(want[op])).all(), (what, L, op)
+        for op in ("covar_pop", "covar_samp", "regr_slope"):
+            assert (ref.bits(got[(op, MY + MX)][sl]) == ref.bits(want[op])).all(), (what, L, op)
+        assert (ref.bits(got[("var_pop", MX)][sl]) == ref.bits(qx / m)).all() and (ref.bits(got[("covar_pop", MX + MX)][sl]) == ref.bits(qx / m)).all(), (what, L)
+        with np.errstate(all="ignore"):
+            for op, var in (("stddev_pop", "var_pop"), ("stddev_samp", "var_samp")):      # within 1 ulp of the square root of the same call's variance
+                s, v = got[(op, MY)][sl], got[(var, MY)][sl]
+                dead = ref.bits(v) == NULL
+                assert (ref.bits(s)[dead] == NULL).all() and (np.abs(ref.bits(s)[~dead].astype(np.int64) - ref.bits(np.sqrt(v[~dead])).astype(np.int64)) <= 1).all(), (what, L, op)
+            corr, back = got[("corr", MY + MX)][sl], got[("corr", MX + MY)][sl]
+            assert (ref.bits(corr) == ref.bits(back)).all(), (what, L, "corr swapped")
+            flat = (qx == 0) | (qy == 0)
+            assert (ref.bits(corr)[flat] == NULL).all() and (np.abs(corr[~flat]) <= 1.0).all(), (what, L)
+            icpt = got[("regr_intercept", MY + MX)][sl]
+            assert (ref.bits(icpt)[qx == 0] == NULL).all(), (what, L)
+        live = np.nonzero(~flat)[0]
+        for j in live[::max(1, len(live) // 40)]:                # a sample against exact rationals: 4 ulp each
+            C_, QX, QY = Fraction(int(c[j])), Fraction(int(qx[j])), Fraction(int(qy[j]))
+            exact_corr = float(C_) / (np.sqrt(np.float64(qx[j])) * np.sqrt(np.float64(qy[j])))
+            assert abs(corr[j] - exact_corr) <= 4 * np.spacing(abs(exact_corr)), (what, L, j, corr[j], exact_corr)
+            exact_icpt = Fraction(ky) - C_ / QX * kx
+            scale = abs(float(ky)) + abs(float(C_ / QX * kx))
+            assert abs(Fraction(float(icpt[j])) - exact_icpt) <= 4 * np.spacing(scale), (what, L, j, icpt[j], float(exact_icpt))
+            assert float(Fraction(int(qy[j])) / int(m[j])) == got[("var_pop", MY)][sl][j] and float(C_ / QX) == got[("regr_slope", MY + MX)][sl][j]
 
 
 @pytest.mark.parametrize("pattern", PATTERNS)
@@ -156,33 +189,7 @@ def test_exact_by_bits(hip_engine, pattern):
                 sib = ctx.table_grouping_sets_count(t, 0, terms, mask)
                 mine = ctx.table_group_moments_count(t, 0, terms, mask, aggs_a)
                 assert mine[0] == sib[0] == len(r[0]) and (mine[1] == sib[1]).all() and (sib[1] == r[5]).all(), what
-                for L, sl in _level_slices(g, mask):
-                    want, (qx, qy, c, m) = _exact_columns(g, L, xs, ys, kx, ky)
-                    for op in ("var_pop", "var_samp"):
-                        assert (ref.bits(got[(op, MY)][sl]) == ref.bits(want[op])).all(), (what, L, op)
-                    for op in ("covar_pop", "covar_samp", "regr_slope"):
-                        assert (ref.bits(got[(op, MY + MX)][sl]) == ref.bits(want[op])).all(), (what, L, op)
-                    assert (ref.bits(got[("var_pop", MX)][sl]) == ref.bits(qx / m)).all() and (ref.bits(got[("covar_pop", MX + MX)][sl]) == ref.bits(qx / m)).all(), (what, L)
-                    with np.errstate(all="ignore"):
-                        for op, var in (("stddev_pop", "var_pop"), ("stddev_samp", "var_samp")):      # within 1 ulp of the square root of the same call's variance
-                            s, v = got[(op, MY)][sl], got[(var, MY)][sl]
-                            dead = ref.bits(v) == NULL
-                            assert (ref.bits(s)[dead] == NULL).all() and (np.abs(ref.bits(s)[~dead].astype(np.int64) - ref.bits(np.sqrt(v[~dead])).astype(np.int64)) <= 1).all(), (what, L, op)
-                        corr, back = got[("corr", MY + MX)][sl], got[("corr", MX + MY)][sl]
-                        assert (ref.bits(corr) == ref.bits(back)).all(), (what, L, "corr swapped")
-                        flat = (qx == 0) | (qy == 0)
-                        assert (ref.bits(corr)[flat] == NULL).all() and (np.abs(corr[~flat]) <= 1.0).all(), (what, L)
-                        icpt = got[("regr_intercept", MY + MX)][sl]
-                        assert (ref.bits(icpt)[qx == 0] == NULL).all(), (what, L)
-                    live = np.nonzero(~flat)[0]
-                    for j in live[::max(1, len(live) // 40)]:                # a sample against exact rationals: 4 ulp each
-                        C_, QX, QY = Fraction(int(c[j])), Fraction(int(qx[j])), Fraction(int(qy[j]))
-                        exact_corr = float(C_) / (np.sqrt(np.float64(qx[j])) * np.sqrt(np.float64(qy[j])))
-                        assert abs(corr[j] - exact_corr) <= 4 * np.spacing(abs(exact_corr)), (what, L, j, corr[j], exact_corr)
-                        exact_icpt = Fraction(ky) - C_ / QX * kx
-                        scale = abs(float(ky)) + abs(float(C_ / QX * kx))
-                        assert abs(Fraction(float(icpt[j])) - exact_icpt) <= 4 * np.spacing(scale), (what, L, j, icpt[j], float(exact_icpt))
-                        assert float(Fraction(int(qy[j])) / int(m[j])) == got[("var_pop", MY)][sl][j] and float(C_ / QX) == got[("regr_slope", MY + MX)][sl][j]
+                _check_exact_levels(g, mask, got, xs, ys, kx, ky, what)
         finally:
             t.free()
     if pattern == "a group over three tiles":

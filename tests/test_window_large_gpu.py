@@ -1,5 +1,5 @@
-"""The window entry points past 256 tiles on the MI355X (run with -m gpu): sdqh_table_window, _window_agg, _window_slide, _window_range
-and _window_quantile against numpy at the sizes at which a thread of the one-workgroup tile scans (k_win_scan, k_wagg_scan, k_wsl_scan in
+"""The window entry points past 256 tiles on the MI355X (run with -m gpu): sdqh_table_window, _window_agg, _window_slide, _window_range,
+_window_quantile and _window_exclude against numpy at the sizes at which a thread of the one-workgroup tile scans (k_win_scan, k_wagg_scan, k_wsl_scan in
 both directions, k_wagg_next, k_sort_scan over tile_kept) folds MORE THAN ONE tile, k_wrg_upper's stride loop iterates more than once
 and the fold tree grows levels above cap = 131072.  With T = 512 positions per tile and W = 256 threads in the scan workgroup, thread t
 takes the tiles [t * per, (t + 1) * per), per = ceil(ntiles / W); every other window test stops at 137 tiles, where per = 1.
@@ -11,6 +11,14 @@ takes the tiles [t * per, (t + 1) * per), per = ceil(ntiles / W); every other wi
     2 W T + 1     513    3    524288
     2 W T + T + 1 514    3    524288  per does not divide the tiles; 257 live nodes at k_wrg_upper's first level
     2 W T + 2 T   514    3    524288  (ranges only) ... the 257th of which lies wholly below n, so that a query reads it
+
+    entry point            W T + 1 and 2 W T + T + 1, six patterns         the other four sizes
+    _window                test_ranks                                      test_one_call_per_entry_point
+    _window_agg            test_frames                                     "
+    _window_slide          test_slides                                     "
+    _window_range          test_ranges (and 2 W T + 2 T)                   "
+    _window_quantile       test_quantiles                                  "
+    _window_exclude        test_exclusions: 24 frames, 3 units x 4 ways    test_exclusions_one_call (SWALLOW)
 
 Everything runs at W T + 1 and at 2 W T + T + 1 (262 657) on six partition patterns; the other four sizes take one call of four columns
 per entry point.  Beside four patterns of test_window_gpu there are two of this file's own, because test_window_gpu's long tie run
@@ -28,7 +36,8 @@ CPU time of the references at 262 657 rows, "every row its own" (262 657 partiti
 and its 31 columns 0.4 s, Quant's 50 columns 0.25 s, Slid's 56 slides 0.7 s; the slowest is Ranged's 56 ranges, 0.8 s — and 2.4 s on
 "one partition", whose 220 000 distinct order values pass through Python integers once per bounded side of a frame.  A table, its
 staged rows and their Ranked are built once per (pattern, size) and shared; Framed, Slid, Ranged and Quant each sort the rows once more
-when a test makes one (the 0.1 s of Ranked above)."""
+when a test makes one (the 0.1 s of Ranked above).  Excluded (test_window_exclude_gpu's, a Ranged) and its 24 columns: 0.9 s on "heavy
+ties" up to 2.2 s on "one partition" (test_large_patterns_cpu prints them)."""
 import numpy as np
 import pytest
 
@@ -38,6 +47,7 @@ from test_window_agg_gpu import MEASURES, Framed, _agg, _all_combinations, _raw 
 from test_window_slide_gpu import NAN_BITS, Slid, _bits, _last_of
 from test_window_range_gpu import RM, Ranged, _order_values, _range_table
 from test_window_quantile_gpu import Quant, _col, _column_lists, _same_col, _same_rows
+from test_window_exclude_gpu import AVG, CUR, GROUP, NO, TIES, Excluded, _col_lists, _frames, _is_f64 as _ex_is_f64, _raw as _raw_exclude
 
 pytestmark = pytest.mark.gpu
 
@@ -152,6 +162,12 @@ def _structure(pattern, ref, T):
         assert any(ref.part_head[t * L:t * L + T].any() for t in range(1, 15))      # ... and heads in the first tile of a run
 
 
+def _ranged_columns(pattern, part, value, rng):
+    """-> (order values, descending?, doubles, integers) of the range tests' table of a pattern"""
+    order = value.astype(np.int64) if pattern in (SWALLOW, "heavy ties") else _order_values("gaps", part, rng)
+    return order, pattern in ("runs", SWALLOW), rng.integers(-50, 50, len(part)).astype(np.float64), rng.integers(-1000, 1000, len(part))
+
+
 # ---- shared tables -----------------------------------------------------------------------------------------------------------------
 class Case:
     """one table of a (pattern, size), its staged rows and their Ranked, built once and shared by the tests of the module"""
@@ -161,10 +177,9 @@ class Case:
         part, value, hits = _large_pattern(pattern, n, T, rng)
         self.ctx, self.pattern, self.n, self.T = ctx, pattern, n, T
         if ranged:                                                         # the range test's table: payloads part, order, a double, an integer
-            order = value.astype(np.int64) if pattern in (SWALLOW, "heavy ties") else _order_values("gaps", part, rng)
-            self.desc = pattern in ("runs", SWALLOW)
+            order, self.desc, dbls, ints = _ranged_columns(pattern, part, value, rng)
             self.terms, self.min_hits = [(P, 0, False, False), (P, 1, self.desc, False)], 0
-            self.t = _range_table(ctx, part, order, rng.integers(-50, 50, n).astype(np.float64), rng.integers(-1000, 1000, n))
+            self.t = _range_table(ctx, part, order, dbls, ints)
         else:
             self.terms, self.min_hits = TERMS, 1
             self.t = _table(ctx, part, value, hits)
@@ -455,6 +470,100 @@ def test_one_call_per_entry_point(cases, pattern, size):
     r = cases(pattern, size, ranged=True)
     ranges = [(SUM,) + RM[1] + (GRP, -2, 1, 0), (SUM,) + RM[0] + (VAL, -T, T, 0), (MAX,) + RM[1] + (VAL, None, None, 0), (COUNT,) + RM[2] + (VAL, 0, None, 0)]
     assert _check_ranges(r, Ranged(r.rows, r.terms, 1), [ranges]) == 4
+
+
+# 6b. exclusions ----------------------------------------------------------------------------------------------------------------------------
+def _query_heights(a, b, cap):
+    """Per query [a, b] of the fold tree over cap leaves the set, as a bit mask, of the heights h whose nodes (2^h leaves each) the
+    bottom-up walk takes: p = cap + a, q = cap + b + 1; while p < q: an odd p takes node p and steps right, an odd q steps left and
+    takes node q; both halve.  Restated from include/sdqh_sort_exclude.h; tile nodes have height log2 T, k_wrg_upper's lie above."""
+    p, q = np.asarray(a, np.int64) + cap, np.asarray(b, np.int64) + cap + 1
+    mask, h = np.zeros(len(p), np.int64), 0
+    while (p < q).any():
+        live = p < q
+        left, right = live & (p & 1 == 1), live & (q & 1 == 1)
+        mask |= (left | right).astype(np.int64) << h
+        p, q = (p + left) >> 1, (q - right) >> 1
+        h += 1
+    return mask
+
+
+def _exclude_reach(ref, T):
+    """On SWALLOW: some row's GROUP / TIES exclusion leaves a left and a right piece whose tree queries, together, take a node of every
+    level of k_wrg_upper from which a node fits between the ends of the longest partition — a frame never leaves its partition, so no
+    query can take a node that does not — and no higher one; among them the first level above the tiles, the one with 257 live nodes
+    at 262 657 rows.  (The levels above that are reached by "one partition": asserted there.)  On the reference's piece ends."""
+    n = ref.n
+    cap = _geometry(n, T)[2]
+    base = T.bit_length() - 1                                               # the tiles' height
+    longest = int(np.argmax(ref.end - ref.start))
+    lo, hi = int(ref.start[longest]), int(ref.end[longest])
+    fits = [up for up in range(1, len(_upper_levels(n, T)) + 1) if (-(-lo // (T << up)) + 1) * (T << up) <= hi + 1]
+    assert fits and fits == list(range(1, len(fits) + 1)), fits
+    need = sum(1 << (base + up) for up in fits)
+    upper = sum(1 << (base + up) for up in range(1, len(_upper_levels(n, T)) + 1))
+    for exclude in (GROUP, TIES):
+        (p1, a1, b1), _, (p3, a3, b3) = ref.pieces((SUM,) + RM[0] + (abi.WEX_ROWS, None, None, 0, exclude))[0]
+        both = np.nonzero(p1 & p3)[0]
+        assert len(both) > T
+        took = _query_heights(a1[both], b1[both], cap) | _query_heights(a3[both], b3[both], cap)
+        assert ((took & upper) == need).any(), (exclude, fits)
+    return fits
+
+
+def _check_exclusions(c, ref, lists, limit=ALL):
+    ctx, t, rows, n = c.ctx, c.t, c.rows, c.n
+    done, m = 0, min(limit, n)
+    for cols in lists:
+        got = ctx.table_window_exclude(t, 0, 1, c.terms, cols, limit, m, want_hits=False)
+        _same(got, rows, ref.order[:m], (c.pattern, n, cols))
+        assert len(got[4]) == len(cols)
+        for a, col in zip(got[4], cols):
+            assert a.dtype == (np.float64 if _ex_is_f64(col) else np.int64) and len(a) == m, (c.pattern, n, col)
+            want = ref.want_col(col)[:m]
+            bad = np.nonzero(_bits(a) != want)[0]
+            assert len(bad) == 0, (c.pattern, n, col, limit, "first slot", bad[:5], "tile", bad[:5] // c.T, "thread run", bad[:5] // (_geometry(n, c.T)[1] * c.T),
+                                   _bits(a)[bad[:5]], want[bad[:5]])
+            done += 1
+    return done
+
+
+@pytest.mark.parametrize("size", FULL)
+@pytest.mark.parametrize("pattern", PATTERNS)
+def test_exclusions(cases, pattern, size):
+    """test_window_exclude_gpu's 24 frames — offsets around the wave, the tile and the table, unbounded sides, frames that do not hold
+    their own row — in all three units and under all four exclusions, four columns to a call; k_wex_ties takes the end of a tie run
+    from k_wagg_next's tnext, several thread runs away on SWALLOW; k_wex_fold asks the tree once per piece."""
+    c = cases(pattern, size, ranged=True)
+    ref = Excluded(c.rows, c.terms, 1)
+    frames = _frames(c.n, c.T)
+    lists = _col_lists(frames, PATTERNS.index(pattern) + FULL.index(size))
+    here = [col for cols in lists for col in cols]
+    assert [(col[5], col[6]) for col in here] == frames and {(col[4], col[8]) for col in here} == {(u, x) for u in (VAL, GRP, abi.WEX_ROWS) for x in (NO, CUR, GROUP, TIES)}
+    assert any(lo is not None and hi is not None and (lo > 0 or hi < 0) for lo, hi in frames)      # frames that do not hold their own row
+    assert _check_exclusions(c, ref, lists) == 24
+    assert _raw_exclude(c.ctx, c.t, 0, 1, c.terms, lists[0], ALL, 0) == (abi.OK, c.n)
+    assert _check_exclusions(c, ref, lists[:1], limit=W * c.T + 1) == 4
+    if pattern == SWALLOW:
+        far = (ref.tie_b - ref.pos) // c.T                                  # tiles between a row and its tie run's end
+        assert far.max() >= 4 * _geometry(c.n, c.T)[1]
+        fits = _exclude_reach(ref, c.T)
+        assert 1 in fits and (size != "2*W*T+T+1" or _upper_levels(c.n, c.T)[0][0] == 257)
+    if pattern == "one partition":                                          # pieces long enough for every level below the two highest
+        (p1, a1, b1), _, (p3, a3, b3) = ref.pieces((SUM,) + RM[0] + (abi.WEX_ROWS, None, None, 0, CUR))[0]
+        cap, base, ups = _geometry(c.n, c.T)[2], c.T.bit_length() - 1, len(_upper_levels(c.n, c.T))
+        took = np.bitwise_or.reduce(np.where(p1, _query_heights(a1, b1, cap), 0) | np.where(p3, _query_heights(a3, b3, cap), 0))
+        assert all((took >> (base + up)) & 1 for up in range(1, ups - 1)), bin(took)
+
+
+@pytest.mark.parametrize("size", LIGHT)
+def test_exclusions_one_call(cases, size):
+    """a double sum without the row, an integer maximum without its tie run, an average with the row alone of its run, a count"""
+    c = cases(SWALLOW, size, ranged=True)
+    T = c.T
+    cols = [(SUM,) + RM[0] + (abi.WEX_ROWS, -T, T, 0, CUR), (MAX,) + RM[1] + (GRP, None, 1, -1, GROUP), (AVG,) + RM[0] + (VAL, -2, None, NAN_BITS, TIES),
+            (COUNT,) + RM[2] + (abi.WEX_ROWS, None, None, 0, GROUP)]
+    assert _check_exclusions(c, Excluded(c.rows, c.terms, 1), [cols]) == 4
 
 
 # 7. general doubles -----------------------------------------------------------------------------------------------------------------------
