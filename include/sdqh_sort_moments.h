@@ -11,8 +11,8 @@
  * SDQH_ERR_OVERFLOW with the needed count, SDQH_ERR_INVALID before SDQH_ERR_UNSUPPORTED, "nothing written on an error, *out_n
  * included" and the empty selection's 0 rows are sdqh_table_grouping_sets', declared in sdqh_sort_groups.h, word for word.
  *
- * Not here: moments over window frames, third and fourth moments, weighted moments, text measures, more than SDQH_GM_MAX_AGGS
- * aggregates per call, and the multi-GPU runner. */
+ * Not here: moments over window frames (they are sdqh_sort_wmoments.h's, the thirteenth extension), third and fourth moments,
+ * weighted moments, text measures, more than SDQH_GM_MAX_AGGS aggregates per call, and the multi-GPU runner. */
 #ifndef SDQH_SORT_MOMENTS_H
 #define SDQH_SORT_MOMENTS_H
 

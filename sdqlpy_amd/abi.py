@@ -81,6 +81,10 @@ SESSIONS_EXPORTS = ["sdqh_table_sessions", "sdqh_sessions_geometry"]
 SS_GAP, SS_CHANGE = 0, 1
 SS_SUM, SS_COUNT, SS_MIN, SS_MAX, SS_FIRST, SS_LAST, SS_AVG, SS_NUMBER, SS_ROW = range(9)      # 0..5 are the slides' ops, 6 is WEX_AVG
 SS_MAX_COLS = 4
+# ... and its thirteenth (include/sdqh_sort_wmoments.h, Library.has_window_moments): the second moments over window frames — the GM_* ops
+# over ROWS / RANGE / GROUPS frames, merged (n, S, Q, C) states in a position-aligned tree
+WINDOW_MOMENTS_EXPORTS = ["sdqh_table_window_moments", "sdqh_window_moments_geometry"]
+WM_MAX_COLS = 4
 # all of them: Library flag -> (exports: the call, then its geometry; header; the extension's name in messages; the flag it builds on)
 WINDOW_EXTENSIONS = {
     "has_window": (WINDOW_EXPORTS, "sdqh_sort_window.h", "window", "has_sort_terms"),
@@ -93,6 +97,7 @@ WINDOW_EXTENSIONS = {
     "has_group_distinct": (GROUP_DISTINCT_EXPORTS, "sdqh_sort_distinct.h", "group distinct", "has_grouping_sets"),
     "has_group_moments": (GROUP_MOMENTS_EXPORTS, "sdqh_sort_moments.h", "group moments", "has_grouping_sets"),
     "has_sessions": (SESSIONS_EXPORTS, "sdqh_sort_sessions.h", "sessions", "has_grouping_sets"),
+    "has_window_moments": (WINDOW_MOMENTS_EXPORTS, "sdqh_sort_wmoments.h", "window moments", "has_window_exclude"),
 }
 # the HIP library's extrema extension (include/sdqh_extrema.h), bound when present like the ordering extension: a library without
 # these symbols (the CPU implementation) has no MIN / MAX — Library.has_extrema is False and the engine refuses smin / smax up front
@@ -217,6 +222,14 @@ def _marshal_moment_aggs(aggs):
         if len(a) > 4:
             arr[i].kind2, arr[i].index2, arr[i].is_f64_2 = int(a[4]), int(a[5]), 1 if a[6] else 0
     return arr
+
+
+class WindowMoment(C.Structure):
+    """sdqh_window_moment: an op (GM_*), its two measures as a MomentAgg names them (Y, then X), and the frame as a WindowExclude gives
+    it: the unit (WRANGE_VALUE / WRANGE_GROUPS / WEX_ROWS), the unbounded-side flags and the signed offsets."""
+    _fields_ = [("op", C.c_int32), ("kind", C.c_int32), ("index", C.c_int32), ("is_f64", C.c_int32),
+                ("kind2", C.c_int32), ("index2", C.c_int32), ("is_f64_2", C.c_int32), ("unit", C.c_int32), ("flags", C.c_int32), ("_pad", C.c_int32),
+                ("lo", C.c_int64), ("hi", C.c_int64)]
 
 
 class SessionRule(C.Structure):
@@ -1499,6 +1512,26 @@ class Context:
         what the tests size their cases from."""
         return self._window_geometry("has_window_exclude", 2)
 
+    def table_window_moments(self, table, min_hits, npartition, terms, cols, limit, capacity, want_hits=True):
+        """Second moments over window frames (include/sdqh_sort_wmoments.h): terms and npartition as table_window takes them; cols:
+        [(op, kind, index, is_f64, kind2, index2, is_f64_2, unit, lo, hi)] — op one of GM_*, the first measure Y, the second X (GM_VAR_* /
+        GM_STDDEV_* read Y alone), the frame as table_window_exclude takes it: unit WRANGE_VALUE / WRANGE_GROUPS / WEX_ROWS per column,
+        lo / hi signed along the order (None: unbounded; floats only for a VALUE column over a double term).  Every selected row is
+        kept; the first min(limit, n) in sorted order.  Returns (keys, payload, values, hits, cols) — cols one float64 array per
+        column, NaN where SQL has NULL."""
+        self._need("has_window_moments", "table_window_moments")
+        arr = (WindowMoment * max(1, len(cols)))()
+        for i, (op, kind, index, is_f64, kind2, index2, is_f64_2, unit, lo, hi) in enumerate(cols):
+            arr[i].op, arr[i].kind, arr[i].index, arr[i].is_f64 = int(op), int(kind), int(index), 1 if is_f64 else 0
+            arr[i].kind2, arr[i].index2, arr[i].is_f64_2, arr[i].unit = int(kind2), int(index2), 1 if is_f64_2 else 0, int(unit)
+            arr[i].flags = (WRANGE_LO_UNBOUNDED if lo is None else 0) | (WRANGE_HI_UNBOUNDED if hi is None else 0)
+            arr[i].lo, arr[i].hi = _range_offset(lo, "table_window_moments"), _range_offset(hi, "table_window_moments")
+        return self._window_columns_call("table_window_moments", table, min_hits, npartition, terms, arr, len(cols), (), limit, capacity, want_hits, True, [True] * len(cols))
+
+    def window_moments_geometry(self):
+        """Sorted positions per tile of sdqh_table_window_moments' passes: what the tests size their cases from."""
+        return self._window_geometry("has_window_moments", 1)
+
     def table_window_quantile(self, table, min_hits, npartition, terms, cols, per_limit, limit, capacity, want_hits=True, want_cols=True):
         """Functions of the partition's size beside the ordered entries: terms and npartition as table_window takes them; cols: [(fn,
         kind, index, is_f64, arg, p, empty)] — fn one of WQ_NTILE (arg = b >= 1) / WQ_PERCENT_RANK / WQ_CUME_DIST / WQ_NTH (arg = k != 0,
@@ -1935,6 +1968,10 @@ class Library:
             L.sdqh_table_sessions.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.sdqh_sessions_geometry.argtypes = [C.c_void_p, C.c_void_p]
+        if self.has_window_moments:
+            L.sdqh_table_window_moments.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.sdqh_window_moments_geometry.argtypes = [C.c_void_p, C.c_void_p]
         if self.has_window_quantile:
             L.sdqh_table_window_quantile.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -40,7 +40,8 @@ GROUPS_HEADER = os.path.join(INCLUDE, "sdqh_sort_groups.h")
 DISTINCT_HEADER = os.path.join(INCLUDE, "sdqh_sort_distinct.h")
 MOMENTS_HEADER = os.path.join(INCLUDE, "sdqh_sort_moments.h")
 SESSIONS_HEADER = os.path.join(INCLUDE, "sdqh_sort_sessions.h")
-UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER, SESSIONS_HEADER], "sdqh_extrema.hip": HIP_HEADERS[:3] + [EXTREMA_HEADER]}
+WMOMENTS_HEADER = os.path.join(INCLUDE, "sdqh_sort_wmoments.h")
+UNIT_HEADERS = {"sdqh_x.hip": HIP_HEADERS, "sdqh_sort.hip": HIP_HEADERS[:3] + [SORT_HEADER, SORT_TERMS_HEADER, WINDOW_HEADER, FRAMES_HEADER, SLIDE_HEADER, RANGE_HEADER, QUANTILE_HEADER, EXCLUDE_HEADER, GROUPS_HEADER, DISTINCT_HEADER, MOMENTS_HEADER, SESSIONS_HEADER, WMOMENTS_HEADER], "sdqh_extrema.hip": HIP_HEADERS[:3] + [EXTREMA_HEADER]}
 HIP_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
     "-ffp-contract=off",          # keep the reference's a*(1.0-b) association: no FMA contraction

@@ -150,6 +150,14 @@
 //                     per row: SUM / COUNT / MIN / MAX over sessions as over partitions; every row takes the value at its session's end
 //   k_sort_bins, k_wagg_tiles / k_wagg_scan / k_gs_run, k_ss_sessions
 //                     per session: the count to the host, the folds kept in the session's slot as a level of GROUPS — see the section
+//   WMOMENTS          in their place (STEP_WMOMENTS).  sdqh_table_window_moments (include/sdqh_sort_wmoments.h) takes the nine ops of MOMENTS
+//                     over ROWS, VALUE and GROUP frames.  Behind k_win_heads, k_win_scan, k_wsl_rows, k_wagg_next, the ranges' k_win_rank
+//                     (a GROUPS column) and k_wrg_stage (the partitions' ends and the frames' keys alone):
+//
+//   k_wmo_stage       per position every distinct measure as a double: the leaves of the component trees (S, Q per measure, C per pair)
+//   k_wmo_tiles / k_wmo_upper
+//                     the trees' nodes: merged (n, S, Q, C) states over aligned blocks of 2^h positions, n never stored
+//   k_wmo_fold        per row and column the frame's ends, the iterative query over the states, the op's formula — see the section
 //
 // What is sorted is a permutation of the gathered positions; a pass reads its digit through it (8-byte gathers from arrays that
 // stay in L2 / Infinity Cache at the sizes a query result has) and moves 4 bytes per entry, whatever the number of sort columns.
@@ -170,6 +178,7 @@
 #include "sdqh_sort_distinct.h"
 #include "sdqh_sort_moments.h"
 #include "sdqh_sort_sessions.h"
+#include "sdqh_sort_wmoments.h"
 
 using namespace sdqh_host;
 
@@ -1831,6 +1840,209 @@ __global__ __launch_bounds__(TPB) void k_mo_finish(DevStage st, DevMoAggs mo, De
     }
 }
 
+// ---- second moments over window frames (sdqh_table_window_moments) ------------------------------------------------------------------
+// VAR / STDDEV / COVAR / CORR / REGR over the frame [l, r] of every row (include/sdqh_sort_wmoments.h).  A frame per row rules the two
+// passes of the section above out — O(n * width) — so the fold here is the one that section put off: merged states.  A state over a
+// run of positions is (n, S, Q) per measure and C per measure pair; wmo_delta / wmo_weight / wmo_second are the header's merge, and
+// every kernel below goes through them, so a node and a query associate and round alike wherever they are computed.  The states lie
+// in component trees of the ranges' layout (tree[slot * tstride + node], leaves at cap + r): S of distinct measure k in slot 2k, its
+// Q in slot 2k + 1, C of distinct pair c in slot 2 nmeas + c.  A node of level h covers 2^h positions — its n is never stored — and
+// one that straddles n or a partition's end is never read by a query: what is folded into it is zeros or a neighbour's rows.
+//   k_wmo_stage       the leaves: perm -> refs -> stage once per row, every distinct measure as a double into its S leaf, +0.0 into
+//                     the Q and C leaves (pend / vkey / gkey are k_wrg_stage's, launched over an image of COUNT ranges)
+//   k_wmo_tiles       a wave per tile, k_wrg_tiles' shape: three levels in a lane's registers, six by shuffles; a measure travels as
+//                     (S, Q), a pair as (Sx, Sy, C) — its sums are added again, to the same bits as the measures' trees hold
+//   k_wmo_upper       the levels above the tiles, a workgroup per measure; launched again, a workgroup per pair, once the S trees stand
+//   k_wmo_fold        per row and column the frame's ends (wex_ends), the iterative query carrying the level, the finish
+constexpr int WMO_MAX_MEAS = 2 * SDQH_WM_MAX_COLS, WMO_MAX_PAIRS = SDQH_WM_MAX_COLS;
+struct DevWmoCol { int32_t op, my, mx, pair; };                       // the measures Y and X among the distinct ones; pair: its C tree (-1: none — one measure, or my == mx: my's Q)
+struct DevWmos {
+    DevWranges rg;                                                    // the frames, as an image of COUNT ranges (a[c].unit may be SDQH_WEX_ROWS: lo / hi clamped to [-n, n])
+    DevSortKey sk[WMO_MAX_MEAS];                                      // the distinct measures (desc unused)
+    int32_t pi[WMO_MAX_PAIRS], pj[WMO_MAX_PAIRS];                     // the distinct pairs, pi < pj
+    DevWmoCol a[SDQH_WM_MAX_COLS];
+    int32_t nmeas, npairs;
+};
+static_assert(SDQH_WM_MAX_COLS == SDQH_WRANGE_MAX_AGGS, "the columns of a moments call are the ranges of its image");
+
+// merge(a, b), a's positions first: the difference of the means, the weight, and a second-order component (Q: dx = dy)
+__device__ __forceinline__ double wmo_delta(double na, double sa, double nb, double sb) { return sb / nb - sa / na; }
+__device__ __forceinline__ double wmo_weight(double na, double nb) { return (na * nb) / (na + nb); }
+__device__ __forceinline__ double wmo_second(double a, double b, double dx, double dy, double w) { return (a + b) + (dx * dy) * w; }
+
+// 1. a wave per tile: the leaves of every component tree
+__global__ __launch_bounds__(TPB) void k_wmo_stage(DevStage st, DevWmos mo, const uint32_t* __restrict__ refs, const uint32_t* __restrict__ perm, uint32_t n, size_t tstride, uint64_t cap,
+                                                  uint64_t* __restrict__ tree, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    for (uint64_t r = r0 + (uint32_t)lane_id(); r < r1; r += WAVE) {
+        const uint32_t g = perm ? perm[r] : (uint32_t)r;
+        const bool ok = g < n;                                           // (a permutation of [0, n): always)
+        const int64_t idx = ok ? (int64_t)refs[g] : 0;
+        const uint32_t hits = ok && st.shits ? st.shits[idx] : 0u;
+        for (int k = 0; k < mo.nmeas; ++k) {
+            tree[(size_t)(2 * k) * tstride + cap + r] = mo_bits(ok ? mo_value(mo.sk[k], st, idx, hits) : 0.0);
+            tree[(size_t)(2 * k + 1) * tstride + cap + r] = mo_bits(0.0);
+        }
+        for (int c = 0; c < mo.npairs; ++c) tree[(size_t)(2 * mo.nmeas + c) * tstride + cap + r] = mo_bits(0.0);
+    }
+}
+// 2. the lowest nine levels, a wave per tile (k_wrg_tiles' walk: lane i takes the leaves [8i, 8i + 8), past n a zero; the lane whose
+// number is a multiple of 2^k holds the node over lanes [lane, lane + 2^k)).  unit u < nmeas: measure u's S and Q; above: a pair's C.
+__global__ __launch_bounds__(TPB) void k_wmo_tiles(DevWmos mo, uint32_t n, size_t tstride, uint64_t cap, uint64_t* __restrict__ tree, uint32_t ntiles) {
+    uint32_t w; uint64_t r0, r1;
+    if (!tile_range(ntiles, n, w, r0, r1)) return;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint64_t p0 = r0 + 8ull * lane;                                // this lane's first leaf
+    for (int u = 0; u < mo.nmeas + mo.npairs; ++u) {
+        const bool pair = u >= mo.nmeas;
+        const int ki = pair ? mo.pi[u - mo.nmeas] : u, kj = pair ? mo.pj[u - mo.nmeas] : u;
+        const uint64_t* __restrict__ li = tree + (size_t)(2 * ki) * tstride + cap;      // the leaves of S_i, S_j
+        const uint64_t* __restrict__ lj = tree + (size_t)(2 * kj) * tstride + cap;
+        uint64_t* __restrict__ ts = tree + (size_t)(2 * ki) * tstride;                  // where S (a measure alone) and the second-order component go
+        uint64_t* __restrict__ t2 = tree + (size_t)(pair ? 2 * mo.nmeas + (u - mo.nmeas) : 2 * ki + 1) * tstride;
+        double si[8], sj[8], q[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const bool in = p0 + i < r1; si[i] = in ? mo_f64(li[p0 + i]) : 0.0; sj[i] = in ? mo_f64(lj[p0 + i]) : 0.0; q[i] = 0.0; }
+#pragma unroll
+        for (int h = 1; h <= 3; ++h) {
+            const double nh = (double)(1u << (h - 1));                   // a child's rows
+            const double wt = wmo_weight(nh, nh);
+#pragma unroll
+            for (int i = 0; i < (8 >> h); ++i) {
+                const double di = wmo_delta(nh, si[2 * i], nh, si[2 * i + 1]), dj = wmo_delta(nh, sj[2 * i], nh, sj[2 * i + 1]);
+                const double nq = wmo_second(q[2 * i], q[2 * i + 1], di, dj, wt);
+                const double ni = si[2 * i] + si[2 * i + 1], nj = sj[2 * i] + sj[2 * i + 1];
+                si[i] = ni; sj[i] = nj; q[i] = nq;
+                const uint64_t at = (cap >> h) + (p0 >> h) + (uint64_t)i;
+                if (!pair) ts[at] = mo_bits(ni);
+                t2[at] = mo_bits(nq);
+            }
+        }
+        double xi = si[0], xj = sj[0], xq = q[0];
+#pragma unroll
+        for (int k = 1; k <= WRG_TILE_LEVELS - 3; ++k) {
+            const double oi = __shfl_down(xi, 1u << (k - 1), WAVE), oj = __shfl_down(xj, 1u << (k - 1), WAVE), oq = __shfl_down(xq, 1u << (k - 1), WAVE);
+            if ((lane & ((1u << k) - 1u)) == 0u) {
+                const double nh = (double)(1u << (2 + k));
+                const double wt = wmo_weight(nh, nh);
+                const double di = wmo_delta(nh, xi, nh, oi), dj = wmo_delta(nh, xj, nh, oj);
+                xq = wmo_second(xq, oq, di, dj, wt);
+                xi = xi + oi; xj = xj + oj;
+                const uint64_t at = (cap >> (3 + k)) + (p0 >> (3 + k));
+                if (!pair) ts[at] = mo_bits(xi);
+                t2[at] = mo_bits(xq);
+            }
+        }
+    }
+}
+// 3. the levels above the tiles, one at a time (k_wrg_upper's walk and barrier).  pairs == 0: workgroup b takes measure b's S and Q;
+// pairs == 1, launched behind it: workgroup b takes pair b's C and reads the S trees that launch left.  A child whose first tile
+// does not exist was never written: zeros.
+__global__ __launch_bounds__(TPB) void k_wmo_upper(DevWmos mo, int pairs, size_t tstride, uint64_t cap, uint64_t* __restrict__ tree, uint32_t ntiles) {
+    const int b = (int)blockIdx.x;
+    if (b >= (pairs ? mo.npairs : mo.nmeas)) return;
+    const int ki = pairs ? mo.pi[b] : b, kj = pairs ? mo.pj[b] : b;
+    uint64_t* si = tree + (size_t)(2 * ki) * tstride;
+    const uint64_t* sj = tree + (size_t)(2 * kj) * tstride;
+    uint64_t* t2 = tree + (size_t)(pairs ? 2 * mo.nmeas + b : 2 * ki + 1) * tstride;
+    for (int h = WRG_TILE_LEVELS + 1; (cap >> h) >= 1ull; ++h) {
+        const uint64_t cnt = cap >> h;                                   // nodes of this level: [cnt, 2 cnt)
+        const int up = h - WRG_TILE_LEVELS;                              // a node of it covers 2^up tiles
+        const uint64_t live = min(cnt, (((uint64_t)ntiles - 1ull) >> up) + 1ull);      // those whose first tile exists
+        const double nh = (double)(1ull << (h - 1));
+        const double wt = wmo_weight(nh, nh);
+        for (uint64_t i = threadIdx.x; i < live; i += TPB) {
+            const uint64_t l = 2ull * (cnt + i), r = l + 1ull;
+            const bool has = ((2ull * i + 1ull) << (up - 1)) < (uint64_t)ntiles;
+            const double ai = mo_f64(si[l]), aj = mo_f64(sj[l]), aq = mo_f64(t2[l]);
+            const double bi = has ? mo_f64(si[r]) : 0.0, bj = has ? mo_f64(sj[r]) : 0.0, bq = has ? mo_f64(t2[r]) : 0.0;
+            const double di = wmo_delta(nh, ai, nh, bi), dj = wmo_delta(nh, aj, nh, bj);
+            t2[cnt + i] = mo_bits(wmo_second(aq, bq, di, dj, wt));
+            if (!pairs) si[cnt + i] = mo_bits(ai + bi);
+        }
+        __syncthreads();
+    }
+}
+// a frame's state under the query: the rows it holds so far (0: the empty state) and the components a column reads
+struct WmoState { uint64_t n; double sy, qy, sx, qx, c; };
+// the node at index p of level h; two: the column reads a second measure
+__device__ __forceinline__ WmoState wmo_node(const uint64_t* __restrict__ ty, const uint64_t* __restrict__ tx, const uint64_t* __restrict__ tc, size_t tstride, uint64_t p, int h, bool two) {
+    WmoState v;
+    v.n = 1ull << h;
+    v.sy = mo_f64(ty[p]); v.qy = mo_f64(ty[tstride + p]);
+    v.sx = two ? mo_f64(tx[p]) : v.sy; v.qx = two ? mo_f64(tx[tstride + p]) : v.qy; v.c = two ? mo_f64(tc[p]) : v.qy;
+    return v;
+}
+__device__ __forceinline__ WmoState wmo_merge(const WmoState& a, const WmoState& b, bool two) {
+    if (a.n == 0ull) return b;
+    if (b.n == 0ull) return a;
+    const double na = (double)a.n, nb = (double)b.n;
+    const double wt = wmo_weight(na, nb);
+    const double dy = wmo_delta(na, a.sy, nb, b.sy);
+    WmoState v;
+    v.n = a.n + b.n;
+    v.sy = a.sy + b.sy; v.qy = wmo_second(a.qy, b.qy, dy, dy, wt);
+    if (two) {
+        const double dx = wmo_delta(na, a.sx, nb, b.sx);
+        v.sx = a.sx + b.sx; v.qx = wmo_second(a.qx, b.qx, dx, dx, wt); v.c = wmo_second(a.c, b.c, dx, dy, wt);
+    } else { v.sx = v.sy; v.qx = v.qy; v.c = v.qy; }
+    return v;
+}
+// 4. the value of every column at the first m positions: fin[c * stride + j].  rown: k_wsl_rows' (s = j - rown[j]); pend, vkey, gkey:
+// k_wrg_stage's.  (wmo_weight's n_a + n_b is exact in a double either way: n < 2^32.)
+__global__ __launch_bounds__(TPB) void k_wmo_fold(DevWmos mo, const uint32_t* __restrict__ rown, const uint32_t* __restrict__ pend, const uint64_t* __restrict__ vkey,
+                                                 const uint64_t* __restrict__ gkey, uint32_t n, uint32_t m, size_t stride, size_t tstride, uint64_t cap,
+                                                 const uint64_t* __restrict__ tree, uint64_t* __restrict__ fin) {
+    for (uint64_t j = (uint64_t)blockIdx.x * TPB + threadIdx.x; j < m; j += (uint64_t)gridDim.x * TPB) {
+        const uint32_t rn = rown[j], e = pend[j];
+        if ((uint64_t)rn > j || (uint64_t)e < j || e >= n) continue;       // (s <= j <= e < n: never taken)
+        const uint32_t s = (uint32_t)j - rn;
+        for (int c = 0; c < mo.rg.n; ++c) {
+            const DevWmoCol& a = mo.a[c];
+            uint32_t l = 0u, r1 = 0u;
+            uint64_t out = WAGG_QNAN;
+            if (wex_ends(mo.rg.a[c], mo.rg, vkey, gkey, j, s, e, l, r1)) {
+                const int op = a.op;
+                const bool two = op >= SDQH_GM_COVAR_POP;
+                const uint64_t* __restrict__ ty = tree + (size_t)(2 * a.my) * tstride;
+                const uint64_t* __restrict__ tx = tree + (size_t)(2 * a.mx) * tstride;
+                const uint64_t* __restrict__ tc = a.pair >= 0 ? tree + (size_t)(2 * mo.nmeas + a.pair) * tstride : ty + tstride;
+                WmoState left, right;
+                left.n = 0ull; left.sy = left.qy = left.sx = left.qx = left.c = 0.0;
+                right = left;
+                int h = 0;
+                for (uint64_t p = cap + l, q = cap + r1; p < q; p >>= 1, q >>= 1, ++h) {
+                    if (p & 1ull) left = wmo_merge(left, wmo_node(ty, tx, tc, tstride, p++, h, two), two);
+                    if (q & 1ull) right = wmo_merge(wmo_node(ty, tx, tc, tstride, --q, h, two), right, two);
+                }
+                const WmoState f = wmo_merge(left, right, two);
+                const uint32_t rows = r1 - l;
+                const double size = (double)rows;
+                // a pair stored as (pi < pj) holds C whichever of the two is Y: dx * dy commutes
+                if (op == SDQH_GM_VAR_POP) out = mo_bits(f.qy / size);
+                else if (op == SDQH_GM_STDDEV_POP) out = mo_bits(sqrt(f.qy / size));
+                else if (op == SDQH_GM_COVAR_POP) out = mo_bits(f.c / size);
+                else if (op == SDQH_GM_VAR_SAMP) { if (rows > 1u) out = mo_bits(f.qy / (size - 1.0)); }
+                else if (op == SDQH_GM_STDDEV_SAMP) { if (rows > 1u) out = mo_bits(sqrt(f.qy / (size - 1.0))); }
+                else if (op == SDQH_GM_COVAR_SAMP) { if (rows > 1u) out = mo_bits(f.c / (size - 1.0)); }
+                else if (op == SDQH_GM_CORR) {
+                    if (f.qx != 0.0 && f.qy != 0.0) {
+                        double t = f.c / (sqrt(f.qx) * sqrt(f.qy));
+                        if (t > 1.0) t = 1.0;
+                        if (t < -1.0) t = -1.0;
+                        out = mo_bits(t);
+                    }
+                } else if (f.qx != 0.0) {                                // REGR_SLOPE, REGR_INTERCEPT
+                    const double slope = f.c / f.qx;
+                    out = mo_bits(op == SDQH_GM_REGR_SLOPE ? slope : f.sy / size - slope * (f.sx / size));
+                }
+            }
+            fin[(size_t)c * stride + j] = out;
+        }
+    }
+}
+
 // ---- sessions inside partitions (sdqh_table_sessions) -----------------------------------------------------------------------------
 // Every pass above cuts where the KEYS decide; a session is cut where the data along the order decide (include/sdqh_sort_sessions.h):
 // sorted position r opens one iff it opens its partition or the rule says so about the raw values at r - 1 and r.  k_ss_heads makes
@@ -2191,7 +2403,8 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // distinct measures they read and the columns its second pass folds.
 // STEP_SESSIONS (sdqh_table_sessions) cuts the partitions of the first npart terms by `ssr` and returns every row (per_session 0) or
 // one row per session — then it filters as STEP_GROUPS does; `ss` are its columns, `aggs` the folds among them.
-enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS, STEP_SESSIONS };
+// STEP_WMOMENTS (sdqh_table_window_moments) returns every row with `wm`'s columns: frames as STEP_EXCLUDES finds them, moments in them.
+enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS, STEP_SESSIONS, STEP_WMOMENTS };
 struct SortStep {
     StepKind kind; int npart;
     bool filters; int rank_kind; int64_t per_limit;
@@ -2201,6 +2414,7 @@ struct SortStep {
     int ngroup; DevGdAggs gd;
     DevMoAggs mo;
     int per_session; DevSsRule ssr; DevSsCols ss;
+    DevWmos wm;
 };
 static_assert(SDQH_WSLIDE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WRANGE_MAX_AGGS == SDQH_WAGG_MAX_AGGS && SDQH_WQUANT_MAX_COLS == SDQH_WAGG_MAX_AGGS,
               "one list of result arrays serves frames, slides, ranges and quantiles");
@@ -2822,6 +3036,56 @@ static int step_sessions(StepRun& r) {
     return SDQH_OK;
 }
 
+// Second moments over frames (sdqh_table_window_moments): block 3 = step_excludes' [partition pass | partition ends | dense ranks | kept
+// per tile | VALUE keys | GROUPS keys] — the frames are found as there, with nothing excluded — then [component trees: S and Q per
+// distinct measure, C per distinct pair | values].  k_wrg_stage runs over the image of COUNT ranges: it stages the ends and the keys alone.
+static int step_wmoments(StepRun& r) {
+    const int64_t n = r.n;
+    DevWmos mo = r.step.wm;
+    DevWranges& rg = mo.rg;
+    const size_t na = (size_t)rg.n;
+    bool groups = false;
+    for (size_t a = 0; a < na; ++a) {
+        DevWrange& d = rg.a[a];
+        groups |= d.unit == SDQH_WRANGE_GROUPS;
+        if (d.unit == SDQH_WEX_ROWS) {                                 // an offset of n or more reaches outside every partition: clamped, as a slide's is
+            d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
+            d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
+        }
+    }
+    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
+    while (cap < (uint64_t)n) cap <<= 1;
+    const size_t tstride = (size_t)(2 * cap), ntrees = (size_t)(2 * mo.nmeas + mo.npairs);
+    Partitions p;
+    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
+    uint64_t *vkey = nullptr, *gkey = nullptr, *tree = nullptr, *fin = nullptr;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.take(c, n, true, true, true);
+            pend = c.take<uint32_t>((size_t)n);
+            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
+            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
+            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
+            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+            tree = c.take<uint64_t>(tstride * ntrees);
+            fin = c.take<uint64_t>(r.stride * na);
+        })) return r.nomem();
+    if (rg.vcol < 0) vkey = nullptr;
+    if (!groups) { dense = nullptr; gkey = nullptr; }
+    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS | PP_NEXT);
+    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
+    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
+           r.stride, (size_t)0, cap, pend, vkey, gkey, (uint64_t*)nullptr, (uint64_t*)nullptr, p.ntiles);
+    LAUNCH(r.ctx, "k_wmo_stage", k_wmo_stage, p.tgrid, r.table->stage, mo, r.s.refs, r.s.perm, r.un, tstride, cap, tree, p.ntiles);
+    LAUNCH(r.ctx, "k_wmo_tiles", k_wmo_tiles, p.tgrid, mo, r.un, tstride, cap, tree, p.ntiles);
+    if (cap > (uint64_t)SORT_TILE) {
+        LAUNCH(r.ctx, "k_wmo_upper", k_wmo_upper, (unsigned)mo.nmeas, mo, 0, tstride, cap, tree, p.ntiles);
+        if (mo.npairs) LAUNCH(r.ctx, "k_wmo_upper", k_wmo_upper, (unsigned)mo.npairs, mo, 1, tstride, cap, tree, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wmo_fold", k_wmo_fold, r.row_grid(), mo, p.rown, pend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, tree, fin);
+    r.columns(fin, rg.n);
+    return SDQH_OK;
+}
+
 // The table entry points behind their argument checks, the spine of every ordered call: select -> passes -> step -> emit -> fetch.
 // who: the entry point's name in messages.
 static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64_t min_hits, int64_t limit, int nsort, const DevSortTerm* terms, const SortStep& step,
@@ -2857,6 +3121,7 @@ static int ordered_impl(sdqh_ctx* ctx, sdqh_table* table, const char* who, int64
         case STEP_DISTINCTS: step_rc = step_distincts(r); break;      // (likewise)
         case STEP_MOMENTS: step_rc = step_moments(r); break;          // (likewise)
         case STEP_SESSIONS: if (step.per_session || (step.out && step.ss.n)) step_rc = step_sessions(r); break;      // (per session likewise; per row its columns alone)
+        case STEP_WMOMENTS: if (step.out) step_rc = step_wmoments(r); break;
     }
     if (step_rc || r.ended) return step_rc;
     const int64_t m = r.m;
@@ -3242,6 +3507,68 @@ int sdqh_table_group_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
 }
 
+int sdqh_table_window_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
+                              int ncols, const sdqh_window_moment* cols, int64_t limit, int64_t capacity,
+                              int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
+    const char* who = "table_window_moments";
+    bool ok = cols && ncols >= 1 && ncols <= SDQH_WM_MAX_COLS;
+    bool value = false;
+    for (int c = 0; ok && c < ncols; ++c) {
+        const sdqh_window_moment& g = cols[c];
+        ok = g.op >= SDQH_GM_VAR_POP && g.op <= SDQH_GM_REGR_INTERCEPT && g.unit >= SDQH_WRANGE_VALUE && g.unit <= SDQH_WEX_ROWS && g._pad == 0 &&
+             !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+    }
+    bool vf64 = false;
+    if (ok && value) {                                                // sdqh_table_window_range's demand of a VALUE frame: one ORDER BY term, with arithmetic
+        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
+        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
+    }
+    for (int c = 0; ok && c < ncols; ++c) {
+        const sdqh_window_moment& g = cols[c];
+        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
+            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
+            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
+            ok = lo_ok && hi_ok && !(both && lo > hi);
+        } else ok = !(both && g.lo > g.hi);
+    }
+    DevSortTerm terms[SDQH_SORT_MAX_KEYS];
+    if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
+    SortStep st = sort_step(STEP_WMOMENTS, npartition, out_cols);
+    DevWmos& mo = st.wm;
+    DevWranges& rg = mo.rg;
+    rg.n = ncols;
+    rg.vcol = value ? npartition : -1; rg.vdesc = value ? terms[npartition].sk.desc : 0; rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    // a measure's trees among the distinct ones (columns naming the same measure share them), and a pair's C tree among the pairs
+    auto measure = [&](const DevSortKey& sk) {
+        for (int k = 0; k < mo.nmeas; ++k) if (mo.sk[k].kind == sk.kind && mo.sk[k].index == sk.index && mo.sk[k].is_f64 == sk.is_f64) return k;
+        mo.sk[mo.nmeas] = sk;
+        return mo.nmeas++;
+    };
+    auto pair_of = [&](int i, int j) {
+        if (i == j) return -1;                                        // C of a measure with itself is its Q
+        if (i > j) std::swap(i, j);
+        for (int c = 0; c < mo.npairs; ++c) if (mo.pi[c] == i && mo.pj[c] == j) return c;
+        mo.pi[mo.npairs] = i; mo.pj[mo.npairs] = j;
+        return mo.npairs++;
+    };
+    for (int c = 0; c < ncols; ++c) {
+        const sdqh_window_moment& g = cols[c];
+        DevWrange& d = rg.a[c];
+        d.g.op = SDQH_WAGG_COUNT; d.g.cls = WSL_NONE;                 // the image: k_wrg_stage stages no element for it
+        d.unit = g.unit; d.flags = g.flags; d.lo = g.lo; d.hi = g.hi;
+        const bool two = g.op >= SDQH_GM_COVAR_POP;                   // (VAR_* and STDDEV_* ignore the second measure)
+        DevSortKey y, x; std::memset(&y, 0, sizeof(y)); std::memset(&x, 0, sizeof(x));
+        if (int rc = measure_set(ctx, table, who, "column", c, g.kind, g.index, g.is_f64, y)) return rc;
+        if (two) if (int rc = measure_set(ctx, table, who, "column", c, g.kind2, g.index2, g.is_f64_2, x)) return rc;
+        DevWmoCol& a = mo.a[c];
+        a.op = g.op; a.my = measure(y); a.mx = two ? measure(x) : a.my;
+        a.pair = two ? pair_of(a.my, a.mx) : -1;
+    }
+    return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
+}
+
 int sdqh_table_sessions(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int npartition, int nterms, const sdqh_sort_term* in,
                         const sdqh_session_rule* rule, int per_session, int ncols, const sdqh_session_col* cols, int64_t limit, int64_t capacity,
                         int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
@@ -3291,6 +3618,7 @@ static int window_tile_rows(sdqh_ctx* ctx, const char* who, int64_t* tile_rows, 
     if (has_narrow) *narrow_max_width = 0;
     return SDQH_OK;
 }
+int sdqh_window_moments_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "window_moments_geometry", tile_rows, false, nullptr); }
 int sdqh_sessions_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "sessions_geometry", tile_rows, false, nullptr); }
 int sdqh_group_moments_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_moments_geometry", tile_rows, false, nullptr); }
 int sdqh_group_distinct_geometry(sdqh_ctx* ctx, int64_t* tile_rows) { return window_tile_rows(ctx, "group_distinct_geometry", tile_rows, false, nullptr); }

@@ -59,8 +59,9 @@ _COLL_ON_RECORDED_STREAM = os.environ.get("SDQLPY_AMD_DIST_COLL_ON_RECORDED_STRE
 
 def refuse_window(top):
     """ORDER BY ... LIMIT per group (top_per / numbered: result.WindowRequest) and every request that travels as one (over, sliding,
-    ranged, excluding, quantiles, grouping_sets, distincts, moments, sessions: its subclasses) are single-GPU operations: a partition's rows may lie on
-    several ranks, and ranking or folding them takes an exchange by partition key that the runner does not have."""
+    ranged, excluding, quantiles, grouping_sets, distincts, moments, sessions, rolling: its subclasses) are single-GPU operations: a
+    partition's rows may lie on several ranks, and ranking or folding them takes an exchange by partition key that the runner does
+    not have."""
     from .result import WindowRequest
     if isinstance(top, WindowRequest):                           # (a plain window is known to the user by two methods)
         raise frontend.UnsupportedQuery("%s on one GPU: the multi-GPU runner has no exchange by partition key"

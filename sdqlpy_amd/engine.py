@@ -23,7 +23,7 @@ import numpy as np
 from . import abi, build
 from .frontend import (DISTINCT_FIELD, And, Bin, Call, Cmp, Col, Const, Contains, DistinctOp, ExtremaOp, FinalizeOp, HostDictOp, IfElse, Lookup, Not, Or, PayloadField,
                        RecordCons, RunNew, ScalarExprOp, ScalarField, ScanOp, SelectKeysOp, StrIn, UnsupportedQuery, WholeKey, WrapScalarOp)
-from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, MOMENT_OPS, MomentsRequest, moments_result, QUANTILE_FNS, RANGE_UNITS, SESSION_OPS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, SessionRequest, SlideRequest, \
+from .result import DISTINCT_MEASURED, DISTINCT_OPS, DistinctRequest, EXCLUDES, EXCLUDE_OPS, EXCLUDE_UNITS, FRAMES, GROUP_OPS, GroupingRequest, grouped_result, MOMENT_OPS, MomentsRequest, moments_result, QUANTILE_FNS, RANGE_UNITS, SESSION_OPS, SLIDE_OPS, WAGG_OPS, WINDOW_KINDS, DeferredResultSet, ExcludeRequest, FrameRequest, Pending, DictResult, QuantileRequest, RangeRequest, ResultSet, RollingRequest, SessionRequest, SlideRequest, \
     TextRefs, WindowRequest, decode_text, slide_empty
 
 # value-tuple vocabulary: canonical shape of the whole value record -> (ABI shape, index of the COUNT field or None)
@@ -162,7 +162,7 @@ class Engine:
         # "ranked": the order columns that went through a rank table} (the last 256)
         self.order_routes = collections.deque(maxlen=256)
         # the requests with partitions (result.WindowRequest and its subclasses) are served on the device where the library has their
-        # extension and their switch is on — one switch per kind, device_window .. device_sessions, set from its environment
+        # extension and their switch is on — one switch per kind, device_window .. device_window_moments, set from its environment
         # variable SDQLPY_AMD_DEVICE_...; 0 forces the host route (A/B measurements, tests).  _WINDOW_ROUTES says which is whose.
         for rec in _WINDOW_ROUTES:
             setattr(self, rec.switch, os.environ.get(rec.env, "1") != "0")
@@ -1839,19 +1839,20 @@ def result_columns(plan):
     return None
 
 
-def _columns_fit(top_items, limit, spec):
+def _columns_fit(top_items, limit, spec, defaults=True):
     """Can the device take the columns `top_items` of a request with partitions (None: it has none) over the terms `spec`?  At most
     SORT_MAX_KEYS terms, at most `limit` columns, measures that are underived numeric columns (spec.measures), and — where a column has
     a default, the last member of its tuple of six or more; an aggregate over a frame has none — no default beyond 2^53 for a column
     the table keeps as integer-valued doubles: such a column takes its default as a double and back, and one no double holds stays on
-    the host (an average's default is a plain double, never written back as an integer: exempt)."""
+    the host (an average's default is a plain double, never written back as an integer: exempt; defaults False: the request's columns
+    have no default at all, whatever their tuples end in — a RollingRequest's end in the frame's `hi`)."""
     if not 1 <= len(spec) <= abi.SORT_MAX_KEYS:
         return False
     if top_items is None:
         return True
     if len(top_items) > limit or getattr(spec, "measures", None) is None:
         return False
-    return not any(len(item) > 5 and item[1] != "avg" and item[2] in spec.int_values and item[-1] is not None and not isinstance(item[-1], (float, np.floating)) and abs(int(item[-1])) > 1 << 53
+    return not defaults or not any(len(item) > 5 and item[1] != "avg" and item[2] in spec.int_values and item[-1] is not None and not isinstance(item[-1], (float, np.floating)) and abs(int(item[-1])) > 1 << 53
                    for item in top_items)
 
 
@@ -1891,7 +1892,7 @@ def _order_route(eng, top, spec):
     rec = _route_of(top)
     if rec is not None:
         items = top.items if rec.items else None
-        fits = _columns_fit(items, len(items) if rec.per_call else rec.limit, spec) and (rec.fits is None or rec.fits(top, spec))
+        fits = _columns_fit(items, len(items) if rec.per_call else rec.limit, spec, rec.defaults) and (rec.fits is None or rec.fits(top, spec))
         return rec.route if fits and on(rec.switch, rec.flag) and terms_ok else "host"
     if derived:
         return "sorted_by" if k >= 1 and n <= abi.SORT_MAX_KEYS and terms_ok else "host"
@@ -1963,6 +1964,27 @@ def _exclude_columns(top, spec):
             kind, index, is_f64, empty = _measure_args(col, measure, default, spec, "excluding")
         cols.append((EXCLUDE_OPS.index(op), kind, index, is_f64, EXCLUDE_UNITS.index(unit), lo, hi, empty, EXCLUDES.index(top.exclude)))
     return cols
+
+
+def _rolling_offsets(top, spec):
+    """The offsets [(lo, hi)] of a RollingRequest's frames as the device takes them, or None where it cannot: _exclude_offsets' rule —
+    every column's through _range_offsets, as a RangeRequest of its unit."""
+    out = []
+    for name, _, y, _, unit, lo, hi in top.aggs:
+        one = _range_offsets(RangeRequest(top[0], top[1], top.npartition, "value" if unit == "value" else "groups", [(name, "count", y, lo, hi, None)]), spec)
+        if one is None:
+            return None
+        out += one
+    return out
+
+
+def _rolling_call(eng, table, min_hits, top, terms, spec, k, cap, want_hits):
+    """The route "window_moments": one abi.Context.table_window_moments call; a univariate op names its one measure twice."""
+    cols = []
+    for (_, op, _, _, unit, _, _), measures, (lo, hi) in zip(top.aggs, spec.measures, _rolling_offsets(top, spec)):
+        y, x = measures[0], measures[-1]
+        cols.append((MOMENT_OPS.index(op),) + _measure_args(y, None, None, spec, None)[:3] + _measure_args(x, None, None, spec, None)[:3] + (EXCLUDE_UNITS.index(unit), lo, hi))
+    return eng.ctx.table_window_moments(table, min_hits, top.npartition, terms, cols, k, cap, want_hits=want_hits)
 
 
 class _GroupColumns(list):
@@ -2092,15 +2114,16 @@ class _Route(tuple):
     per_call: the limit holds per device call (the request says how it splits), not for the request
     renote: the note follows the result's aliases (_finalize) — not where it has always named the table's own columns
     raw_modes: a "mode" column comes back as the stored 64 bits, decoded as the field itself is (_mode_decoded)
+    defaults: a column of six or more fields ends in its default (_columns_fit); False: its columns have none
     finish(rs, ordered, top): the result where it is not the rows with a column each appended, or None."""
 
     def __new__(cls, request, route, switch, flag, items, limit, call, note, integral=None, fits=None, measured=lambda top, spec: [item[2] for item in top.items],
-                value_frames=False, per_call=False, renote=True, raw_modes=False, finish=None):
+                value_frames=False, per_call=False, renote=True, raw_modes=False, defaults=True, finish=None):
         self = tuple.__new__(cls, (request, route, switch, flag, items, limit))
         self.request, self.route, self.switch, self.flag, self.items, self.limit = self
         self.env = "SDQLPY_AMD_" + switch.upper()               # the switch's environment variable
         self.call, self.note, self.integral, self.fits, self.measured = call, note, integral, fits, measured
-        self.value_frames, self.per_call, self.renote, self.raw_modes, self.finish = value_frames, per_call, renote, raw_modes, finish
+        self.value_frames, self.per_call, self.renote, self.raw_modes, self.defaults, self.finish = value_frames, per_call, renote, raw_modes, defaults, finish
         return self
 
 
@@ -2212,6 +2235,14 @@ _WINDOW_ROUTES = (
     _Route(ExcludeRequest, "window_exclude", "device_window_exclude", "has_window_exclude", "frames", abi.WEX_MAX_COLS, call=_exclude_call,
            note=lambda top, route, spec: {"exclude": top.exclude, "frames": [list(a) for a in top.frames]}, integral=lambda item: item[1] not in ("count", "avg"),
            fits=lambda top, spec: _exclude_offsets(top, spec) is not None, value_frames=True),
+    # VAR / STDDEV / COVAR / CORR / REGR over window frames (rolling), one abi.Context.table_window_moments call (_rolling_call): at most
+    # WM_MAX_COLS columns whose measures — one or two a column — are underived numeric columns, offsets under "window_exclude"'s
+    # conditions (_rolling_offsets); a request of more columns is the host's, as every window route's is.  Every column is a double:
+    # none takes its measure's dtype.  Noted with the columns and "calls"
+    _Route(RollingRequest, "window_moments", "device_window_moments", "has_window_moments", "aggs", abi.WM_MAX_COLS, call=_rolling_call,
+           note=lambda top, route, spec: {"aggs": [list(a) for a in top.aggs], "calls": 1 if route == "window_moments" else 0},
+           integral=lambda item: False, fits=lambda top, spec: _rolling_offsets(top, spec) is not None,
+           measured=lambda top, spec: [[y] if x is None else [y, x] for _, _, y, x, _, _, _ in top.aggs], value_frames=True, defaults=False),
     # sessions — gaps and islands — inside partitions (sessions), one abi.Context.table_sessions call (_session_call): at most SS_MAX_COLS
     # columns whose measures — and the change rule's marker — are underived numeric columns, a gap the device's gap term can take
     # (_session_gap: no text, no column decoded on the host, nothing beyond 2^53 for integers kept as doubles).  Noted with "rule",

@@ -844,6 +844,79 @@ def moment_finish(op, count, qy, qx, c, muy, mux):
         return np.where(qx != 0.0, slope if op == "regr_slope" else muy - slope * mux, MOMENT_NULL)
 
 
+class RollingRequest(WindowRequest):
+    """The second moments over window frames, travelling where an ExcludeRequest travels (every row is kept): [0] = the limit on the
+    whole result, [1] = the PARTITION BY terms followed by the ORDER BY terms, npartition, and aggs = [(name of the new column, op: a
+    name of MOMENT_OPS, y, x or None — a univariate op reads y alone —, unit: a name of EXCLUDE_UNITS, the column's own, lo, hi: the
+    frame's offsets in that unit, negative = preceding, None = unbounded)] in the order the columns are appended.  Every new column
+    is float64, NaN where SQL has NULL (an empty frame among them)."""
+    method, items_attr, served_by = "rolling", "aggs", "rolled"
+
+    def __new__(cls, k, terms, npartition, aggs):
+        self = WindowRequest.__new__(cls, k, terms, npartition, 0, WINDOW_ALL, None)
+        self.aggs = [(str(n), str(op), str(y), None if x is None else str(x), str(unit), lo, hi) for n, op, y, x, unit, lo, hi in aggs]
+        if not self.aggs or any(op not in MOMENT_OPS or (x is None) != (op in MOMENT_UNIVARIATE) or unit not in EXCLUDE_UNITS or
+                                (lo is not None and hi is not None and lo > hi) for _, op, _, x, unit, lo, hi in self.aggs):
+            raise ValueError("rolling: bad aggregate")
+        if any(unit == "value" for _, _, _, _, unit, _, _ in self.aggs) and len(terms) != npartition + 1:
+            raise ValueError("rolling: a value frame is ordered by exactly one column")
+        return self
+
+    def _with(self, terms, items):
+        return RollingRequest(self[0], terms, self.npartition, items)
+
+    def renamed(self, terms, names=None):
+        """The same request over other column names: the terms term for term, both measures through `names` (old name -> new)."""
+        names = names or {}
+        return self._with(terms, [(n, op, names.get(y, y), names.get(x, x), unit, lo, hi) for n, op, y, x, unit, lo, hi in self.aggs])
+
+    def check_columns(self, columns):
+        WindowRequest.check_columns(self, columns)               # (the terms, y and the new names)
+        for _, _, _, x, _, _, _ in self.aggs:
+            if x is not None and x not in columns:
+                raise KeyError("rolling: the result has no column %r" % x)
+
+
+def rolling_request(columns, by, order, aggs, unit="rows", k=WINDOW_ALL):
+    """The checked RollingRequest of `rolling`: by / order as window_request takes them; unit a name of EXCLUDE_UNITS, the unit of every
+    column that names none; aggs = {new column: (op, y, lo, hi[, unit]) | (op, y, x, lo, hi[, unit])} with op a name of MOMENT_OPS —
+    "var_pop" .. "stddev_samp" take the first form, "covar_pop" .. "regr_intercept" the second, y first — and lo / hi offsets in the
+    column's unit (negative = preceding, None = unbounded): ints, or floats as well for unit "value".  columns: the result's column
+    names when they are known (None: checked when the result is).  KeyError for a column the result lacks or a new column it has
+    already, ValueError for everything else."""
+    req = window_request(None, by, order, "row_number", WINDOW_ALL, k=k)     # (its checks of by / order / k)
+    if unit not in EXCLUDE_UNITS:
+        raise ValueError("rolling: unit is one of %s, not %r" % (", ".join(EXCLUDE_UNITS), unit))
+    shape = "(op, y, lo, hi[, unit]) or (op, y, x, lo, hi[, unit])"
+    _aggs_dict("rolling", aggs, shape)
+    out = []
+    for name, spec in aggs.items():
+        _agg_spec("rolling", name, spec, shape, lambda n: n >= 1)
+        op = spec[0]
+        if op not in MOMENT_OPS:
+            raise ValueError("rolling: op is one of %s, not %r" % (", ".join(MOMENT_OPS), op))
+        nm = 1 if op in MOMENT_UNIVARIATE else 2                 # the measures come first, then lo, hi and perhaps the unit
+        if len(spec) not in (nm + 3, nm + 4):
+            raise ValueError("rolling: %s takes %s" % (op, "one column: (op, y, lo, hi[, unit])" if nm == 1 else "two columns: (op, y, x, lo, hi[, unit])"))
+        y, x = spec[1], spec[2] if nm == 2 else None
+        for col in (y,) if x is None else (y, x):
+            if not isinstance(col, str):
+                raise ValueError("rolling: a measure is a column name")
+        own = spec[nm + 3] if len(spec) == nm + 4 else unit
+        if own not in EXCLUDE_UNITS:
+            raise ValueError("rolling: a column's unit is one of %s, not %r" % (", ".join(EXCLUDE_UNITS), own))
+        if own == "value" and len(req[1]) != req.npartition + 1:
+            raise ValueError("rolling: a value frame is ordered by exactly one column, not %d" % (len(req[1]) - req.npartition))
+        lo = None if spec[nm + 1] is None else _range_offset(spec[nm + 1], own, "rolling")
+        hi = None if spec[nm + 2] is None else _range_offset(spec[nm + 2], own, "rolling")
+        _agg_frame("rolling", lo, hi)
+        out.append((name, op, y, x, own, lo, hi))
+    req = RollingRequest(req[0], req[1], req.npartition, out)
+    if columns is not None:
+        req.check_columns(columns)
+    return req
+
+
 SESSION_OPS = ("sum", "count", "min", "max", "first", "last", "avg", "number", "row")      # their positions are abi.SS_SUM .. SS_ROW
 SESSION_UNMEASURED = ("count", "number", "row")            # the ops that read no measure
 SESSION_HOST_MAX_COLS = 64                                 # the columns of one request (the device takes abi.SS_MAX_COLS a call; the rest is the host's)
@@ -1385,6 +1458,67 @@ class ResultSet:
         tied with it), "ties" (those rows but not the row itself) or "no others".  Nothing left gives `default` (0 / NaN), a count 0;
         an avg is float64."""
         return self.excluded(exclude_request(self.columns, by, order, aggs, exclude, unit))
+
+    def rolled(self, req):
+        """Every row in a RollingRequest's order (the first req[0] of them) with its columns appended: what sdqh_table_window_moments
+        gives on the device (include/sdqh_sort_wmoments.h), on the host — by the definition, not by the device's tree: the frame's
+        ends as `excluded` finds them with nothing taken out, then per row two passes over the frame's rows as float64: the means,
+        then the sums of the centred squares and products, and the op's formula (moment_finish).  NaN where SQL has NULL: an empty
+        frame, *_samp of one row, corr with a constant column, regr_* with a constant x."""
+        self._wait()
+        req.check_columns(self.columns)
+        idx, part_head, tie_head = self._window_heads(req.by, req.order)
+        n = self._n
+        pos = np.arange(n, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(part_head, pos, 0)) if n else pos
+        heads = np.nonzero(part_head)[0]
+        stops = np.append(heads[1:], n)
+        end = (stops - 1)[np.cumsum(part_head) - 1] if n else pos
+        measures, keys, frames, sums = {}, {}, {}, {}
+        new = []
+        for name, op, y, x, unit, lo, hi in req.aggs:
+            for col in (y, x):
+                if col is not None and col not in measures:
+                    v = self.column(col)
+                    if v.dtype.kind not in "iubf":
+                        raise ValueError("rolling: %s of column %r: the measure is not numeric" % (op, col))
+                    measures[col] = np.ascontiguousarray(v[idx], np.float64)
+            if (unit, lo, hi) not in frames:
+                if unit == "rows":
+                    lo_c = -n if lo is None else max(-n, min(n, lo))     # an offset of n or more leaves every partition
+                    hi_c = n if hi is None else max(-n, min(n, hi))
+                    left, right = np.maximum(pos + lo_c, start), np.minimum(pos + hi_c, end)
+                    empty = left > right
+                else:
+                    if unit not in keys:
+                        keys[unit] = self._range_keys(unit, req.order, idx, start, tie_head, "rolling")
+                    left, right, empty = _range_ends(unit, keys[unit], lo, hi, heads, stops, start, end)
+                frames[(unit, lo, hi)] = (left, right, np.asarray(empty, bool))
+            left, right, empty = frames[(unit, lo, hi)]
+            if (unit, lo, hi, y, x) not in sums:                         # [count, qy, qx, c, muy, mux] per row; an empty frame counts one row of zeros
+                s = np.zeros((6, n), np.float64)
+                s[0] = 1.0
+                vy, vx = measures[y], measures[x if x is not None else y]
+                with np.errstate(all="ignore"):
+                    for j in np.nonzero(~empty)[0]:
+                        a, b = left[j], right[j] + 1
+                        m = np.float64(b - a)
+                        muy, mux = vy[a:b].sum() / m, vx[a:b].sum() / m
+                        dy, dx = vy[a:b] - muy, vx[a:b] - mux
+                        s[:, j] = (m, (dy * dy).sum(), (dx * dx).sum(), (dx * dy).sum(), muy, mux)
+                sums[(unit, lo, hi, y, x)] = s
+            count, qy, qx, c, muy, mux = sums[(unit, lo, hi, y, x)]
+            new.append((name, np.where(empty, MOMENT_NULL, moment_finish(op, count, qy, qx, c, muy, mux)) if n else np.zeros(0, np.float64)))
+        k = max(0, min(int(req[0]), n))
+        cols = [c[idx[:k]] for c in self._cols]                          # undecoded text stays undecoded
+        return ResultSet(self.columns + [nm for nm, _ in new], cols + [np.ascontiguousarray(c[:k], np.float64) for _, c in new])
+
+    def rolling(self, by, order, aggs, unit="rows"):
+        """Every row, ordered by `by` then `order`, plus one float64 column per aggregate over a frame inside the row's group of `by`:
+        aggs = {new column: (op, y, lo, hi[, unit]) | (op, y, x, lo, hi[, unit])}, op in MOMENT_OPS — a moving standard deviation, a
+        rolling correlation, a rolling regression slope.  The frame in `unit` — "rows" (the rows [row + lo, row + hi]), "value" or
+        "groups" (ranged's frames) — or in the column's own; None: unbounded.  NaN where SQL has NULL, an empty frame included."""
+        return self.rolled(rolling_request(self.columns, by, order, aggs, unit))
 
     def ranged(self, by, order, aggs, unit="value"):
         """Every row, ordered by `by` then `order`, plus one column per aggregate over a value or group frame inside the row's group of

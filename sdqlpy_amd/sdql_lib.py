@@ -528,6 +528,19 @@ def sdql_compile(in_type):
             per="session": one row per session, its first row.  Names and ops are checked here, before anything is launched."""
             return _requested("sessions_request", list(partition) if isinstance(partition, (list, tuple)) else partition, order, gap, change, cols, per)
 
+        def rolling(by, order, aggs, unit="rows"):
+            """The same query finished with ORDER BY `by`, `order` and one float64 column per SECOND MOMENT over a window frame inside
+            the row's group of `by`: aggs = {new column: (op, y, lo, hi[, unit]) | (op, y, x, lo, hi[, unit])}, op one of moments'
+            nine names — "var_pop" .. "stddev_samp" take the first form, "covar_pop" .. "regr_intercept" the second, y the dependent
+            column —, the frame in `unit` or the column's own — "rows", "value" or "groups", lo / hi as excluding's: negative =
+            preceding, None = unbounded —, e.g. ``q3.rolling(["o_shippriority"], [("o_orderdate", "asc")], {"vol": ("stddev_samp",
+            "revenue", -19, 0), "beta": ("regr_slope", "revenue", "l_orderkey", -19, 0)})(li, cu, ord)``: a 20-row volatility and a
+            rolling slope.  Where SQL gives NULL — an empty frame, a sample variance of one row, a correlation with a constant column
+            — the column holds NaN.  Folded from merged (count, sum, centred sum of squares) states, never from sum(x^2) - sum(x)^2 /
+            m: the error grows with mean / spread times log2 of the frame's width, not with the data's size.  Names, ops, arity,
+            bounds and units are checked here, before anything is launched."""
+            return _requested("rolling_request", list(by), list(order), aggs, unit)
+
         wrapper.top = top
         wrapper.order_by = order_by
         wrapper.top_per = top_per
@@ -543,6 +556,7 @@ def sdql_compile(in_type):
         wrapper.distincts = distincts
         wrapper.moments = moments
         wrapper.sessions = sessions
+        wrapper.rolling = rolling
         wrapper.__sdql_in_type__ = in_type
         wrapper.__sdql_func__ = func
         return wrapper
