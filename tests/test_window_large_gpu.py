@@ -1,5 +1,5 @@
 """The window entry points past 256 tiles on the MI355X (run with -m gpu): sdqh_table_window, _window_agg, _window_slide, _window_range,
-_window_quantile and _window_exclude against numpy at the sizes at which a thread of the one-workgroup tile scans (k_win_scan, k_wagg_scan, k_wsl_scan in
+_window_quantile, _window_exclude and _window_moments against numpy at the sizes at which a thread of the one-workgroup tile scans (k_win_scan, k_wagg_scan, k_wsl_scan in
 both directions, k_wagg_next, k_sort_scan over tile_kept) folds MORE THAN ONE tile, k_wrg_upper's stride loop iterates more than once
 and the fold tree grows levels above cap = 131072.  With T = 512 positions per tile and W = 256 threads in the scan workgroup, thread t
 takes the tiles [t * per, (t + 1) * per), per = ceil(ntiles / W); every other window test stops at 137 tiles, where per = 1.
@@ -19,6 +19,7 @@ takes the tiles [t * per, (t + 1) * per), per = ceil(ntiles / W); every other wi
     _window_range          test_ranges (and 2 W T + 2 T)                   "
     _window_quantile       test_quantiles                                  "
     _window_exclude        test_exclusions: 24 frames, 3 units x 4 ways    test_exclusions_one_call (SWALLOW)
+    _window_moments        test_moments: 8 / 4 columns (and 2 W T + 2 T)   test_moments_one_call ("one partition", SWALLOW)
 
 Everything runs at W T + 1 and at 2 W T + T + 1 (262 657) on six partition patterns; the other four sizes take one call of four columns
 per entry point.  Beside four patterns of test_window_gpu there are two of this file's own, because test_window_gpu's long tie run
@@ -37,11 +38,21 @@ and its 31 columns 0.4 s, Quant's 50 columns 0.25 s, Slid's 56 slides 0.7 s; the
 "one partition", whose 220 000 distinct order values pass through Python integers once per bounded side of a frame.  A table, its
 staged rows and their Ranked are built once per (pattern, size) and shared; Framed, Slid, Ranged and Quant each sort the rows once more
 when a test makes one (the 0.1 s of Ranked above).  Excluded (test_window_exclude_gpu's, a Ranged) and its 24 columns: 0.9 s on "heavy
-ties" up to 2.2 s on "one partition" (test_large_patterns_cpu prints them)."""
+ties" up to 2.2 s on "one partition" (test_large_patterns_cpu prints them).
+
+The window moments (k_wmo_tiles over 257 and 514 tiles, k_wmo_upper's stride loop, k_wmo_fold's queries above cap = 131072) are general
+sums of squares, exact in no association: they are compared BY BITS ON EVERY ROW with the header's pinned fold restated in whole-array
+numpy (window_moments_numpy_reference; test_window_moments_numpy_cpu holds it against the Python restatement bit for bit), over the frame
+ends of Excluded.base.  That reference costs, on the same core: the tree 0.04 s, a column of 262 657 rows 0.1 s ("heavy ties": few
+distinct frames) to 0.7 s ("one partition": a frame per row); the four columns of test_moments at 262 657 rows 0.3 s to 2.0 s, the
+eight at 131 073 rows 0.4 s to 1.4 s, the one call at 263 168 rows 2.5 s.  On the MI355X's host a test_moments id takes 0.2 s to 0.8 s,
+a test_moments_one_call id 0.3 s to 0.9 s, test_moments_read_the_upper_levels_second_stride 0.9 s."""
 import numpy as np
 import pytest
 
+import window_moments_numpy_reference as npref
 from sdqlpy_amd import abi
+from test_window_moments_numpy_cpu import Expected
 from test_window_gpu import KINDS, TERMS, Ranked, _pattern, _raw as _raw_window, _runs, _same, _stage_rows, _table, hip_engine     # noqa: F401 (fixture)
 from test_window_agg_gpu import MEASURES, Framed, _agg, _all_combinations, _raw as _raw_agg
 from test_window_slide_gpu import NAN_BITS, Slid, _bits, _last_of
@@ -564,6 +575,96 @@ def test_exclusions_one_call(cases, size):
     cols = [(SUM,) + RM[0] + (abi.WEX_ROWS, -T, T, 0, CUR), (MAX,) + RM[1] + (GRP, None, 1, -1, GROUP), (AVG,) + RM[0] + (VAL, -2, None, NAN_BITS, TIES),
             (COUNT,) + RM[2] + (abi.WEX_ROWS, None, None, 0, GROUP)]
     assert _check_exclusions(c, Excluded(c.rows, c.terms, 1), [cols]) == 4
+
+
+# 6c. second moments --------------------------------------------------------------------------------------------------------------------------
+def _moment_columns(pattern, size, n, T):
+    """The columns of test_moments at a (pattern, size): one call of four at 262 657 rows, two at 131 073 (the reference costs about a
+    second per column and 262 657 rows).  The frames are test_window_exclude_gpu's 24, rotated by the pattern; the unit turns with the
+    column, the op moves on by one, the measures are the double and the integer payload, alone and in both orders."""
+    fl = _frames(n, T)
+    pi, big = PATTERNS.index(pattern), size == FULL[1]
+    cols = []
+    for k in range(4 if big else 8):
+        lo, hi = fl[(4 * pi + 5 * k + (2 if big else 0)) % len(fl)]
+        y, x = [(RM[0], RM[1]), (RM[1], RM[0]), (RM[0], RM[0]), (RM[1], RM[1])][(k + pi) % 4]
+        cols.append(((3 * pi + k + (4 if big else 0)) % len(npref.OPS),) + y + x + ((VAL, GRP, abi.WEX_ROWS)[(k + pi) % 3], lo, hi))
+    return [cols[i:i + 4] for i in range(0, len(cols), 4)]
+
+
+def _check_moments(c, exc, lists):
+    """every column float64 and equal BY BITS ON EVERY ROW to the numpy restatement of the pinned fold (window_moments_numpy_reference)
+    over the reference's frame ends, the leaves in the reference's row order (the device's is asserted equal to it)"""
+    ctx, t, rows, n = c.ctx, c.t, c.rows, c.n
+    want = Expected(exc)
+    done = 0
+    for cols in lists:
+        got = ctx.table_window_moments(t, 0, 1, c.terms, cols, ALL, n, want_hits=False)
+        _same(got, rows, exc.order, (c.pattern, n, cols))
+        assert len(got[4]) == len(cols)
+        for a, col in zip(got[4], cols):
+            assert a.dtype == np.float64 and len(a) == n, (c.pattern, n, col)
+            w = want.column(col)
+            bad = np.nonzero(npref.bits(a) != npref.bits(w))[0]
+            assert len(bad) == 0, (c.pattern, n, col, len(bad), "first slot", bad[:5], "tile", bad[:5] // c.T, "thread run", bad[:5] // (_geometry(n, c.T)[1] * c.T), a[bad[:5]], w[bad[:5]])
+            done += 1
+    return done
+
+
+def test_moment_columns_meet_every_unit_and_op():
+    met = [col for p in PATTERNS for s in FULL for cols in _moment_columns(p, s, _rows_of(s, 512), 512) for col in cols]
+    assert {col[7] for col in met} == {VAL, GRP, abi.WEX_ROWS} and {col[0] for col in met} == set(range(len(npref.OPS))) and len(met) == 6 * (4 + 8)
+    assert {(col[0], col[7]) for col in met} >= {(op, u) for op in range(len(npref.OPS)) for u in (VAL, GRP)}      # every op under both units that are not ROWS
+    assert len({(col[8], col[9]) for col in met}) >= 20                     # ... over most of the 24 frames
+
+
+@pytest.mark.parametrize("size", FULL)
+@pytest.mark.parametrize("pattern", PATTERNS)
+def test_moments(cases, pattern, size):
+    """VAR / STDDEV / COVAR / CORR / REGR over VALUE, GROUPS and ROWS frames on the tables of test_ranges — ties, heads at the seams,
+    descending on "runs" and SWALLOW —: k_wmo_tiles over 257 and 514 tiles, k_wmo_upper's stride loop, k_wmo_fold's queries above
+    cap = 131072, by bits on every row."""
+    c = cases(pattern, size, ranged=True)
+    exc = Excluded(c.rows, c.terms, 1)
+    lists = _moment_columns(pattern, size, c.n, c.T)
+    assert _check_moments(c, exc, lists) == (4 if size == FULL[1] else 8)
+    if pattern == "one partition":                                          # a frame that passes a node whose right child does not exist
+        assert any(missing for _, missing in _upper_levels(c.n, c.T))
+
+
+@pytest.mark.parametrize("size", LIGHT)
+@pytest.mark.parametrize("pattern", ["one partition", SWALLOW])
+def test_moments_one_call(cases, pattern, size):
+    """a sample deviation behind the row, a correlation over the tie runs around it, a slope over the values from it on, a covariance over
+    the partition up to it"""
+    c = cases(pattern, size, ranged=True)
+    T = c.T
+    cols = [(abi.GM_STDDEV_SAMP,) + RM[0] + RM[0] + (abi.WEX_ROWS, -T, 0), (abi.GM_CORR,) + RM[0] + RM[1] + (GRP, -1, 1), (abi.GM_REGR_SLOPE,) + RM[1] + RM[0] + (VAL, 0, None),
+            (abi.GM_COVAR_POP,) + RM[1] + RM[0] + (abi.WEX_ROWS, None, 0)]
+    assert _check_moments(c, Excluded(c.rows, c.terms, 1), [cols]) == 4
+
+
+def test_moments_read_the_upper_levels_second_stride(cases):
+    """test_ranges_read_the_upper_levels_second_stride for k_wmo_upper: at 2 W T + 2 T rows the 257th live node of its first level lies
+    wholly below n, and the query of a frame that ends at the table's last row reads it (node 512 + 256 at h = 10).  Over the rows
+    compared — all of them — some frame reads a node on every level above the tiles but the root, which no frame shorter than cap can."""
+    c = cases("one partition", "2*W*T+2*T", ranged=True)
+    n, T = c.n, c.T
+    ntiles, per, cap = _geometry(n, T)
+    assert (ntiles, per, cap) == (514, 3, 524288) and _upper_levels(n, T)[0][0] == 257 > W
+    assert all(((cap + n) >> h) % 2 == 0 for h in range(10)) and ((cap + n) >> 10) % 2 == 1 and ((cap + n) >> 10) - 1 == (cap >> 10) + 256
+    exc = Excluded(c.rows, c.terms, 1)
+    cols = [(abi.GM_VAR_SAMP,) + RM[0] + RM[0] + (GRP, 0, None), (abi.GM_REGR_INTERCEPT,) + RM[0] + RM[1] + (abi.WEX_ROWS, None, 0), (abi.GM_CORR,) + RM[1] + RM[0] + (VAL, None, None),
+            (abi.GM_COVAR_SAMP,) + RM[0] + RM[1] + (VAL, -T, T)]
+    left, right, emp = exc.base(GRP, 0, None)
+    assert not emp.any() and (right == n - 1).all() and (left < 2 * W * T).sum() > 2 * W * T - 8      # frames that end at the last row: they read node 512 + 256
+    base, ups = T.bit_length() - 1, len(_upper_levels(n, T))
+    took = 0
+    for col in cols:
+        l, r, e = exc.base(*col[7:])
+        took |= int(np.bitwise_or.reduce(_query_heights(l[~e], r[~e], cap)))
+    assert all((took >> (base + up)) & 1 for up in range(1, ups)) and not (took >> (base + ups)) & 1, bin(took)
+    assert _check_moments(c, exc, [cols]) == 4
 
 
 # 7. general doubles -----------------------------------------------------------------------------------------------------------------------
