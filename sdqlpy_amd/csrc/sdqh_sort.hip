@@ -25,15 +25,23 @@
 // One path behind the table entry points — sdqh_table_sorted, sdqh_table_sorted_by (include/sdqh_sort_terms.h), sdqh_table_window
 // (include/sdqh_sort_window.h), sdqh_table_window_agg (include/sdqh_sort_frames.h), sdqh_table_window_slide
 // (include/sdqh_sort_slide.h), sdqh_table_window_range (include/sdqh_sort_range.h), sdqh_table_window_quantile
-// (include/sdqh_sort_quantile.h) and sdqh_table_window_exclude (include/sdqh_sort_exclude.h): select -> passes -> step -> emit -> fetch
-// (ordered_impl, the spine).  What differs between them
+// (include/sdqh_sort_quantile.h), sdqh_table_window_exclude (include/sdqh_sort_exclude.h), sdqh_table_grouping_sets
+// (include/sdqh_sort_groups.h), sdqh_table_group_distinct (include/sdqh_sort_distinct.h), sdqh_table_group_moments
+// (include/sdqh_sort_moments.h), sdqh_table_sessions (include/sdqh_sort_sessions.h) and sdqh_table_window_moments
+// (include/sdqh_sort_wmoments.h): select -> passes -> step -> emit -> fetch (ordered_impl, the spine).  What differs between them
 // is data, not code: their terms, and ONE step description (SortStep) that the spine hands to one dispatch.  On the host the step
-// is three pieces: the partition pass (Partitions + partition_pass: the arrays every family reads its partitions from, k_win_heads
-// and of k_win_scan / k_wsl_rows / k_wagg_next those the family names), the filter (rank_filter: k_win_rank -> k_sort_scan -> the
-// kept count to the host -> the ways out -> k_win_place; a window filters on its own ranks, quantiles on row numbers) and the family
-// steps (step_ranks / _frames / _slides / _ranges / _quantiles / _excludes: each lays out scratch block 3, runs the pieces above and its own
-// kernels and says where each output column lies).  In front of them the entry points share window_enter, measure_set and
-// fold_class.  On the device:
+// is a few shared pieces — each a small struct whose take() lays its arrays into the family's scratch block, and a function that
+// launches — and the family steps.  The pieces: Tiles (the tiles of a count and the grid that gives each a wave: the one place that
+// arithmetic is written), the partition pass (Partitions + partition_pass: the arrays every window family reads its partitions from,
+// k_win_heads and of k_win_scan / k_wsl_rows / k_wagg_next those the family names), the filter (rank_filter: k_win_rank ->
+// k_sort_scan -> the kept count to the host -> the ways out -> k_win_place; a window filters on its own ranks, quantiles on row
+// numbers), the tile fold (tile_fold: k_wagg_tiles -> k_wagg_scan -> k_wagg_run, over partitions, groups or sessions), the frame
+// pass (Frames + frame_pass / frame_trees: where ranges, excludes and moments over frames find their data-dependent frames and
+// build their fold trees) and the level pass (Levels + level_pass / level_counts / level_sets: the heads and counts of every
+// grouping level, the count to the host and the ways out of the steps that return one row per group).  The family steps (step_ranks
+// / _frames / _slides / _ranges / _quantiles / _excludes / _groups / _distincts / _moments / _sessions / _wmoments) each lay out
+// their scratch blocks, run the pieces above and their own kernels and say where each output column lies.  In front of them the
+// entry points share window_enter, measure_set, fold_class, frame_bounds_ok, frame_image and measure_slot.  On the device:
 //
 //   a TERM            every sort column is a DevSortTerm.  k_sort_keys reads the column (sort_raw) and, for a DERIVED term, takes
 //                     field = (uint64(source) / div) % mod + add and a bounds-checked gather through a ranks column in front of
@@ -2245,6 +2253,13 @@ template <class Layout> bool carve(sdqh_ctx* ctx, void*& slot, Layout layout) {
     return true;
 }
 
+// A wave owns a tile of SORT_TILE consecutive positions: the tiles of `count` positions and the grid that gives each a wave.
+struct Tiles {
+    uint32_t ntiles = 0; unsigned tgrid = 0;
+    Tiles() = default;
+    explicit Tiles(int64_t count) : ntiles((uint32_t)((count + SORT_TILE - 1) / SORT_TILE)), tgrid((ntiles + TPB / WAVE - 1) / (TPB / WAVE)) {}
+};
+
 }  // namespace
 
 extern "C" {
@@ -2256,11 +2271,10 @@ int sdqh_sort_geometry(sdqh_ctx* ctx, int64_t* single_wg_max, int64_t* tile_rows
 }
 
 // one pass of the radix path over `key` at `shift`: perm (nullptr: the identity) -> out
-static void radix_pass(sdqh_ctx* ctx, const uint64_t* key, const uint32_t* perm, uint32_t n, int shift, uint32_t* hist, uint32_t* bin_total, uint32_t ntiles, uint32_t* out) {
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-    LAUNCH(ctx, "k_sort_hist", k_sort_hist, tgrid, key, perm, n, shift, hist, ntiles);
-    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 256, hist, ntiles, bin_total);
-    LAUNCH(ctx, "k_sort_scatter", k_sort_scatter, tgrid, key, perm, n, shift, hist, bin_total, ntiles, out);
+static void radix_pass(sdqh_ctx* ctx, const uint64_t* key, const uint32_t* perm, uint32_t n, int shift, uint32_t* hist, uint32_t* bin_total, const Tiles& t, uint32_t* out) {
+    LAUNCH(ctx, "k_sort_hist", k_sort_hist, t.tgrid, key, perm, n, shift, hist, t.ntiles);
+    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 256, hist, t.ntiles, bin_total);
+    LAUNCH(ctx, "k_sort_scatter", k_sort_scatter, t.tgrid, key, perm, n, shift, hist, bin_total, t.ntiles, out);
 }
 
 // What the first half of an ORDER BY leaves on the device — the references of the selected entries in stage order, the keys of every
@@ -2320,7 +2334,7 @@ static int sort_passes(sdqh_ctx* ctx, const std::string& me, int nsort, Scratch&
         for (int shift = 0; shift < 64; shift += 8) if ((vary >> shift) & 255ull) { pass_col[npass] = c; pass_shift[npass] = shift; ++npass; }
     }
     const uint32_t un = (uint32_t)n;
-    const uint32_t ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE);
+    const Tiles t(n);
     const bool small = n <= SORT_SMALL;
     s.perm = nullptr;
     if (npass) {
@@ -2328,7 +2342,7 @@ static int sort_passes(sdqh_ctx* ctx, const std::string& me, int nsort, Scratch&
         if (!carve(ctx, scratch.p[1], [&](Carver& c) {
                 pa = c.take<uint32_t>((size_t)n);
                 pb = c.take<uint32_t>(small ? 0 : (size_t)n);
-                hist = c.take<uint32_t>(small ? 0 : (size_t)ntiles * 256);
+                hist = c.take<uint32_t>(small ? 0 : (size_t)t.ntiles * 256);
                 bin_total = c.take<uint32_t>(256);
             })) return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory");
         if (small) {
@@ -2336,7 +2350,7 @@ static int sort_passes(sdqh_ctx* ctx, const std::string& me, int nsort, Scratch&
             s.perm = pa;
         } else {
             for (int p = 0; p < npass; ++p) {
-                radix_pass(ctx, s.keys + (size_t)pass_col[p] * s.key_stride, s.perm, un, pass_shift[p], hist, bin_total, ntiles, pa);
+                radix_pass(ctx, s.keys + (size_t)pass_col[p] * s.key_stride, s.perm, un, pass_shift[p], hist, bin_total, t, pa);
                 s.perm = pa; std::swap(pa, pb);
             }
         }
@@ -2404,6 +2418,8 @@ static int sort_rows_fetch(sdqh_ctx* ctx, const SortRows& r, int64_t capacity, i
 // STEP_SESSIONS (sdqh_table_sessions) cuts the partitions of the first npart terms by `ssr` and returns every row (per_session 0) or
 // one row per session — then it filters as STEP_GROUPS does; `ss` are its columns, `aggs` the folds among them.
 // STEP_WMOMENTS (sdqh_table_window_moments) returns every row with `wm`'s columns: frames as STEP_EXCLUDES finds them, moments in them.
+// Behind the dispatch a step is built from shared pieces: the partition pass (Partitions), the filter (rank_filter), the tile fold
+// (tile_fold), the frame pass of `rg` / `ex.rg` / `wm.rg` (Frames) and the level pass of `levels` / `ngroup` (Levels); see each.
 enum StepKind { STEP_NONE, STEP_RANKS, STEP_FRAMES, STEP_SLIDES, STEP_RANGES, STEP_QUANTILES, STEP_EXCLUDES, STEP_GROUPS, STEP_DISTINCTS, STEP_MOMENTS, STEP_SESSIONS, STEP_WMOMENTS };
 struct SortStep {
     StepKind kind; int npart;
@@ -2440,17 +2456,22 @@ struct StepRun {
     int done(int64_t rows) { *out_n = rows; call_end(ctx); ended = true; return SDQH_OK; }
     int overflow(int64_t rows) { *out_n = rows; call_end(ctx); ended = true; return fail(ctx, SDQH_ERR_OVERFLOW, me + ": capacity too small"); }
     int nomem() const { return fail(ctx, SDQH_ERR_NOMEM, me + ": out of device memory"); }
+    // a step that returns groups knows its count only now: m, and the ways out again (taken: `ended`)
+    int counted(int64_t rows) {
+        m = std::min<int64_t>(limit, rows);
+        if (count_only) return done(m);
+        return m > capacity ? overflow(m) : SDQH_OK;
+    }
 };
 
 // The partition pass: the arrays every family reads its partitions from — out of the family's block 3 (take() inside its layout):
 // head flags and tile carries always, the others as its kernels read them (an array not asked for takes no bytes) — and the kernels
 // that fill them: `what` of the four, in this order.  A family whose own kernels come in between asks twice: frames fill the first
 // heads themselves (k_wagg_tiles), quantiles filter behind PP_SCAN and mark tie heads (k_wq_ties) in front of PP_NEXT.
-struct Partitions {
-    uint32_t ntiles = 0; unsigned tgrid = 0;                          // a wave per tile of SORT_TILE sorted positions
+struct Partitions : Tiles {                                           // (the tiles of the n sorted positions)
     uint8_t* heads = nullptr; WinCarry* carry = nullptr; uint32_t* rown = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
     void take(Carver& c, int64_t n, bool rows, bool firsts, bool nexts) {
-        ntiles = (uint32_t)((n + SORT_TILE - 1) / SORT_TILE); tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+        static_cast<Tiles&>(*this) = Tiles(n);
         heads = c.take<uint8_t>((size_t)n);
         carry = c.take<WinCarry>(ntiles);
         rown = c.take<uint32_t>(rows ? (size_t)n : 0);
@@ -2464,6 +2485,15 @@ static void partition_pass(const StepRun& r, const Partitions& p, int what) {
     if (what & PP_SCAN) LAUNCH(r.ctx, "k_win_scan", k_win_scan, 1, p.carry, p.ntiles);
     if (what & PP_ROWS) LAUNCH(r.ctx, "k_wsl_rows", k_wsl_rows, p.tgrid, p.heads, p.carry, r.un, p.rown, p.tfirst, p.ntiles);
     if (what & PP_NEXT) LAUNCH(r.ctx, "k_wagg_next", k_wagg_next, 1, p.tfirst, r.un, p.tnext, p.ntiles);
+}
+
+// The tile fold of the frames, over whatever head flags cut the rows (partitions, the highest level's groups, sessions): every
+// fold's element of every position and the tiles' carries and first heads, the carries scanned and — `run` — the running value of
+// every position in place of its element.  Without `run` the carries are left for k_gs_run, which keeps a group's last value.
+static void tile_fold(const StepRun& r, const Tiles& t, const DevWaggs& ag, const uint8_t* heads, uint64_t* elem, uint64_t* tval, WaggHeads* tfirst, bool run) {
+    LAUNCH(r.ctx, "k_wagg_tiles", k_wagg_tiles, t.tgrid, r.table->stage, ag, r.s.refs, r.s.perm, heads, r.un, r.stride, elem, tval, tfirst, t.ntiles);
+    LAUNCH(r.ctx, "k_wagg_scan", k_wagg_scan, (unsigned)ag.n, ag, tfirst, r.un, tval, t.ntiles);
+    if (run) LAUNCH(r.ctx, "k_wagg_run", k_wagg_run, t.tgrid, ag, heads, r.un, r.stride, elem, tval, t.ntiles);
 }
 
 // The filter (behind PP_SCAN): the step's rank of every position into `rank`, the positions with rank <= per_limit counted per tile;
@@ -2485,6 +2515,69 @@ static int rank_filter(StepRun& r, const Partitions& p, uint32_t* rank, uint32_t
     LAUNCH(ctx, "k_win_place", k_win_place, p.tgrid, rank, r.un, pl, tile_kept, p.ntiles, sel, (uint32_t)r.m);
     r.sel = sel;
     return SDQH_OK;
+}
+
+// The frame pass: where the data-dependent frames of ranges, excludes and moments over frames are found.  Its constructor reads the
+// family's DevWranges image — a folded column's tree slot, a FIRST / LAST column's element slot, is there a GROUPS column, does a
+// column exclude its GROUP or TIES (`exclude`: excludes alone have one), a ROWS offset clamped as a slide's is — take() lays
+// [partition pass | partition ends | dense ranks | kept per tile | tie-run ranks | kept per tile of that pass | tie-run ends | VALUE
+// keys | GROUPS keys] in front of the family's own arrays (an array nobody asked for takes no bytes and is null), and frame_pass fills
+// them; frame_trees builds the fold trees of the folded columns bottom-up.
+struct Frames {
+    Partitions p;
+    int nfold = 0, nraw = 0; bool groups = false, ties = false;
+    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
+    size_t tstride = 0;                                                // a fold tree: nodes [1, cap), leaves [cap, 2 cap)
+    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr, *frank = nullptr, *fkept = nullptr, *tend = nullptr;
+    uint64_t *vkey = nullptr, *gkey = nullptr;
+    Frames(DevWranges& rg, int64_t n, const int32_t* exclude) {
+        for (int a = 0; a < rg.n; ++a) {
+            DevWrange& d = rg.a[a];
+            d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
+            groups |= d.unit == SDQH_WRANGE_GROUPS;
+            ties |= exclude && (exclude[a] == SDQH_WEX_GROUP || exclude[a] == SDQH_WEX_TIES);
+            if (d.unit == SDQH_WEX_ROWS) {                             // an offset of n or more reaches outside every partition: clamped, as a slide's is
+                d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
+                d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
+            }
+        }
+        while (cap < (uint64_t)n) cap <<= 1;
+        tstride = nfold ? (size_t)(2 * cap) : 0;
+    }
+    void take(Carver& c, int64_t n, const DevWranges& rg) {
+        p.take(c, n, true, true, true);
+        pend = c.take<uint32_t>((size_t)n);
+        dense = c.take<uint32_t>(groups ? (size_t)n : 0);
+        tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
+        frank = c.take<uint32_t>(ties ? (size_t)n : 0);
+        fkept = c.take<uint32_t>(ties ? p.ntiles : 0);
+        tend = c.take<uint32_t>(ties ? (size_t)n : 0);
+        vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
+        gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+        if (rg.vcol < 0) vkey = nullptr;
+        if (!groups) { dense = nullptr; gkey = nullptr; }
+        if (!ties) { frank = nullptr; tend = nullptr; }
+    }
+};
+// partitions, rows and ends; with ties the first tie heads, tie-run ranks and ends; with a GROUPS column the dense ranks; then
+// k_wrg_stage: the partitions' ends, the frames' keys, and the columns' elements — raw into `elem`, leaves into `tree` (both null: none)
+static void frame_pass(const StepRun& r, const Frames& f, const DevWranges& rg, uint64_t* elem, uint64_t* tree) {
+    const Partitions& p = f.p;
+    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS);
+    if (f.ties) LAUNCH(r.ctx, "k_wq_ties", k_wq_ties, p.tgrid, p.heads, r.un, p.tfirst, p.ntiles);
+    partition_pass(r, p, PP_NEXT);
+    if (f.groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, f.dense, f.tile_kept, p.ntiles);
+    if (f.ties) {
+        LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_RANK, ~0ull, f.frank, f.fkept, p.ntiles);
+        LAUNCH(r.ctx, "k_wex_ties", k_wex_ties, p.tgrid, p.heads, p.tnext, r.un, f.tend, p.ntiles);
+    }
+    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, f.dense, r.un,
+           r.stride, f.tstride, f.cap, f.pend, f.vkey, f.gkey, elem, tree, p.ntiles);
+}
+static void frame_trees(const StepRun& r, const Frames& f, const DevWranges& rg, uint64_t* tree) {
+    if (!f.nfold) return;
+    LAUNCH(r.ctx, "k_wrg_tiles", k_wrg_tiles, f.p.tgrid, rg, r.un, f.tstride, f.cap, tree, f.p.ntiles);
+    if (f.cap > (uint64_t)SORT_TILE) LAUNCH(r.ctx, "k_wrg_upper", k_wrg_upper, (unsigned)f.nfold, rg, f.tstride, f.cap, tree, f.p.ntiles);
 }
 
 // The family steps.  Each carves block 3 (scratch.p[3]: one pool block per call, the partition pass's arrays and its own in one
@@ -2521,13 +2614,11 @@ static int step_frames(StepRun& r) {
             tval = c.take<uint64_t>((size_t)p.ntiles * na);
         })) return r.nomem();
     partition_pass(r, p, PP_HEADS);
-    LAUNCH(r.ctx, "k_wagg_tiles", k_wagg_tiles, p.tgrid, r.table->stage, ag, r.s.refs, r.s.perm, p.heads, r.un, r.stride, elem, tval, p.tfirst, p.ntiles);
-    LAUNCH(r.ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, p.tfirst, r.un, tval, p.ntiles);
-    LAUNCH(r.ctx, "k_wagg_run", k_wagg_run, p.tgrid, ag, p.heads, r.un, r.stride, elem, tval, p.ntiles);
+    tile_fold(r, p, ag, p.heads, elem, tval, p.tfirst, true);
     if (ends) {
-        const uint32_t mtiles = (uint32_t)((r.m + SORT_TILE - 1) / SORT_TILE);
+        const Tiles mt(r.m);                                          // (the returned rows' tiles)
         partition_pass(r, p, PP_NEXT);
-        LAUNCH(r.ctx, "k_wagg_ends", k_wagg_ends, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), ag, p.heads, p.tnext, r.un, (uint32_t)r.m, r.stride, elem, fin, mtiles);
+        LAUNCH(r.ctx, "k_wagg_ends", k_wagg_ends, mt.tgrid, ag, p.heads, p.tnext, r.un, (uint32_t)r.m, r.stride, elem, fin, mt.ntiles);
     }
     r.columns(elem, ag.n);                                            // each from the array its frame left it in
     for (int a = 0; a < ag.n; ++a) if (ag.a[a].frame != SDQH_FRAME_ROWS) r.col_src[a] = fin + (size_t)a * r.stride;
@@ -2574,46 +2665,21 @@ static int step_slides(StepRun& r) {
     return SDQH_OK;
 }
 
-// Values over value and group frames (sdqh_table_window_range): block 3 = [partition pass | partition ends | dense ranks | kept per
-// tile | VALUE keys | GROUPS keys | raw elements, an array per FIRST / LAST range | fold trees, one per folded range | values]
+// Values over value and group frames (sdqh_table_window_range): block 3 = [frame pass | raw elements, an array per FIRST / LAST
+// range | fold trees, one per folded range (SUM / MIN / MAX) | values]
 static int step_ranges(StepRun& r) {
-    const int64_t n = r.n;
     DevWranges rg = r.step.rg;
-    const size_t na = (size_t)rg.n;
-    int nfold = 0, nraw = 0; bool groups = false;                     // folded ranges (SUM / MIN / MAX), FIRST / LAST ranges, any GROUPS range
-    for (size_t a = 0; a < na; ++a) {
-        DevWrange& d = rg.a[a];
-        d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
-        groups |= d.unit == SDQH_WRANGE_GROUPS;
-    }
-    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
-    while (cap < (uint64_t)n) cap <<= 1;
-    const size_t tstride = nfold ? (size_t)(2 * cap) : 0;              // a tree: nodes [1, cap), leaves [cap, 2 cap)
-    Partitions p;
-    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
-    uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr;
+    Frames f(rg, r.n, nullptr);
+    uint64_t *elem = nullptr, *tree = nullptr, *fin = nullptr;
     if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
-            p.take(c, n, true, true, true);
-            pend = c.take<uint32_t>((size_t)n);
-            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
-            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
-            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
-            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
-            elem = c.take<uint64_t>(r.stride * (size_t)nraw);
-            tree = c.take<uint64_t>(tstride * (size_t)nfold);
-            fin = c.take<uint64_t>(r.stride * na);
+            f.take(c, r.n, rg);
+            elem = c.take<uint64_t>(r.stride * (size_t)f.nraw);
+            tree = c.take<uint64_t>(f.tstride * (size_t)f.nfold);
+            fin = c.take<uint64_t>(r.stride * (size_t)rg.n);
         })) return r.nomem();
-    if (rg.vcol < 0) vkey = nullptr;
-    if (!groups) { dense = nullptr; gkey = nullptr; }
-    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS | PP_NEXT);
-    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
-    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
-           r.stride, tstride, cap, pend, vkey, gkey, elem, tree, p.ntiles);
-    if (nfold) {
-        LAUNCH(r.ctx, "k_wrg_tiles", k_wrg_tiles, p.tgrid, rg, r.un, tstride, cap, tree, p.ntiles);
-        if (cap > (uint64_t)SORT_TILE) LAUNCH(r.ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, p.ntiles);
-    }
-    LAUNCH(r.ctx, "k_wrg_fold", k_wrg_fold, r.row_grid(), rg, p.rown, pend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, elem, tree, fin);
+    frame_pass(r, f, rg, elem, tree);
+    frame_trees(r, f, rg, tree);
+    LAUNCH(r.ctx, "k_wrg_fold", k_wrg_fold, r.row_grid(), rg, f.p.rown, f.pend, f.vkey, f.gkey, r.un, (uint32_t)r.m, r.stride, f.tstride, f.cap, elem, tree, fin);
     r.columns(fin, rg.n);
     return SDQH_OK;
 }
@@ -2661,135 +2727,109 @@ static int step_quantiles(StepRun& r) {
     return SDQH_OK;
 }
 
-// Values over frames with rows taken out (sdqh_table_window_exclude): block 3 = [partition pass | partition ends | dense ranks | kept
-// per tile | tie-run ranks | kept per tile of that pass | tie-run ends | VALUE keys | GROUPS keys | raw elements, an array per FIRST /
-// LAST column | fold trees, one per folded column (SUM / MIN / MAX / AVG) | values] — the dense ranks and the GROUPS keys only with a
-// GROUPS column, the VALUE keys only with a VALUE column, the tie arrays only when some column excludes GROUP or TIES.  The trees and
-// the keys are the ranges': k_wrg_stage / _tiles / _upper over the columns' DevWranges image.
+// Values over frames with rows taken out (sdqh_table_window_exclude): block 3 = [frame pass, its tie arrays when some column excludes
+// GROUP or TIES | raw elements, an array per FIRST / LAST column | fold trees, one per folded column (SUM / MIN / MAX / AVG) | values].
+// The trees and the keys are the ranges': the frame pass over the columns' DevWranges image.
 static int step_excludes(StepRun& r) {
-    const int64_t n = r.n;
     DevWexs ex = r.step.ex;
     DevWranges& rg = ex.rg;
-    const size_t na = (size_t)rg.n;
-    int nfold = 0, nraw = 0; bool groups = false, ties = false;      // folded columns, FIRST / LAST columns, any GROUPS column, any GROUP / TIES exclusion
-    for (size_t a = 0; a < na; ++a) {
-        DevWrange& d = rg.a[a];
-        d.slot = d.g.cls != WSL_NONE ? nfold++ : (d.g.op != SDQH_WAGG_COUNT ? nraw++ : 0);
-        groups |= d.unit == SDQH_WRANGE_GROUPS;
-        ties |= ex.exclude[a] == SDQH_WEX_GROUP || ex.exclude[a] == SDQH_WEX_TIES;
-        if (d.unit == SDQH_WEX_ROWS) {                                 // an offset of n or more reaches outside every partition: clamped, as a slide's is
-            d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
-            d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
-        }
-    }
-    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
-    while (cap < (uint64_t)n) cap <<= 1;
-    const size_t tstride = nfold ? (size_t)(2 * cap) : 0;
-    Partitions p;
-    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr, *frank = nullptr, *fkept = nullptr, *tend = nullptr;
-    uint64_t *vkey = nullptr, *gkey = nullptr, *elem = nullptr, *tree = nullptr, *fin = nullptr;
+    Frames f(rg, r.n, ex.exclude);
+    uint64_t *elem = nullptr, *tree = nullptr, *fin = nullptr;
     if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
-            p.take(c, n, true, true, true);
-            pend = c.take<uint32_t>((size_t)n);
-            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
-            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
-            frank = c.take<uint32_t>(ties ? (size_t)n : 0);
-            fkept = c.take<uint32_t>(ties ? p.ntiles : 0);
-            tend = c.take<uint32_t>(ties ? (size_t)n : 0);
-            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
-            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
-            elem = c.take<uint64_t>(r.stride * (size_t)nraw);
-            tree = c.take<uint64_t>(tstride * (size_t)nfold);
-            fin = c.take<uint64_t>(r.stride * na);
+            f.take(c, r.n, rg);
+            elem = c.take<uint64_t>(r.stride * (size_t)f.nraw);
+            tree = c.take<uint64_t>(f.tstride * (size_t)f.nfold);
+            fin = c.take<uint64_t>(r.stride * (size_t)rg.n);
         })) return r.nomem();
-    if (rg.vcol < 0) vkey = nullptr;
-    if (!groups) { dense = nullptr; gkey = nullptr; }
-    if (!ties) { frank = nullptr; tend = nullptr; }
-    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS);
-    if (ties) LAUNCH(r.ctx, "k_wq_ties", k_wq_ties, p.tgrid, p.heads, r.un, p.tfirst, p.ntiles);
-    partition_pass(r, p, PP_NEXT);
-    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
-    if (ties) {
-        LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_RANK, ~0ull, frank, fkept, p.ntiles);
-        LAUNCH(r.ctx, "k_wex_ties", k_wex_ties, p.tgrid, p.heads, p.tnext, r.un, tend, p.ntiles);
-    }
-    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
-           r.stride, tstride, cap, pend, vkey, gkey, elem, tree, p.ntiles);
-    if (nfold) {
-        LAUNCH(r.ctx, "k_wrg_tiles", k_wrg_tiles, p.tgrid, rg, r.un, tstride, cap, tree, p.ntiles);
-        if (cap > (uint64_t)SORT_TILE) LAUNCH(r.ctx, "k_wrg_upper", k_wrg_upper, (unsigned)nfold, rg, tstride, cap, tree, p.ntiles);
-    }
-    LAUNCH(r.ctx, "k_wex_fold", k_wex_fold, r.row_grid(), ex, p.rown, pend, frank, tend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, elem, tree, fin);
+    frame_pass(r, f, rg, elem, tree);
+    frame_trees(r, f, rg, tree);
+    LAUNCH(r.ctx, "k_wex_fold", k_wex_fold, r.row_grid(), ex, f.p.rown, f.pend, f.frank, f.tend, f.vkey, f.gkey, r.un, (uint32_t)r.m, r.stride, f.tstride, f.cap, elem, tree, fin);
     r.columns(fin, rg.n);
     return SDQH_OK;
 }
 
-// Groups at nested levels (sdqh_table_grouping_sets).  Block 3 = [depths | head flags of the highest level | heads per tile and level
-// | level counts]: what the level pass needs.  The counts go to the host — the call's second wait, as a filter's — and the ways out
-// are taken; only then is the output's size known: block 4 = [representatives' positions | their depths | group values | the rows'
-// elements | value carries | first heads | heads per tile | their total], the first three over all g groups, highest level first.
-static int step_groups(StepRun& r) {
-    sdqh_ctx* ctx = r.ctx;
-    const int nl = r.nsort + 1;
-    const uint32_t levels = r.step.levels;
-    int top = r.nsort;
-    while (!((levels >> top) & 1u)) --top;                            // (levels != 0 and no bit above nsort: the entry point's check)
-    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+// The level pass: the steps that return one row per group find the heads of every level of the nsort terms at once.  Block 3 =
+// [depths | head flags of level `top` | heads per tile and level | level counts], laid out and filled by level_pass: k_gs_depth, then
+// level_counts — the tiles' heads scanned per level in place (k_sort_bins, a workgroup a level: a level's tile offsets), the level
+// counts to the host (the call's second wait, as a filter's) into tot[].  level_sets is what groups and moments make of them.
+struct Levels : Tiles {                                               // (the tiles of the n sorted positions)
+    int nl = 0, top = 0;                                              // nsort + 1 levels; the highest one the call reads
     uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
-    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
-            depth = c.take<uint8_t>((size_t)r.n);
-            heads = c.take<uint8_t>((size_t)r.n);
-            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
-            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
-        })) return r.nomem();
-    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
+    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];                             // level L's groups
+    DevGsLevels lv; int lvl[SDQH_SORT_MAX_KEYS + 1]; int64_t g = 0;   // level_sets: the levels asked for, highest first; their groups in all
+    const uint32_t* offsets(int L) const { return tcount + (size_t)L * ntiles; }
+};
+static int level_counts(StepRun& r, uint32_t* tcount, uint32_t ntiles, uint32_t* ltot, int nl, uint32_t* tot) {
+    sdqh_ctx* ctx = r.ctx;
     LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);      // per level: the tiles' offsets in place, the level's count
     HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (int rc = sync_stream(ctx)) return rc;
-    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
     std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
-    DevGsLevels lv; std::memset(&lv, 0, sizeof(lv));
-    int lvl[SDQH_SORT_MAX_KEYS + 1];
-    int64_t g = 0;
-    for (int L = top; L >= 0; --L) if ((levels >> L) & 1u) { lvl[lv.n] = L; g += (int64_t)tot[L]; lv.off[++lv.n] = (uint32_t)g; }
-    if (g > 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 groups over the levels asked for");
-    if (r.step.level_rows) for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) r.step.level_rows[L] = (L < nl && ((levels >> L) & 1u)) ? (int64_t)tot[L] : 0;
-    r.m = std::min<int64_t>(r.limit, g);
-    if (r.count_only) return r.done(r.m);
-    if (r.m > r.capacity) return r.overflow(r.m);
+    return SDQH_OK;
+}
+static int level_pass(StepRun& r, Levels& p, int top) {
+    static_cast<Tiles&>(p) = Tiles(r.n);
+    p.nl = r.nsort + 1; p.top = top;
+    if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
+            p.depth = c.take<uint8_t>((size_t)r.n);
+            p.heads = c.take<uint8_t>((size_t)r.n);
+            p.tcount = c.take<uint32_t>((size_t)p.ntiles * (size_t)p.nl);
+            p.ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
+        })) return r.nomem();
+    LAUNCH(r.ctx, "k_gs_depth", k_gs_depth, p.tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, p.depth, p.heads, p.tcount, p.ntiles);
+    return level_counts(r, p.tcount, p.ntiles, p.ltot, p.nl, p.tot);
+}
+// The level pass up to the highest of the step's `levels`, then the levels asked for from the highest down — lvl[k], its groups rows
+// [lv.off[k], lv.off[k + 1]) of the output, g in all —, their counts to level_rows, and the ways out (r.counted).
+static int level_sets(StepRun& r, Levels& p) {
+    const uint32_t levels = r.step.levels;
+    int top = r.nsort;
+    while (!((levels >> top) & 1u)) --top;                            // (levels != 0 and no bit above nsort: the entry point's check)
+    if (int rc = level_pass(r, p, top)) return rc;
+    std::memset(&p.lv, 0, sizeof(p.lv));
+    for (int L = top; L >= 0; --L) if ((levels >> L) & 1u) { p.lvl[p.lv.n] = L; p.g += (int64_t)p.tot[L]; p.lv.off[++p.lv.n] = (uint32_t)p.g; }
+    if (p.g > 0xFFFFFFFFll) return fail(r.ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 groups over the levels asked for");
+    if (r.step.level_rows) for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) r.step.level_rows[L] = (L < p.nl && ((levels >> L) & 1u)) ? (int64_t)p.tot[L] : 0;
+    return r.counted(p.g);
+}
+
+// Groups at nested levels (sdqh_table_grouping_sets).  Block 3 is the level pass's; only behind its ways out is the output's size
+// known: block 4 = [representatives' positions | their depths | group values | the rows' elements | value carries | first heads |
+// heads per tile | their total], the first three over all g groups, highest level first.
+static int step_groups(StepRun& r) {
+    sdqh_ctx* ctx = r.ctx;
+    Levels p;
+    const int rc = level_sets(r, p);
+    if (rc || r.ended) return rc;
+    const DevGsLevels& lv = p.lv;
     DevWaggs ag = r.step.aggs;
     if (!r.step.out) ag.n = 0;                                        // rows only: nothing is folded
-    const size_t na = (size_t)ag.n, gstride = round_up((size_t)g * 8) / 8;
+    const size_t na = (size_t)ag.n, gstride = round_up((size_t)p.g * 8) / 8;
     uint32_t *sel = nullptr, *tcnt = nullptr, *tot1 = nullptr; uint8_t* gdepth = nullptr;
     uint64_t *fin = nullptr, *elem = nullptr, *tval = nullptr; WaggHeads* tfirst = nullptr;
     if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
-            sel = c.take<uint32_t>((size_t)g);
-            gdepth = c.take<uint8_t>((size_t)g);
+            sel = c.take<uint32_t>((size_t)p.g);
+            gdepth = c.take<uint8_t>((size_t)p.g);
             fin = c.take<uint64_t>(gstride * na);
             elem = c.take<uint64_t>(r.stride * na);
-            tval = c.take<uint64_t>((size_t)ntiles * na);
-            tfirst = c.take<WaggHeads>(ntiles);
-            tcnt = c.take<uint32_t>(ntiles);
+            tval = c.take<uint64_t>((size_t)p.ntiles * na);
+            tfirst = c.take<WaggHeads>(p.ntiles);
+            tcnt = c.take<uint32_t>(p.ntiles);
             tot1 = c.take<uint32_t>(1);
         })) return r.nomem();
     // the highest level, over the rows
-    if (na) {
-        LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, heads, r.un, r.stride, elem, tval, tfirst, ntiles);
-        LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, r.un, tval, ntiles);
-    }
-    LAUNCH(ctx, "k_gs_run", k_gs_run, tgrid, ag, top, 1, depth, (const uint32_t*)nullptr, elem, r.stride, r.un, tval, tcount + (size_t)top * ntiles, ntiles,
-           fin, gstride, gdepth, sel, tot[top]);
+    if (na) tile_fold(r, p, ag, p.heads, elem, tval, tfirst, false);
+    LAUNCH(ctx, "k_gs_run", k_gs_run, p.tgrid, ag, p.top, 1, p.depth, (const uint32_t*)nullptr, elem, r.stride, r.un, tval, p.offsets(p.top), p.ntiles,
+           fin, gstride, gdepth, sel, p.tot[p.top]);
     // every lower level, over the groups of the one above it
     for (int k = 1; k < lv.n; ++k) {
-        const uint32_t nf = tot[lvl[k - 1]], nt = (nf + SORT_TILE - 1) / SORT_TILE;
-        const unsigned fgrid = (nt + TPB / WAVE - 1) / (TPB / WAVE);
-        const uint32_t from = lv.off[k - 1], to = lv.off[k];
-        LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, fgrid, ag, lvl[k], gdepth + from, fin + from, gstride, nf, tval, tfirst, tcnt, nt);
-        if (na) LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, nf, tval, nt);
-        LAUNCH(ctx, "k_sort_bins", k_sort_bins, 1, tcnt, nt, tot1);
-        LAUNCH(ctx, "k_gs_run", k_gs_run, fgrid, ag, lvl[k], 0, gdepth + from, sel + from, fin + from, gstride, nf, tval, tcnt, nt,
-               fin + to, gstride, gdepth + to, sel + to, tot[lvl[k]]);
+        const uint32_t nf = p.tot[p.lvl[k - 1]], from = lv.off[k - 1], to = lv.off[k];
+        const Tiles ft(nf);                                           // SORT_TILE groups of the level above each
+        LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, ft.tgrid, ag, p.lvl[k], gdepth + from, fin + from, gstride, nf, tval, tfirst, tcnt, ft.ntiles);
+        if (na) LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, nf, tval, ft.ntiles);
+        LAUNCH(ctx, "k_sort_bins", k_sort_bins, 1, tcnt, ft.ntiles, tot1);
+        LAUNCH(ctx, "k_gs_run", k_gs_run, ft.tgrid, ag, p.lvl[k], 0, gdepth + from, sel + from, fin + from, gstride, nf, tval, tcnt, ft.ntiles,
+               fin + to, gstride, gdepth + to, sel + to, p.tot[p.lvl[k]]);
     }
     bool avg = false;
     for (size_t a = 0; a < na; ++a) avg |= r.step.avg.avg[a] != 0;
@@ -2799,38 +2839,24 @@ static int step_groups(StepRun& r) {
     return SDQH_OK;
 }
 
-// Aggregates over the distinct values of a group (sdqh_table_group_distinct).  Block 3 = step_groups' [depths | head flags of level
-// nsort | heads per tile and level | level counts].  The counts of runs (level nsort) and groups (level ngroup) go to the host — the
-// call's second wait — and the ways out are taken.  Block 4 = [runs: positions | depths | elements] [groups: first runs | depths |
-// values | positions] [the upper stage's value carries | first heads | heads per tile | their total].
+// Aggregates over the distinct values of a group (sdqh_table_group_distinct).  Block 3 is the level pass's, up to level nsort.  Of
+// its counts the step reads two, the runs' (level nsort) and the groups' (level ngroup), and takes the ways out.  Block 4 = [runs:
+// positions | depths | elements] [groups: first runs | depths | values | positions] [the upper stage's value carries | first heads |
+// heads per tile | their total].
 static int step_distincts(StepRun& r) {
     sdqh_ctx* ctx = r.ctx;
-    const int nl = r.nsort + 1, top = r.nsort, L = r.step.ngroup;
-    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-    uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
-    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
-            depth = c.take<uint8_t>((size_t)r.n);
-            heads = c.take<uint8_t>((size_t)r.n);
-            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
-            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
-        })) return r.nomem();
-    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
-    LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = sync_stream(ctx)) return rc;
-    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
-    std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
-    const uint32_t nr = tot[top], ng = tot[L];                        // value runs, groups: 1 <= ng <= nr <= n
-    r.m = std::min<int64_t>(r.limit, (int64_t)ng);
-    if (r.count_only) return r.done(r.m);
-    if (r.m > r.capacity) return r.overflow(r.m);
+    const int top = r.nsort, L = r.step.ngroup;
+    Levels p;
+    if (int rc = level_pass(r, p, top)) return rc;
+    const uint32_t nr = p.tot[top], ng = p.tot[L];                    // value runs, groups: 1 <= ng <= nr <= n
+    const int rc = r.counted((int64_t)ng);
+    if (rc || r.ended) return rc;
     DevWaggs ag = r.step.aggs;
     DevGdAggs gd = r.step.gd;
     if (!r.step.out) ag.n = gd.n = 0;                                 // rows only: nothing is folded
     const size_t na = (size_t)ag.n, rstride = round_up((size_t)nr * 8) / 8, gstride = round_up((size_t)ng * 8) / 8;
-    const uint32_t nt = (nr + SORT_TILE - 1) / SORT_TILE;             // the upper stage's tiles: SORT_TILE runs each
-    const unsigned fgrid = (nt + TPB / WAVE - 1) / (TPB / WAVE);
+    const Tiles ft(nr);                                               // the upper stage's tiles: SORT_TILE runs each
+    const uint32_t nt = ft.ntiles;
     uint32_t *rpos = nullptr, *gfirst = nullptr, *sel = nullptr, *tcnt = nullptr, *tot1 = nullptr; uint8_t *rdepth = nullptr, *gdepth = nullptr;
     uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr; WaggHeads* tfirst = nullptr;
     if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
@@ -2848,53 +2874,30 @@ static int step_distincts(StepRun& r) {
         })) return r.nomem();
     // the lower stage: rows -> value runs
     const unsigned rgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((int64_t)nr + TPB - 1) / TPB, (int64_t)ctx->num_cu * 8));
-    LAUNCH(ctx, "k_gd_heads", k_gd_heads, tgrid, top, depth, r.un, tcount + (size_t)top * ntiles, ntiles, rpos, rdepth, nr);
+    LAUNCH(ctx, "k_gd_heads", k_gd_heads, p.tgrid, top, p.depth, r.un, p.offsets(top), p.ntiles, rpos, rdepth, nr);
     if (na) LAUNCH(ctx, "k_gd_elems", k_gd_elems, rgrid, r.table->stage, gd, r.s.refs, r.s.perm, rpos, r.un, nr, rstride, elem);
     // the upper stage: value runs -> groups, a lower level of the grouping sets over the runs (positions: run indices)
-    LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, fgrid, ag, L, rdepth, elem, rstride, nr, tval, tfirst, tcnt, nt);
+    LAUNCH(ctx, "k_gs_tiles", k_gs_tiles, ft.tgrid, ag, L, rdepth, elem, rstride, nr, tval, tfirst, tcnt, nt);
     if (na) LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)na, ag, tfirst, nr, tval, nt);
     LAUNCH(ctx, "k_sort_bins", k_sort_bins, 1, tcnt, nt, tot1);
-    LAUNCH(ctx, "k_gs_run", k_gs_run, fgrid, ag, L, 0, rdepth, (const uint32_t*)nullptr, elem, rstride, nr, tval, tcnt, nt, fin, gstride, gdepth, gfirst, ng);
+    LAUNCH(ctx, "k_gs_run", k_gs_run, ft.tgrid, ag, L, 0, rdepth, (const uint32_t*)nullptr, elem, rstride, nr, tval, tcnt, nt, fin, gstride, gdepth, gfirst, ng);
     LAUNCH(ctx, "k_gd_finish", k_gd_finish, r.row_grid(), r.table->stage, gd, r.s.refs, r.s.perm, rpos, gfirst, r.un, nr, ng, (uint32_t)r.m, gstride, fin, sel);
     r.sel = sel;
     for (r.ncols = 0; r.ncols < ag.n; ++r.ncols) r.col_src[r.ncols] = fin + (size_t)r.ncols * gstride;
     return SDQH_OK;
 }
 
-// Second moments per group (sdqh_table_group_moments).  Block 3 = step_groups' [depths | head flags of the highest level | heads per
-// tile and level | level counts]; the level counts go to the host and the ways out are taken as there.  Block 4 = [groups: positions |
-// depths | pass 1's sums | pass 2's sums | results] [rows: staged measures | centred products] [value carries | first heads | heads
-// per tile].  Every level asked for is folded over the rows, its tile offsets k_sort_bins' (tcount).
+// Second moments per group (sdqh_table_group_moments).  Block 3 is the level pass's, the levels and the ways out step_groups'.
+// Block 4 = [groups: positions | depths | pass 1's sums | pass 2's sums | results] [rows: staged measures | centred products] [value
+// carries | first heads | heads per tile].  Every level asked for is folded over the rows, its tile offsets the level pass's.
 static int step_moments(StepRun& r) {
     sdqh_ctx* ctx = r.ctx;
-    const int nl = r.nsort + 1;
-    const uint32_t levels = r.step.levels;
-    int top = r.nsort;
-    while (!((levels >> top) & 1u)) --top;                            // (levels != 0 and no bit above nsort: the entry point's check)
-    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-    uint8_t *depth = nullptr, *heads = nullptr; uint32_t *tcount = nullptr, *ltot = nullptr;
-    if (!carve(ctx, r.scratch.p[3], [&](Carver& c) {
-            depth = c.take<uint8_t>((size_t)r.n);
-            heads = c.take<uint8_t>((size_t)r.n);
-            tcount = c.take<uint32_t>((size_t)ntiles * (size_t)nl);
-            ltot = c.take<uint32_t>(SDQH_SORT_MAX_KEYS + 1);
-        })) return r.nomem();
-    LAUNCH(ctx, "k_gs_depth", k_gs_depth, tgrid, r.s.keys, r.s.key_stride, r.nsort, top, r.s.perm, r.un, depth, heads, tcount, ntiles);
-    LAUNCH(ctx, "k_sort_bins", k_sort_bins, (unsigned)nl, tcount, ntiles, ltot);      // per level: the tiles' offsets in place, the level's count
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, (size_t)nl * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = sync_stream(ctx)) return rc;
-    uint32_t tot[SDQH_SORT_MAX_KEYS + 1];
-    std::memcpy(tot, ctx->result_host, (size_t)nl * 4);
-    DevGsLevels lv; std::memset(&lv, 0, sizeof(lv));
-    int lvl[SDQH_SORT_MAX_KEYS + 1];
-    int64_t g = 0;
-    for (int L = top; L >= 0; --L) if ((levels >> L) & 1u) { lvl[lv.n] = L; g += (int64_t)tot[L]; lv.off[++lv.n] = (uint32_t)g; }
-    if (g > 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 groups over the levels asked for");
-    if (r.step.level_rows) for (int L = 0; L <= SDQH_SORT_MAX_KEYS; ++L) r.step.level_rows[L] = (L < nl && ((levels >> L) & 1u)) ? (int64_t)tot[L] : 0;
-    r.m = std::min<int64_t>(r.limit, g);
-    if (r.count_only) return r.done(r.m);
-    if (r.m > r.capacity) return r.overflow(r.m);
+    Levels p;
+    const int rc = level_sets(r, p);
+    if (rc || r.ended) return rc;
+    const DevGsLevels& lv = p.lv;
+    const uint32_t ntiles = p.ntiles; const unsigned tgrid = p.tgrid; const int64_t g = p.g;
+    const uint8_t* depth = p.depth;
     DevMoAggs mo = r.step.mo;
     if (!r.step.out) mo.n = mo.nmeas = mo.ncen = 0;                   // rows only: nothing is folded
     const size_t na = (size_t)mo.n, nm = (size_t)mo.nmeas, nc = (size_t)mo.ncen, gstride = round_up((size_t)g * 8) / 8;
@@ -2913,9 +2916,9 @@ static int step_moments(StepRun& r) {
             tcnt = c.take<uint32_t>(ntiles);
         })) return r.nomem();
     for (int k = 0; k < lv.n; ++k) {
-        const int L = lvl[k];
-        const uint32_t from = lv.off[k], ng = tot[L];
-        const uint32_t* toff = tcount + (size_t)L * ntiles;
+        const int L = p.lvl[k];
+        const uint32_t from = lv.off[k], ng = p.tot[L];
+        const uint32_t* toff = p.offsets(L);
         LAUNCH(ctx, "k_gd_heads", k_gd_heads, tgrid, L, depth, r.un, toff, ntiles, sel + from, gdepth + from, ng);
         if (!na) continue;
         // `cols` columns of doubles at `src`, one per row, summed per level-L group into `dst`: the frames' folds, four columns a launch
@@ -2957,8 +2960,8 @@ static int step_sessions(StepRun& r) {
         number |= sc.op[c] == SDQH_SS_NUMBER;
         rown |= !per && (sc.op[c] == SDQH_SS_ROW || sc.op[c] == SDQH_WSLIDE_FIRST || sc.op[c] == SDQH_WEX_AVG);
     }
-    const uint32_t ntiles = (uint32_t)((r.n + SORT_TILE - 1) / SORT_TILE);
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
+    const Tiles t(r.n);
+    const uint32_t ntiles = t.ntiles; const unsigned tgrid = t.tgrid;
     uint8_t *headsA = nullptr, *headsB = nullptr, *depth = nullptr; WinCarry *carryA = nullptr, *carryB = nullptr; WaggHeads *tfirst = nullptr, *tnext = nullptr;
     uint32_t *tcount = nullptr, *ltot = nullptr, *numb = nullptr, *rowb = nullptr, *tile_kept = nullptr;
     uint64_t *elem = nullptr, *fin = nullptr, *tval = nullptr;
@@ -2992,28 +2995,20 @@ static int step_sessions(StepRun& r) {
             LAUNCH(ctx, "k_win_scan", k_win_scan, 1, carryB, ntiles);
             LAUNCH(ctx, "k_win_rank", k_win_rank, tgrid, headsB, carryB, r.un, (int)SDQH_WIN_ROW_NUMBER, ~0ull, rowb, tile_kept, ntiles);
         }
-        if (nf) {
-            LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, headsB, r.un, r.stride, elem, tval, tfirst, ntiles);
-            LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)nf, ag, tfirst, r.un, tval, ntiles);
-            LAUNCH(ctx, "k_wagg_run", k_wagg_run, tgrid, ag, headsB, r.un, r.stride, elem, tval, ntiles);
-        }
-        const uint32_t mtiles = (uint32_t)((r.m + SORT_TILE - 1) / SORT_TILE);
+        if (nf) tile_fold(r, t, ag, headsB, elem, tval, tfirst, true);
+        const Tiles mt(r.m);                                          // (the returned rows' tiles)
         LAUNCH(ctx, "k_wagg_next", k_wagg_next, 1, tfirst, r.un, tnext, ntiles);
-        LAUNCH(ctx, "k_ss_rows", k_ss_rows, (mtiles + TPB / WAVE - 1) / (TPB / WAVE), r.table->stage, sc, r.s.refs, r.s.perm, headsB, tnext, numb, rowb, r.un, (uint32_t)r.m,
-               r.stride, elem, fin, mtiles);
+        LAUNCH(ctx, "k_ss_rows", k_ss_rows, mt.tgrid, r.table->stage, sc, r.s.refs, r.s.perm, headsB, tnext, numb, rowb, r.un, (uint32_t)r.m,
+               r.stride, elem, fin, mt.ntiles);
         r.columns(fin, sc.n);
         return SDQH_OK;
     }
-    LAUNCH(ctx, "k_sort_bins", k_sort_bins, 3, tcount, ntiles, ltot);  // per level: the tiles' offsets in place, the level's count
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, ltot, 3 * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (int rc = sync_stream(ctx)) return rc;
-    uint32_t tot[3];
-    std::memcpy(tot, ctx->result_host, sizeof(tot));
+    uint32_t tot[3];                                                   // the level pass's counts over k_ss_heads' three levels: level 2 is the sessions
+    if (int rc = level_counts(r, tcount, ntiles, ltot, 3, tot)) return rc;
     const int64_t g = (int64_t)tot[2];
     if (g >= 0xFFFFFFFFll) return fail(ctx, SDQH_ERR_UNSUPPORTED, r.me + ": more than 2^32 - 1 sessions");      // (a selection holds fewer rows: never taken)
-    r.m = std::min<int64_t>(r.limit, g);
-    if (r.count_only) return r.done(r.m);
-    if (r.m > r.capacity) return r.overflow(r.m);
+    const int rc = r.counted(g);
+    if (rc || r.ended) return rc;
     const size_t gstride = round_up((size_t)g * 8) / 8;
     uint32_t* sel = nullptr; uint8_t* gdepth = nullptr; uint64_t *sums = nullptr, *val = nullptr;
     if (!carve(ctx, r.scratch.p[4], [&](Carver& c) {
@@ -3024,10 +3019,7 @@ static int step_sessions(StepRun& r) {
             elem = c.take<uint64_t>(r.stride * nf);
             tval = c.take<uint64_t>((size_t)ntiles * nf);
         })) return r.nomem();
-    if (nf) {
-        LAUNCH(ctx, "k_wagg_tiles", k_wagg_tiles, tgrid, r.table->stage, ag, r.s.refs, r.s.perm, headsB, r.un, r.stride, elem, tval, tfirst, ntiles);
-        LAUNCH(ctx, "k_wagg_scan", k_wagg_scan, (unsigned)nf, ag, tfirst, r.un, tval, ntiles);
-    }
+    if (nf) tile_fold(r, t, ag, headsB, elem, tval, tfirst, false);
     LAUNCH(ctx, "k_gs_run", k_gs_run, tgrid, ag, 2, 1, depth, (const uint32_t*)nullptr, elem, r.stride, r.un, tval, tcount + (size_t)2 * ntiles, ntiles,
            sums, gstride, gdepth, sel, tot[2]);
     if (nc) LAUNCH(ctx, "k_ss_sessions", k_ss_sessions, r.row_grid(), r.table->stage, sc, r.s.refs, r.s.perm, sel, numb, r.un, tot[2], (uint32_t)r.m, gstride, sums, val);
@@ -3036,52 +3028,30 @@ static int step_sessions(StepRun& r) {
     return SDQH_OK;
 }
 
-// Second moments over frames (sdqh_table_window_moments): block 3 = step_excludes' [partition pass | partition ends | dense ranks | kept
-// per tile | VALUE keys | GROUPS keys] — the frames are found as there, with nothing excluded — then [component trees: S and Q per
-// distinct measure, C per distinct pair | values].  k_wrg_stage runs over the image of COUNT ranges: it stages the ends and the keys alone.
+// Second moments over frames (sdqh_table_window_moments): block 3 = [frame pass | component trees: S and Q per distinct measure, C per
+// distinct pair | values].  The frames are found as step_excludes finds them, with nothing excluded; the image is one of COUNT ranges,
+// so the frame pass stages the ends and the keys alone (no fold tree of its own: f.tstride is 0, and the component trees are this step's).
 static int step_wmoments(StepRun& r) {
-    const int64_t n = r.n;
     DevWmos mo = r.step.wm;
     DevWranges& rg = mo.rg;
-    const size_t na = (size_t)rg.n;
-    bool groups = false;
-    for (size_t a = 0; a < na; ++a) {
-        DevWrange& d = rg.a[a];
-        groups |= d.unit == SDQH_WRANGE_GROUPS;
-        if (d.unit == SDQH_WEX_ROWS) {                                 // an offset of n or more reaches outside every partition: clamped, as a slide's is
-            d.lo = std::max<int64_t>(std::min<int64_t>(d.lo, n), -n);
-            d.hi = std::max<int64_t>(std::min<int64_t>(d.hi, n), -n);
-        }
-    }
-    uint64_t cap = SORT_TILE;                                          // the trees' leaf count: the power of two at or above n
-    while (cap < (uint64_t)n) cap <<= 1;
+    Frames f(rg, r.n, nullptr);
+    const Partitions& p = f.p;
+    const uint64_t cap = f.cap;
     const size_t tstride = (size_t)(2 * cap), ntrees = (size_t)(2 * mo.nmeas + mo.npairs);
-    Partitions p;
-    uint32_t *pend = nullptr, *dense = nullptr, *tile_kept = nullptr;
-    uint64_t *vkey = nullptr, *gkey = nullptr, *tree = nullptr, *fin = nullptr;
+    uint64_t *tree = nullptr, *fin = nullptr;
     if (!carve(r.ctx, r.scratch.p[3], [&](Carver& c) {
-            p.take(c, n, true, true, true);
-            pend = c.take<uint32_t>((size_t)n);
-            dense = c.take<uint32_t>(groups ? (size_t)n : 0);
-            tile_kept = c.take<uint32_t>(groups ? p.ntiles : 0);
-            vkey = c.take<uint64_t>(rg.vcol >= 0 ? (size_t)n : 0);
-            gkey = c.take<uint64_t>(groups ? (size_t)n : 0);
+            f.take(c, r.n, rg);
             tree = c.take<uint64_t>(tstride * ntrees);
-            fin = c.take<uint64_t>(r.stride * na);
+            fin = c.take<uint64_t>(r.stride * (size_t)rg.n);
         })) return r.nomem();
-    if (rg.vcol < 0) vkey = nullptr;
-    if (!groups) { dense = nullptr; gkey = nullptr; }
-    partition_pass(r, p, PP_HEADS | PP_SCAN | PP_ROWS | PP_NEXT);
-    if (groups) LAUNCH(r.ctx, "k_win_rank", k_win_rank, p.tgrid, p.heads, p.carry, r.un, (int)SDQH_WIN_DENSE_RANK, ~0ull, dense, tile_kept, p.ntiles);
-    LAUNCH(r.ctx, "k_wrg_stage", k_wrg_stage, p.tgrid, r.table->stage, rg, r.s.refs, r.s.perm, p.heads, p.tnext, rg.vcol >= 0 ? r.s.keys + (size_t)rg.vcol * r.s.key_stride : nullptr, dense, r.un,
-           r.stride, (size_t)0, cap, pend, vkey, gkey, (uint64_t*)nullptr, (uint64_t*)nullptr, p.ntiles);
+    frame_pass(r, f, rg, nullptr, nullptr);
     LAUNCH(r.ctx, "k_wmo_stage", k_wmo_stage, p.tgrid, r.table->stage, mo, r.s.refs, r.s.perm, r.un, tstride, cap, tree, p.ntiles);
     LAUNCH(r.ctx, "k_wmo_tiles", k_wmo_tiles, p.tgrid, mo, r.un, tstride, cap, tree, p.ntiles);
     if (cap > (uint64_t)SORT_TILE) {
         LAUNCH(r.ctx, "k_wmo_upper", k_wmo_upper, (unsigned)mo.nmeas, mo, 0, tstride, cap, tree, p.ntiles);
         if (mo.npairs) LAUNCH(r.ctx, "k_wmo_upper", k_wmo_upper, (unsigned)mo.npairs, mo, 1, tstride, cap, tree, p.ntiles);
     }
-    LAUNCH(r.ctx, "k_wmo_fold", k_wmo_fold, r.row_grid(), mo, p.rown, pend, vkey, gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, tree, fin);
+    LAUNCH(r.ctx, "k_wmo_fold", k_wmo_fold, r.row_grid(), mo, p.rown, f.pend, f.vkey, f.gkey, r.un, (uint32_t)r.m, r.stride, tstride, cap, tree, fin);
     r.columns(fin, rg.n);
     return SDQH_OK;
 }
@@ -3184,7 +3154,7 @@ static int sort_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, b
 static bool sort_args_ok(const void* terms, int nterms, int64_t limit, int64_t capacity, const int64_t* out_n) {
     return out_n && terms && nterms >= 1 && nterms <= SDQH_SORT_MAX_KEYS && limit >= 1 && capacity >= 0;
 }
-// ... and what the five window entry points do before they look at their columns: the arguments they share tested with `own` (the
+// ... and what every entry point with a step does before it looks at its columns: the arguments they share tested with `own` (the
 // entry point's conditions on the rest), sort_enter, the terms marshalled
 static int window_enter(sdqh_ctx* ctx, const sdqh_table* table, const char* who, int npartition, int nterms, const sdqh_sort_term* in, int64_t limit, int64_t capacity,
                         const int64_t* out_n, bool own, DevSortTerm* terms) {
@@ -3206,6 +3176,40 @@ static int fold_class(int op, int is_f64, bool folding_ops_only) {
     if (op == SDQH_WAGG_MIN || op == SDQH_WAGG_MAX) return WAGG_UMAX;
     if (op != SDQH_WAGG_SUM) return folding_ops_only ? WAGG_ADD_I : WSL_NONE;
     return is_f64 ? WAGG_ADD_F : WAGG_ADD_I;
+}
+// The frame of a column of the entry points whose frames depend on the data (ranges, excludes, moments over frames), and what they
+// demand of it behind their own tests of op, unit and flags: a VALUE frame (`value`: is there one?) takes exactly one ORDER BY term
+// (read here, so: is it there?), one with arithmetic; offsets over a double term are finite; no frame ends before it begins.
+struct FrameEnds { int unit, flags; int64_t lo, hi; };
+static bool frame_bounds_ok(const FrameEnds* cols, int ncols, const sdqh_sort_term* in, int npartition, int nterms, bool& value) {
+    value = false;
+    for (int c = 0; c < ncols; ++c) value |= cols[c].unit == SDQH_WRANGE_VALUE;
+    bool ok = true, vf64 = false;
+    if (value) {
+        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
+        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
+    }
+    for (int c = 0; ok && c < ncols; ++c) {
+        const FrameEnds& g = cols[c];
+        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
+        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
+            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
+            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
+            ok = lo_ok && hi_ok && !(both && lo > hi);
+        } else ok = !(both && g.lo > g.hi);
+    }
+    return ok;
+}
+// ... and the head of their DevWranges image: the column count and the VALUE frames' ORDER BY term, its direction and type
+static void frame_image(DevWranges& rg, int ncols, bool value, int npartition, const DevSortTerm* terms) {
+    rg.n = ncols;
+    rg.vcol = value ? npartition : -1; rg.vdesc = value ? terms[npartition].sk.desc : 0; rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+}
+// a measure's place among the n distinct ones of a moments call (columns naming the same measure share it)
+static int measure_slot(DevSortKey* sk, int32_t& n, const DevSortKey& m) {
+    for (int k = 0; k < n; ++k) if (sk[k].kind == m.kind && sk[k].index == m.index && sk[k].is_f64 == m.is_f64) return k;
+    sk[n] = m;
+    return n++;
 }
 
 int sdqh_table_sorted(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_hits, int64_t limit, int nsort, const sdqh_sort_key* sort,
@@ -3285,33 +3289,19 @@ int sdqh_table_window_range(sdqh_ctx* ctx, const sdqh_table* table, int64_t min_
                             int nranges, const sdqh_window_range* ranges, int64_t limit, int64_t capacity,
                             int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_aggs, int64_t* out_n) {
     const char* who = "table_window_range";
-    bool ok = ranges && nranges >= 1 && nranges <= SDQH_WRANGE_MAX_AGGS;
-    bool value = false;
+    bool ok = ranges && nranges >= 1 && nranges <= SDQH_WRANGE_MAX_AGGS, value = false;
+    FrameEnds ends[SDQH_WRANGE_MAX_AGGS];
     for (int a = 0; ok && a < nranges; ++a) {
         const sdqh_window_range& g = ranges[a];
         ok = g.op >= SDQH_WAGG_SUM && g.op <= SDQH_WSLIDE_LAST && (g.unit == SDQH_WRANGE_VALUE || g.unit == SDQH_WRANGE_GROUPS) &&
              !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+        ends[a] = FrameEnds{g.unit, g.flags, g.lo, g.hi};
     }
-    bool vf64 = false;
-    if (ok && value) {                                                // exactly one ORDER BY term (read here, so: is it there?), and one with arithmetic
-        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
-        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
-    }
-    for (int a = 0; ok && a < nranges; ++a) {
-        const sdqh_window_range& g = ranges[a];
-        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
-            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
-            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
-            ok = lo_ok && hi_ok && !(both && lo > hi);
-        } else ok = !(both && g.lo > g.hi);
-    }
+    ok = ok && frame_bounds_ok(ends, nranges, in, npartition, nterms, value);
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
     SortStep st = sort_step(STEP_RANGES, npartition, out_aggs);
-    st.rg.n = nranges;
-    st.rg.vcol = value ? npartition : -1; st.rg.vdesc = value ? terms[npartition].sk.desc : 0; st.rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    frame_image(st.rg, nranges, value, npartition, terms);
     for (int a = 0; a < nranges; ++a) {
         const sdqh_window_range& g = ranges[a];
         DevWrange& d = st.rg.a[a];
@@ -3362,34 +3352,20 @@ int sdqh_table_window_exclude(sdqh_ctx* ctx, const sdqh_table* table, int64_t mi
                               int ncols, const sdqh_window_exclude* cols, int64_t limit, int64_t capacity,
                               int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
     const char* who = "table_window_exclude";
-    bool ok = cols && ncols >= 1 && ncols <= SDQH_WEX_MAX_COLS;
-    bool value = false;
+    bool ok = cols && ncols >= 1 && ncols <= SDQH_WEX_MAX_COLS, value = false;
+    FrameEnds ends[SDQH_WEX_MAX_COLS];
     for (int c = 0; ok && c < ncols; ++c) {
         const sdqh_window_exclude& g = cols[c];
         ok = g.op >= SDQH_WAGG_SUM && g.op <= SDQH_WEX_AVG && g.unit >= SDQH_WRANGE_VALUE && g.unit <= SDQH_WEX_ROWS &&
              g.exclude >= SDQH_WEX_NO_OTHERS && g.exclude <= SDQH_WEX_TIES && g._pad == 0 && !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+        ends[c] = FrameEnds{g.unit, g.flags, g.lo, g.hi};
     }
-    bool vf64 = false;
-    if (ok && value) {                                                // sdqh_table_window_range's demand of a VALUE frame: one ORDER BY term, with arithmetic
-        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
-        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
-    }
-    for (int c = 0; ok && c < ncols; ++c) {
-        const sdqh_window_exclude& g = cols[c];
-        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
-            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
-            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
-            ok = lo_ok && hi_ok && !(both && lo > hi);
-        } else ok = !(both && g.lo > g.hi);
-    }
+    ok = ok && frame_bounds_ok(ends, ncols, in, npartition, nterms, value);
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
     SortStep st = sort_step(STEP_EXCLUDES, npartition, out_cols);
     DevWranges& rg = st.ex.rg;
-    rg.n = ncols;
-    rg.vcol = value ? npartition : -1; rg.vdesc = value ? terms[npartition].sk.desc : 0; rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
+    frame_image(rg, ncols, value, npartition, terms);
     for (int c = 0; c < ncols; ++c) {
         const sdqh_window_exclude& g = cols[c];
         DevWrange& d = rg.a[c];
@@ -3473,12 +3449,7 @@ int sdqh_table_group_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min
     st.levels = levels; st.level_rows = out_level_rows;
     DevMoAggs& mo = st.mo;
     mo.n = ok ? naggs : 0;
-    // a measure's column among the distinct ones (aggregates naming the same measure share it), and a product's among pass 2's
-    auto measure = [&](const DevSortKey& sk) {
-        for (int k = 0; k < mo.nmeas; ++k) if (mo.sk[k].kind == sk.kind && mo.sk[k].index == sk.index && mo.sk[k].is_f64 == sk.is_f64) return k;
-        mo.sk[mo.nmeas] = sk;
-        return mo.nmeas++;
-    };
+    // a product's column among pass 2's (a measure's among the distinct ones: measure_slot)
     auto product = [&](int i, int j) {
         if (i > j) std::swap(i, j);
         for (int c = 0; c < mo.ncen; ++c) if (mo.ci[c] == i && mo.cj[c] == j) return c;
@@ -3493,7 +3464,7 @@ int sdqh_table_group_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t min
         if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind, g.index, g.is_f64, y)) return rc;
         if (two) if (int rc = measure_set(ctx, table, who, "aggregate", a, g.kind2, g.index2, g.is_f64_2, x)) return rc;
         mo.op[a] = g.op;
-        mo.my[a] = measure(y); mo.mx[a] = two ? measure(x) : mo.my[a];
+        mo.my[a] = measure_slot(mo.sk, mo.nmeas, y); mo.mx[a] = two ? measure_slot(mo.sk, mo.nmeas, x) : mo.my[a];
         mo.qy[a] = mo.qx[a] = mo.cc[a] = -1;
         if (!two) mo.qy[a] = product(mo.my[a], mo.my[a]);
         else {
@@ -3511,41 +3482,22 @@ int sdqh_table_window_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t mi
                               int ncols, const sdqh_window_moment* cols, int64_t limit, int64_t capacity,
                               int64_t* out_keys, int64_t* out_payload, double* out_values, int64_t* out_hits, int64_t* out_cols, int64_t* out_n) {
     const char* who = "table_window_moments";
-    bool ok = cols && ncols >= 1 && ncols <= SDQH_WM_MAX_COLS;
-    bool value = false;
+    bool ok = cols && ncols >= 1 && ncols <= SDQH_WM_MAX_COLS, value = false;
+    FrameEnds ends[SDQH_WM_MAX_COLS];
     for (int c = 0; ok && c < ncols; ++c) {
         const sdqh_window_moment& g = cols[c];
         ok = g.op >= SDQH_GM_VAR_POP && g.op <= SDQH_GM_REGR_INTERCEPT && g.unit >= SDQH_WRANGE_VALUE && g.unit <= SDQH_WEX_ROWS && g._pad == 0 &&
              !(g.flags & ~(SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        value |= ok && g.unit == SDQH_WRANGE_VALUE;
+        ends[c] = FrameEnds{g.unit, g.flags, g.lo, g.hi};
     }
-    bool vf64 = false;
-    if (ok && value) {                                                // sdqh_table_window_range's demand of a VALUE frame: one ORDER BY term, with arithmetic
-        ok = in && npartition >= 0 && nterms == npartition + 1 && in[npartition].ranks == nullptr;
-        if (ok) vf64 = column_is_f64(in[npartition].kind, in[npartition].is_f64) != 0;
-    }
-    for (int c = 0; ok && c < ncols; ++c) {
-        const sdqh_window_moment& g = cols[c];
-        const bool both = !(g.flags & (SDQH_WRANGE_LO_UNBOUNDED | SDQH_WRANGE_HI_UNBOUNDED));
-        if (g.unit == SDQH_WRANGE_VALUE && vf64) {
-            double lo, hi; std::memcpy(&lo, &g.lo, 8); std::memcpy(&hi, &g.hi, 8);
-            const bool lo_ok = (g.flags & SDQH_WRANGE_LO_UNBOUNDED) || std::isfinite(lo), hi_ok = (g.flags & SDQH_WRANGE_HI_UNBOUNDED) || std::isfinite(hi);
-            ok = lo_ok && hi_ok && !(both && lo > hi);
-        } else ok = !(both && g.lo > g.hi);
-    }
+    ok = ok && frame_bounds_ok(ends, ncols, in, npartition, nterms, value);
     DevSortTerm terms[SDQH_SORT_MAX_KEYS];
     if (int rc = window_enter(ctx, table, who, npartition, nterms, in, limit, capacity, out_n, ok, terms)) return rc;
     SortStep st = sort_step(STEP_WMOMENTS, npartition, out_cols);
     DevWmos& mo = st.wm;
     DevWranges& rg = mo.rg;
-    rg.n = ncols;
-    rg.vcol = value ? npartition : -1; rg.vdesc = value ? terms[npartition].sk.desc : 0; rg.vf64 = value ? terms[npartition].sk.is_f64 : 0;
-    // a measure's trees among the distinct ones (columns naming the same measure share them), and a pair's C tree among the pairs
-    auto measure = [&](const DevSortKey& sk) {
-        for (int k = 0; k < mo.nmeas; ++k) if (mo.sk[k].kind == sk.kind && mo.sk[k].index == sk.index && mo.sk[k].is_f64 == sk.is_f64) return k;
-        mo.sk[mo.nmeas] = sk;
-        return mo.nmeas++;
-    };
+    frame_image(rg, ncols, value, npartition, terms);
+    // a pair's C tree among the pairs (a measure's trees among the distinct ones: measure_slot — columns naming the same measure share them)
     auto pair_of = [&](int i, int j) {
         if (i == j) return -1;                                        // C of a measure with itself is its Q
         if (i > j) std::swap(i, j);
@@ -3563,7 +3515,7 @@ int sdqh_table_window_moments(sdqh_ctx* ctx, const sdqh_table* table, int64_t mi
         if (int rc = measure_set(ctx, table, who, "column", c, g.kind, g.index, g.is_f64, y)) return rc;
         if (two) if (int rc = measure_set(ctx, table, who, "column", c, g.kind2, g.index2, g.is_f64_2, x)) return rc;
         DevWmoCol& a = mo.a[c];
-        a.op = g.op; a.my = measure(y); a.mx = two ? measure(x) : a.my;
+        a.op = g.op; a.my = measure_slot(mo.sk, mo.nmeas, y); a.mx = two ? measure_slot(mo.sk, mo.nmeas, x) : a.my;
         a.pair = two ? pair_of(a.my, a.mx) : -1;
     }
     return ordered_impl(ctx, const_cast<sdqh_table*>(table), who, min_hits, limit, nterms, terms, st, capacity, out_keys, out_payload, out_values, out_hits, out_n);
@@ -3647,7 +3599,8 @@ int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_
     const int width = text->width;
     const uint32_t* units = static_cast<const uint32_t*>(text->data);
     const uint32_t un = (uint32_t)nrows;
-    const uint32_t ntiles = (uint32_t)((nrows + SORT_TILE - 1) / SORT_TILE);
+    const Tiles t(nrows);
+    const uint32_t ntiles = t.ntiles;
     // one block: [masks | info | tile heads | keys | permutation x 2 | digit counts per tile | digit totals]
     uint32_t *masks = nullptr, *tile_heads = nullptr, *pa = nullptr, *pb = nullptr, *hist = nullptr, *bin_total = nullptr;
     unsigned long long* info = nullptr;
@@ -3687,15 +3640,14 @@ int sdqh_text_ranks(sdqh_ctx* ctx, const sdqh_column* text, int64_t nrows, sdqh_
         for (int b = 0; b < tw.nbytes; ++b) { tw.unit[b] = vunit[w * TEXT_WORD_BYTES + b]; tw.shift[b] = vshift[w * TEXT_WORD_BYTES + b]; }
         LAUNCH(ctx, "k_text_pack", k_text_pack, pgrid, units, (uint64_t)nrows, width, tw, key);
         for (int b = tw.nbytes - 1; b >= 0; --b) {
-            radix_pass(ctx, key, perm, un, 56 - 8 * b, hist, bin_total, ntiles, pa);
+            radix_pass(ctx, key, perm, un, 56 - 8 * b, hist, bin_total, t, pa);
             perm = pa; std::swap(pa, pb);
         }
     }
     // (d) dense ranks
-    const unsigned tgrid = (ntiles + TPB / WAVE - 1) / (TPB / WAVE);
-    LAUNCH(ctx, "k_rank_count", k_rank_count, tgrid, units, width, perm, un, tile_heads, ntiles);
+    LAUNCH(ctx, "k_rank_count", k_rank_count, t.tgrid, units, width, perm, un, tile_heads, ntiles);
     LAUNCH(ctx, "k_sort_scan", k_sort_scan, 1, tile_heads, (int)ntiles, info);
-    LAUNCH(ctx, "k_rank_place", k_rank_place, tgrid, units, width, perm, un, tile_heads, ntiles, static_cast<int64_t*>(rk->data));
+    LAUNCH(ctx, "k_rank_place", k_rank_place, t.tgrid, units, width, perm, un, tile_heads, ntiles, static_cast<int64_t*>(rk->data));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->result_host, info, 8, hipMemcpyDeviceToHost, ctx->stream));
     call_end(ctx);
     if (int rc = sync_stream(ctx)) return rc;
